@@ -22,6 +22,13 @@ import types
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+# The headline step runs in the library's deterministic mode (fixed-order folds instead of fp32 atomics): with the same arguments every run
+# computes the same bits, so the outputs --dump-outputs writes can be compared run to run and build to build.  In the default mode the
+# atomics' arrival order changes the last bits of a step, and 25 fp16 AdamW steps grow that into percent-level differences.  Cost at the
+# BERT-base configuration: 35.35 vs 34.65 ms per step (profiles/det_mode_step.txt).  MOREC_DETERMINISTIC=0 times the atomic kernels.
+# The secondary child lines keep the mode they were recorded in (atomics) unless the caller set the variable.
+_DET_SET_BY_CALLER = "MOREC_DETERMINISTIC" in os.environ
+os.environ.setdefault("MOREC_DETERMINISTIC", "1")
 
 import numpy as np
 import torch
@@ -29,6 +36,8 @@ import torch.distributed as dist
 
 MFMA_PEAK_TFLOPS = {"bf16": 2500.0, "fp16": 2500.0, "f32": 157.3}   # /opt/skills/guides/MI355X_MICROARCH.md, dense
 HBM_PEAK_GBS = 8000.0
+DUMP_SAMPLE = 16384            # --dump-outputs: elements written of a larger tensor (a fixed sample)
+DUMP_MAX_BYTES = 64 * 10 ** 6       # --dump-outputs: all files together, .npy headers included
 
 
 def parse():
@@ -71,6 +80,13 @@ def parse():
                     "with the backward or after it -- and print each configuration's bucket trace under `sweep` (schema: INTEGRATION.md)")
     ap.add_argument("--launch-check", action="store_true", help="rendezvous only: every rank joins the process group, rank 0 prints the "
                     "world size it observed as one JSON line and exits (no GPU work; used by the CPU test of the N > 1 launch path)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed region, write what its last step computed to DIR/<name>.npy "
+                    "(rank 0): loss.npy (float64), and for every trained parameter param.<name>.npy (its value after the update) and "
+                    f"grad.<name>.npy (the step's gradient, loss scale divided out), float32.  A tensor of more than {DUMP_SAMPLE} elements is "
+                    "written as a fixed sample: the flat indices np.unique(np.random.default_rng(zlib.crc32(name.encode())).integers(0, numel, "
+                    f"{DUMP_SAMPLE})).  At most {DUMP_MAX_BYTES // 10 ** 6} MB in all.  The inputs are seeded; in the deterministic mode, "
+                    "which bench.py turns on for the headline step unless MOREC_DETERMINISTIC is set, a text / ID step and its dump are bit-reproducible.  "
+                    "(bench_outputs/ is git-ignored for this.)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-timeout", type=int, default=150)
     a = ap.parse_args()
@@ -201,6 +217,33 @@ def _pci_bdf(dev):
         return None
 
 
+def dump_outputs(path, loss, ts):
+    """--dump-outputs: what the last step of the timed region handed back -- its loss and, for every trained parameter, the updated value
+    and the gradient it was updated from -- as float .npy files, so that two builds can be compared output for output."""
+    import zlib
+    ts.flush()
+    torch.cuda.synchronize()
+    inv_scale = np.float32(ts.sp.host().inv_scale) if ts.sp is not None else np.float32(1.0)    # the scale the step's gradients carry
+    arrays = {"loss": np.array([float(loss.item())], dtype=np.float64)}
+    for grp in ts.groups:
+        a = grp["arena"]
+        for name, (o, n, _) in a.offsets.items():
+            sel = None
+            if n > DUMP_SAMPLE:
+                idx = np.unique(np.random.default_rng(zlib.crc32(name.encode())).integers(0, n, DUMP_SAMPLE))
+                sel = torch.from_numpy(idx).to(a.data.device)
+            for kind, buf, scale in (("param", a.data, np.float32(1.0)), ("grad", a.grad, inv_scale)):
+                v = buf[o:o + n] if sel is None else buf[o:o + n][sel]
+                arrays[f"{kind}.{name}"] = v.float().cpu().numpy() * scale
+    total = sum(v.nbytes + 128 for v in arrays.values())      # (a .npy header of these shapes is 128 bytes)
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs exceed {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return len(arrays), total
+
+
 def main():
     a = parse()
     if a.cpu_baseline_only:
@@ -249,6 +292,7 @@ def main():
 
     from idvs.morec_amd import engine as _engine
     from idvs.morec_amd import ops
+    from idvs.morec_amd._lib import env_flag as _lib_env_flag
     from idvs.morec_amd.model import BertShape, HipBertModel, Model
     if a.padded:
         _engine.UNPAD_DEFAULT = False
@@ -506,6 +550,9 @@ def main():
     dt = float(t.item())
     loss_v = float(loss.item())
     log(f"timed region done: {dt / a.steps * 1e3:.2f} ms/step")
+    if a.dump_outputs and rank == 0:        # before any later pass steps the model again
+        n_arr, n_bytes = dump_outputs(a.dump_outputs, loss, ts)
+        log(f"outputs of the last timed step: {n_arr} arrays, {n_bytes / 1e6:.1f} MB in {a.dump_outputs}")
     # ---- N > 1: the headline is measured; everything from here on (traced step, reduced sweep, instrumented pass) is explanation.  No
     # multi-GPU run of this file has ever happened on hardware, and a collective that hangs in that part would take the measured line
     # with it: a watchdog prints the headline alone and ends every rank if the rest does not finish in time (MOREC_BENCH_WATCHDOG_S,
@@ -919,8 +966,9 @@ def main():
         import subprocess
 
         def child(extra, timeout=240):
+            env = None if _DET_SET_BY_CALLER else dict(os.environ, MOREC_DETERMINISTIC="0")
             r = subprocess.run([sys.executable, os.path.abspath(__file__)] + extra + ["--no-cpu-baseline", "--no-secondary"],
-                               capture_output=True, text=True, timeout=timeout)
+                               capture_output=True, text=True, timeout=timeout, env=env)
             return json.loads(r.stdout.strip().splitlines()[-1])
 
         other16 = "bf16" if a.dtype16 == "fp16" else "fp16"
@@ -938,6 +986,7 @@ def main():
             try:
                 vj = child(extra if "--dtype" in extra else extra + ["--dtype", a.dtype16])
                 out[key] = {"ms_per_step": vj["ms_per_step"], "user_seq_per_s": vj["value"], "dtype": vj["dtype"], "config": vj["config"]["workload"],
+                            "deterministic": vj["config"].get("deterministic"),
                             "gemm_roofline_frac": vj.get("roofline", {}).get("frac"),
                             "note": "python bench.py " + " ".join(extra)}
                 if per_seq:
@@ -989,6 +1038,7 @@ def main():
                          "seq_len": S + 1, "parallelism": out["config"]["parallelism"],
                          "dropout": "on (SASRec p = 0.1; Swin DropPath 0 -> 0.1 linear, per-image scales from the counter-based RNG)"}
 
+    out["config"]["deterministic"] = _lib_env_flag("MOREC_DETERMINISTIC")
     if rank == 0 and not a.no_cpu_baseline and (vision or id_tower):
         out["cpu_baseline"] = {"value": None, "unit": "user-seq/s", "cores": None, "kind": "port",
                                "sample": "not measured for the vision tower (the BASELINE.json metric is the text tower)"}

@@ -94,25 +94,36 @@ extern "C" int morec_det_scratch_reserve(size_t n_floats, void* stream) {
     return det_scratch_impl(reinterpret_cast<hipStream_t>(stream), n_floats, true) ? MOREC_OK : (int)hipErrorOutOfMemory;
 }
 
+// 16 columns x 16 partial groups per block: group g sums the partials g, g + 16, ... in four chains, then thread g == 0 of each column adds
+// the 16 group sums in group order -- a fixed summation order, and 16x fewer dependent loads per thread than one thread per column (a
+// LayerNorm fold of ~500 partial rows took 36 us as one thread per column: profiles/det_mode_step.txt)
 __global__ __launch_bounds__(256) void det_fold_add_kernel(const float* __restrict__ part, float* __restrict__ dst, int n_parts, size_t n, size_t stride) {
-    for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < n; j += (size_t)gridDim.x * blockDim.x) {
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;      // four chains for the memory latency; their combination order is fixed as well
-        int p = 0;
-        for (; p + 4 <= n_parts; p += 4) {
+    __shared__ float red[16][17];
+    const int c = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const size_t j = blockIdx.x * (size_t)16 + c;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    if (j < n) {
+        int p = g;
+        for (; p + 48 < n_parts; p += 64) {
             a0 += part[(size_t)p * stride + j];
-            a1 += part[(size_t)(p + 1) * stride + j];
-            a2 += part[(size_t)(p + 2) * stride + j];
-            a3 += part[(size_t)(p + 3) * stride + j];
+            a1 += part[(size_t)(p + 16) * stride + j];
+            a2 += part[(size_t)(p + 32) * stride + j];
+            a3 += part[(size_t)(p + 48) * stride + j];
         }
-        for (; p < n_parts; ++p) a0 += part[(size_t)p * stride + j];
-        dst[j] += (a0 + a1) + (a2 + a3);
+        for (; p < n_parts; p += 16) a0 += part[(size_t)p * stride + j];
+    }
+    red[g][c] = (a0 + a1) + (a2 + a3);
+    __syncthreads();
+    if (g == 0 && j < n) {
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) t += red[k][c];
+        dst[j] += t;
     }
 }
 int morec_det_fold_add(const float* part, float* dst, int n_parts, size_t n, size_t stride, hipStream_t s) {
     if (n == 0 || n_parts <= 0) return MOREC_OK;
-    size_t blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(det_fold_add_kernel, dim3((unsigned)blocks), dim3(256), 0, s, part, dst, n_parts, n, stride);
+    hipLaunchKernelGGL(det_fold_add_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, s, part, dst, n_parts, n, stride);
     MOREC_CHECK_LAUNCH();
     return MOREC_OK;
 }

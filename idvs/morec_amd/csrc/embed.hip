@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void word_scatter_kernel(const int32_t* __rest
 template <typename T, int CPL>   // CPL = float4 column groups per lane: H <= 256 * CPL
 __global__ __launch_bounds__(256) void word_scatter_sorted_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ order,
                                                                   const T* __restrict__ dz, float* __restrict__ dword, int pad_id,
-                                                                  int M, int H, int rows_per_wave) {
+                                                                  int M, int H, int rows_per_wave, float* __restrict__ part) {
     const int lane = threadIdx.x & 63;
     const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int i0 = w * rows_per_wave, i1 = min(M, i0 + rows_per_wave);
@@ -174,7 +174,10 @@ __global__ __launch_bounds__(256) void word_scatter_sorted_kernel(const int32_t*
         for (int q = 0; q < CPL; ++q) {
             const int c = (q * 64 + lane) * 4;
             if (c < H) {
-                if (shared_run) {
+                if (shared_run && part) {      // deterministic mode: this wave's share of the run, folded in wave order by word_scatter_fold_kernel
+                    float* pd = part + ((size_t)w * 2 + (cur == id_before ? 0 : 1)) * H + c;
+                    *reinterpret_cast<float4*>(pd) = make_float4(acc[q][0], acc[q][1], acc[q][2], acc[q][3]);
+                } else if (shared_run) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) atomicAdd(dst + c + k, acc[q][k]);
                 } else {
@@ -227,10 +230,57 @@ __global__ __launch_bounds__(256) void word_scatter_sorted_kernel(const int32_t*
     flush();
 }
 
+// Deterministic mode, second half of the sorted scatter: the run that crosses the end of a wave's rows is owned by the wave it starts in
+// (its share sits in slot 1 of that wave's partials); the owner adds the slot-0 shares of the following waves, in wave order, for as long as
+// the run continues, and writes the table row alone.  The waves' slots are written by word_scatter_sorted_kernel(part != nullptr).
+template <int CPL>
+__global__ __launch_bounds__(256) void word_scatter_fold_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ order,
+                                                                const float* __restrict__ part, float* __restrict__ dword, int pad_id,
+                                                                int M, int H, int rows_per_wave) {
+    const int lane = threadIdx.x & 63;
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int i0 = w * rows_per_wave, i1 = min(M, i0 + rows_per_wave);
+    if (i0 >= M) return;
+    const int id = ids[order[i1 - 1]];
+    if (id == pad_id || i1 >= M || ids[order[i1]] != id) return;                 // no run continues past this wave's rows
+    if (ids[order[i0]] == id && i0 > 0 && ids[order[i0 - 1]] == id) return;      // the run started in an earlier wave: not the owner
+    float acc[CPL][4];
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) {
+        const int c = (q * 64 + lane) * 4;
+        if (c < H) {
+            const float4 v = *reinterpret_cast<const float4*>(part + ((size_t)w * 2 + 1) * H + c);
+            acc[q][0] = v.x; acc[q][1] = v.y; acc[q][2] = v.z; acc[q][3] = v.w;
+        }
+    }
+    for (int w2 = w + 1;; ++w2) {      // the run continues into wave w2 (so w2's rows exist and start with this id)
+        const int j1 = min(M, (w2 + 1) * rows_per_wave);
+#pragma unroll
+        for (int q = 0; q < CPL; ++q) {
+            const int c = (q * 64 + lane) * 4;
+            if (c < H) {
+                const float4 v = *reinterpret_cast<const float4*>(part + ((size_t)w2 * 2) * H + c);
+                acc[q][0] += v.x; acc[q][1] += v.y; acc[q][2] += v.z; acc[q][3] += v.w;
+            }
+        }
+        if (j1 >= M || ids[order[j1 - 1]] != id || ids[order[j1]] != id) break;      // the run ends inside (or at the end of) wave w2
+    }
+    float* dst = dword + (size_t)id * H;
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) {
+        const int c = (q * 64 + lane) * 4;
+        if (c < H) {
+            float4 o = *reinterpret_cast<const float4*>(dst + c);
+            o.x += acc[q][0]; o.y += acc[q][1]; o.z += acc[q][2]; o.w += acc[q][3];
+            *reinterpret_cast<float4*>(dst + c) = o;
+        }
+    }
+}
+
 // Deterministic mode: ONE wave owns a table row.  The wave at sorted position i acts only when i starts a run of equal ids; it then sums
 // the run's rows in `order` (four rows in flight) and adds the total to the table row with a plain read-modify-write -- no other wave
 // touches that row, and the summation order is the (stable) sort order.  Long runs ([CLS] / [SEP]: one row per title) are serial in one
-// wave: slower than the atomics (~0.3 ms at B = 128), which is the price of the mode.
+// wave (4.7 ms per BERT-base step at B = 128, profiles/det_mode_step.txt): used only for rows wider than the sorted kernel takes (H > 1024).
 template <typename T>
 __global__ __launch_bounds__(256) void word_scatter_runs_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ order,
                                                                 const T* __restrict__ dz, float* __restrict__ dword, int pad_id, int M, int H) {
@@ -306,12 +356,21 @@ extern "C" int morec_bert_embed_bwd(const int32_t* ids, const void* dz, float* d
     // deterministic mode has no atomic fall-backs: it needs the token-id order (one writer wave per table row) and a row width the
     // vector kernel takes; anything else is refused instead of silently summing in arrival order
     if (det && (order == nullptr || !vec)) return MOREC_E_UNSUPPORTED;
+    // deterministic + sorted: the sorted kernel with per-wave partials for the runs that cross its rows, folded in wave order (two slots per wave)
+    float* part = nullptr;
+    if (det && sorted) {
+        part = morec_det_scratch(s, (size_t)2 * ((M + rpw - 1) / rpw) * H);
+        if (!part) return (int)hipErrorOutOfMemory;
+    }
     int rc_pos = 1;
     if (!by_dtype(dtype, [&](auto* t) {
             using T = MOREC_TAG_T(t);
-            if (det)
+            if (det && !sorted)
                 hipLaunchKernelGGL((word_scatter_runs_kernel<T>), g1, dim3(256), 0, s, ids, order, (const T*)dz, dword, pad_id, M, H);
-            else if (sorted) hipLaunchKernelGGL((word_scatter_sorted_kernel<T, 4>), g3, dim3(256), 0, s, ids, order, (const T*)dz, dword, pad_id, M, H, rpw);
+            else if (sorted) {
+                hipLaunchKernelGGL((word_scatter_sorted_kernel<T, 4>), g3, dim3(256), 0, s, ids, order, (const T*)dz, dword, pad_id, M, H, rpw, part);
+                if (part) hipLaunchKernelGGL((word_scatter_fold_kernel<4>), g3, dim3(256), 0, s, ids, order, (const float*)part, dword, pad_id, M, H, rpw);
+            }
             else hipLaunchKernelGGL((word_scatter_kernel<T>), g1, dim3(256), 0, s, ids, (const T*)dz, dword, pad_id, M, H);
             if (vec) rc_pos = pos_type_grad_launch<T>((const T*)dz, dpos, dtype0, M / T_, T_, H, s);
             else hipLaunchKernelGGL((pos_type_grad_scalar_kernel<T>), g2, dim3(256), 0, s, (const T*)dz, dpos, dtype0, M / T_, T_, H, spb);

@@ -82,3 +82,54 @@ def test_watchdog_prints_the_headline_alone():
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["world_size_observed"] == 2 and out["value"] > 0 and "watchdog" in out["post_headline"]
     assert abs(out["value"] - 32 * 1e3 / out["ms_per_step"]) < 1e-2 * out["value"]
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: after exactly --steps timed steps, the last step's loss and every trained parameter's updated value and gradient
+    land in DIR as float .npy files (large tensors as their fixed sample), within the size limit -- and, the headline step running in the
+    deterministic mode, a second run with the same arguments writes the same bits."""
+    import zlib
+
+    import numpy as np
+
+    def run(d):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--bert", "tiny", "--batch", "16", "--steps", "3", "--warmup", "2", "--no-secondary",
+                            "--no-cpu-baseline", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=250,
+                           env={k: v for k, v in _clean_env().items() if k != "MOREC_DETERMINISTIC"})
+        assert r.returncode == 0, r.stderr[-3000:]
+        return json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
+
+    d = tmp_path / "out"
+    out = run(d)
+    assert out["config"]["deterministic"] is True
+    # 2 warm-up + 3 timed + the instrumented pass after the headline (1 untimed + min(steps, 8) event-timed): the timed region ran 3 steps
+    assert out["steps"] == 3 and out["steps_executed"] == 2 + 3 + 1 + 3 and out["ms_per_step"] > 0
+    files = {f.name: np.load(f) for f in d.iterdir()}
+    assert sum(f.stat().st_size for f in d.iterdir()) <= 64 * 10 ** 6
+    assert all(v.dtype in (np.float32, np.float64) for v in files.values())
+    # final_loss is the loss of the last TIMED step (a warm-up step's loss would not match it)
+    assert files["loss.npy"].shape == (1,) and abs(float(files["loss.npy"][0]) - out["final_loss"]) < 1e-4
+    params = {k[len("param."):-len(".npy")] for k in files if k.startswith("param.")}
+    assert params and params == {k[len("grad."):-len(".npy")] for k in files if k.startswith("grad.")}
+    assert any("bert_model" in k for k in params) and any("user_encoder" in k for k in params)
+    for k in params:
+        p, g = files[f"param.{k}.npy"], files[f"grad.{k}.npy"]
+        assert p.shape == g.shape and p.ndim == 1 and np.isfinite(p).all()      # (an fp16 step may overflow: its gradient need not be finite)
+    # real gradients, not an empty buffer: most tensors carry finite, non-zero values
+    live = [k for k in params if np.isfinite(files[f"grad.{k}.npy"]).all() and np.abs(files[f"grad.{k}.npy"]).max() > 0]
+    assert len(live) >= 0.9 * len(params), sorted(set(params) - set(live))[:5]
+    # the word embeddings (vocab x H) are larger than the sample: the fixed, seeded sample of their flat indices
+    from idvs.morec_amd.model import BertShape
+    shp = BertShape.named("tiny")
+    w = "bert_encoder.text_encoders.title.bert_model.embeddings.word_embeddings.weight"
+    idx = np.unique(np.random.default_rng(zlib.crc32(w.encode())).integers(0, shp.vocab_size * shp.hidden_size, 16384))
+    assert files[f"param.{w}.npy"].shape == idx.shape
+    assert files["param.user_encoder.transformer_encoder.layer_norm.weight.npy"].shape == (512,)      # small tensors: whole
+    # same arguments, same bits
+    d2 = tmp_path / "again"
+    run(d2)
+    assert sorted(f.name for f in d2.iterdir()) == sorted(files)
+    differ = [k for k, v in files.items() if not np.array_equal(np.load(d2 / k), v)]
+    assert not differ, differ[:5]

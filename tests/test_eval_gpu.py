@@ -112,13 +112,13 @@ def test_encode_all_items_second_pass_allocates_nothing():
 
 
 @pytest.mark.parametrize("fused", [True, False])
-def test_run_driver_id_tower_learns(fused):
+def test_run_driver_id_tower_learns(fused, tmp_path):
     """A few dozen steps of the driver on synthetic data: the loss must fall (both optimisation paths)."""
     from idvs.morec_amd import run
     from idvs.morec_amd.parameters import parse_args
     argv = ["--synthetic", "1500", "--synthetic_items", "300", "--item_tower", "id", "--batch_size", "64", "--embedding_dim",
             "64", "--lr", "3e-3", "--l2_weight", "0.0", "--drop_rate", "0.1", "--epoch", "3", "--compute_dtype", "fp32",
-            "--local_rank", "0"] + (["--fused_step"] if fused else [])
+            "--local_rank", "0", "--checkpoint_root", str(tmp_path)] + (["--fused_step"] if fused else [])
     args = parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     run.setup_seed(12345)
@@ -126,19 +126,20 @@ def test_run_driver_id_tower_learns(fused):
     assert 0.0 <= best <= 1.0
 
 
-def test_run_driver_modal_tiny_steps():
+def test_run_driver_modal_tiny_steps(tmp_path):
     from idvs.morec_amd import run
     from idvs.morec_amd.parameters import parse_args
     args = parse_args(["--synthetic", "400", "--synthetic_items", "200", "--item_tower", "modal", "--bert_model_load", "bert_tiny",
                        "--freeze_paras_before", "0", "--batch_size", "32", "--embedding_dim", "128", "--lr", "1e-3",
-                       "--fine_tune_lr", "1e-4", "--epoch", "1", "--max_steps", "6", "--fused_step", "--local_rank", "0"])
+                       "--fine_tune_lr", "1e-4", "--epoch", "1", "--max_steps", "6", "--fused_step", "--local_rank", "0",
+                       "--checkpoint_root", str(tmp_path)])
     run.setup_seed(12345)
     best = run.train(args, True, 0)
     assert 0.0 <= best <= 1.0
 
 
 @pytest.mark.parametrize("fused", [True, False])
-def test_run_driver_vision_micro_steps(fused):
+def test_run_driver_vision_micro_steps(fused, tmp_path):
     """The driver in vision mode (V/run.py shape): uint8 image catalogue, on-device normalisation, Swin micro tower, the
     optimizer grouping of V/run.py:121-135, eval over the image catalogue."""
     from idvs.morec_amd import run
@@ -146,18 +147,19 @@ def test_run_driver_vision_micro_steps(fused):
     args = parse_args(["--synthetic", "300", "--synthetic_items", "120", "--item_tower", "modal", "--CV_model_load", "swin_micro",
                        "--CV_resize", "56", "--freeze_paras_before", "0", "--batch_size", "16", "--max_seq_len", "6",
                        "--embedding_dim", "64", "--lr", "1e-3", "--fine_tune_lr", "1e-4", "--epoch", "1", "--max_steps", "4",
-                       "--local_rank", "0"] + (["--fused_step"] if fused else []))
+                       "--local_rank", "0", "--checkpoint_root", str(tmp_path)] + (["--fused_step"] if fused else []))
     run.setup_seed(12345)
     best = run.train(args, True, 0)
     assert 0.0 <= best <= 1.0
 
 
-def test_run_driver_bce_loss_learns():
+def test_run_driver_bce_loss_learns(tmp_path):
     """The driver with the one-negative BCE loss of bce_text/main-end2end (ID tower): runs, evaluates, loss is finite."""
     from idvs.morec_amd import run
     from idvs.morec_amd.parameters import parse_args
     args = parse_args(["--synthetic", "1200", "--synthetic_items", "300", "--item_tower", "id", "--loss", "bce", "--batch_size", "64",
-                       "--embedding_dim", "64", "--lr", "3e-3", "--epoch", "2", "--compute_dtype", "fp32", "--local_rank", "0"])
+                       "--embedding_dim", "64", "--lr", "3e-3", "--epoch", "2", "--compute_dtype", "fp32", "--local_rank", "0",
+                       "--checkpoint_root", str(tmp_path)])
     run.setup_seed(12345)
     best = run.train(args, False, 0)
     assert 0.0 <= best <= 1.0

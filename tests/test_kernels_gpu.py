@@ -37,10 +37,9 @@ def rnd(*shape, dt=torch.float32, scale=1.0, seed=0):
     return (torch.randn(*shape, generator=g) * scale).to(DEV).to(dt)
 
 
-def test_probe_mfma_layouts():
+def test_probe_mfma_layouts(tmp_path):
     out = ops.probe().cpu().numpy()
-    os.makedirs("gpurun_out", exist_ok=True)
-    with open("gpurun_out/probe.txt", "w") as f:
+    with open(tmp_path / "probe.txt", "w") as f:
         f.write("bf16 16x16x32:\n%s\nf32 16x16x4:\n%s\ntr_b16 (lane: 4 values):\n%s\n" % (
             out[:256].reshape(64, 4), out[256:512].reshape(64, 4), out[512:768].reshape(64, 4)))
     lanes = np.arange(64)
