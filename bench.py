@@ -10,6 +10,12 @@ Workload: BASELINE.json configs[2] = SASRec + BERT-base, B = 128 user sequences 
 history 23), 30-token titles, D = 512, 2 heads, 2 blocks; fp16 MFMA operands / fp32 accumulate / fp32 master
 weights with the GradScaler protocol on the device (the reference runs fp16 autocast + GradScaler, T/run.py:210,242-247).
 Prints ONE JSON line on rank 0.
+
+A plain run does what its headline needs and nothing else: set up, warm up, time the K steps, write --dump-outputs, print the line.
+--full adds everything that explains the headline, after the timed region: at N > 1 a traced step and the data-parallel sweep; the
+instrumented pass behind `roofline`; the sustained rate with socket power; the padded-layout, item-dedup, fp32 / fp32x3 lines; the scoring
+kernels at the pooled size; the operand-activity probe; the eval pass; child runs of the other BASELINE.json configurations and
+precisions; the CPU baseline.
 """
 from __future__ import annotations
 
@@ -64,9 +70,9 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=8)
     ap.add_argument("--dedup", action="store_true", help="encode each distinct item of the batch once (SURVEY §8(f)-2; opt-in: with "
-                    "dropout on, duplicates then share a mask). The default run reports it as a secondary measurement only.")
+                    "dropout on, duplicates then share a mask). A --full run reports it as a secondary measurement only.")
     ap.add_argument("--padded", action="store_true", help="text tower: run the encoder layers on all T positions of every title (the "
-                    "reference's shape of compute) instead of the real tokens only; the default run reports it as a secondary line")
+                    "reference's shape of compute) instead of the real tokens only; a --full run reports it as a secondary line")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary (item-dedup) measurement after the timed region")
     ap.add_argument("--no-pool", action="store_true", help="rank-local negatives (reference behaviour) instead of the pooled set")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for single-GPU smoke tests)")
@@ -74,7 +80,7 @@ def parse():
     ap.add_argument("--graph", action="store_true", help="one rank: replay the step as a captured hipGraph (TrainStep.step_graphed; one graph per input "
                     "shape, the unpadded token layout padded to buckets of 512 rows) instead of launching its ~700 kernels from the host.  Opt-in: on "
                     "this stack a replayed graph keeps the 5-8 us dependency gap between consecutive kernels, so it buys little (DESIGN.md)")
-    ap.add_argument("--no-sweep", action="store_true", help="N > 1: skip the reduced default sweep (torch.distributed x reserved CUs x overlap)")
+    ap.add_argument("--no-sweep", action="store_true", help="N > 1: skip the reduced sweep of a --full run (torch.distributed x reserved CUs x overlap)")
     ap.add_argument("--sweep", action="store_true", help="N > 1: after the headline region, time the data-parallel knobs -- collectives through "
                     "torch.distributed vs the library's own RCCL communicators, 0 / 8 / 16 CUs reserved for the ring kernel, reduction overlapped "
                     "with the backward or after it -- and print each configuration's bucket trace under `sweep` (schema: INTEGRATION.md)")
@@ -87,9 +93,13 @@ def parse():
                     f"{DUMP_SAMPLE})).  At most {DUMP_MAX_BYTES // 10 ** 6} MB in all.  The inputs are seeded; in the deterministic mode, "
                     "which bench.py turns on for the headline step unless MOREC_DETERMINISTIC is set, a text / ID step and its dump are bit-reproducible.  "
                     "(bench_outputs/ is git-ignored for this.)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, run every pass that explains the headline (module docstring); "
+                    "--no-secondary, --no-cpu-baseline, --sweep and --no-sweep select among them.  Off: the headline line alone")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-timeout", type=int, default=150)
     a = ap.parse_args()
+    if a.sweep and not a.full:
+        ap.error("--sweep widens the sweep of a --full run: give --full too")
     a.dtype16 = a.dtype.split("_")[0]      # storage type of the GEMM operands ("fp16_res32" -> "fp16")
     return a
 
@@ -553,12 +563,15 @@ def main():
     if a.dump_outputs and rank == 0:        # before any later pass steps the model again
         n_arr, n_bytes = dump_outputs(a.dump_outputs, loss, ts)
         log(f"outputs of the last timed step: {n_arr} arrays, {n_bytes / 1e6:.1f} MB in {a.dump_outputs}")
+    # ---- What follows up to the result line explains the headline and runs with --full only; a plain run goes straight to its line.
+    # `secondary`: the part of a --full run that --no-secondary leaves out.
+    secondary = a.full and not a.no_secondary
     # ---- N > 1: the headline is measured; everything from here on (traced step, reduced sweep, instrumented pass) is explanation.  No
     # multi-GPU run of this file has ever happened on hardware, and a collective that hangs in that part would take the measured line
     # with it: a watchdog prints the headline alone and ends every rank if the rest does not finish in time (MOREC_BENCH_WATCHDOG_S,
     # default 240 s; 0 = off).
     watchdog = None
-    if world > 1:
+    if world > 1 and a.full:
         wd_s = float(os.environ.get("MOREC_BENCH_WATCHDOG_S", "240"))
         if wd_s > 0:
             import threading
@@ -635,16 +648,16 @@ def main():
 
     # ---- N > 1: one traced step, so that a scaling run explains itself
     keep_ce = (list(ce_log), list(ce_shapes))
-    reduce_trace = traced_step() if world > 1 else None
+    reduce_trace = traced_step() if world > 1 and a.full else None
     # ---- N > 1, --sweep: the knobs of the data-parallel step measured in ONE launch, so that the first multi-GPU run settles them:
     # {torch.distributed | the library's own RCCL communicators} x {CUs kept out of the GEMM grid during the backward: 0, 8, 16} x
     # {bucketed reduction overlapped with the backward | one sweep after it}.  Every configuration: 2 untimed + K timed steps between
     # barriers (max over ranks), then one traced step.  Schema: INTEGRATION.md "bench.py --sweep".
-    # Without --sweep (the driver's scaling runs) a REDUCED sweep still runs at N > 1: torch.distributed only -- no second communicator is
+    # Without --sweep a --full run still runs a REDUCED sweep at N > 1: torch.distributed only -- no second communicator is
     # created, nothing that could hang a run that has never been on > 1 GPU -- x {overlap, reserve 16 | overlap, reserve 0 | after the
     # backward}, so that the first real multi-GPU line already says what the reserved CUs and the bucket overlap are worth (--no-sweep: off).
     sweep = None
-    if world > 1 and (a.sweep or not a.no_sweep):
+    if world > 1 and a.full and (a.sweep or not a.no_sweep):
         sweep = []
         full = bool(a.sweep)
         base = (ts.comm, ts.comm_grad, ts._grad_stream, ts.reserve_cus, ts.overlap_reduce)
@@ -703,19 +716,20 @@ def main():
     n_inst = min(a.steps, 8)
     graph_was, use_graph["v"] = use_graph["v"], False      # the per-launch events need the launches: every pass from here on is eager
     wgrad_was = _engine.WgradStream.enabled
-    _engine.WgradStream.enabled = False
-    run_step(a.warmup)
-    torch.cuda.synchronize()
-    timing_on["v"] = True
-    for i in range(a.warmup, a.warmup + n_inst):
-        run_step(i)
-    torch.cuda.synchronize()
-    timing_on["v"] = False
-    _engine.WgradStream.enabled = wgrad_was
+    if a.full:
+        _engine.WgradStream.enabled = False
+        run_step(a.warmup)
+        torch.cuda.synchronize()
+        timing_on["v"] = True
+        for i in range(a.warmup, a.warmup + n_inst):
+            run_step(i)
+        torch.cuda.synchronize()
+        timing_on["v"] = False
+        _engine.WgradStream.enabled = wgrad_was
     # ---- sustained rate: the same K batches cycled for >= 3 s (the shader clock of a power-limited part settles over seconds;
     # the K-step headline region is < 1 s)
     sustained = None
-    if not a.no_secondary and world == 1:
+    if secondary and world == 1:
         use_graph["v"] = graph_was
         n_sus, t1 = 0, time.perf_counter()
         with PowerSampler(pci_bdf=_pci_bdf(dev)) as psamp:
@@ -748,7 +762,7 @@ def main():
         return time.perf_counter() - t1
 
     padded_info = None
-    if not vision and not id_tower and not a.padded and not a.no_secondary and _engine.UNPAD_DEFAULT:
+    if not vision and not id_tower and not a.padded and secondary and _engine.UNPAD_DEFAULT:
         _engine.UNPAD_DEFAULT = False
         dt3 = timed_again()
         _engine.UNPAD_DEFAULT = True
@@ -761,7 +775,7 @@ def main():
                                "real_token_fraction = real tokens / (Nc T) over the timed BATCHES (Zipf sampling favours some titles); "
                                "..._catalog_mean = the same over the catalog"}
     dedup_info = None
-    if not a.dedup and not a.no_secondary and not id_tower:
+    if not a.dedup and secondary and not id_tower:
         ts.dedup_items = True
         for i in range(min(2, a.warmup)):
             run_step(i)
@@ -786,7 +800,7 @@ def main():
     fp32_info = fp32x3_info = None
     main_gemm_log = list(gemm_log)
     main_ce_log, main_ce_shapes = list(ce_log), list(ce_shapes)
-    if not vision and not id_tower and a.dtype16 in ("bf16", "fp16") and not a.no_secondary and world == 1:
+    if not vision and not id_tower and a.dtype16 in ("bf16", "fp16") and secondary and world == 1:
         def fp32_mode_line(mode):
             nonlocal ts
             info = None
@@ -838,84 +852,86 @@ def main():
         ce_log[:] = main_ce_log
         ce_shapes[:] = main_ce_shapes
 
-    # roofline of the dominant kernel: algorithmic FLOPs of every GEMM launch / its measured duration
-    fl = sum(g_[0] for g_ in gemm_log)
-    ms = sum(g_[1].elapsed_time(g_[2]) for g_ in gemm_log)
-    tf = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-    # fp32x3: three bf16 MFMA passes per fp32 product -> a third of the bf16 peak in fp32-equivalent FLOPs
-    peak = {"bf16": MFMA_PEAK_TFLOPS["bf16"], "fp16": MFMA_PEAK_TFLOPS["fp16"], "fp32": MFMA_PEAK_TFLOPS["f32"],
-            "fp32x3": round(MFMA_PEAK_TFLOPS["bf16"] / 3.0, 1)}[a.dtype16]
-    launches_per_step = len(gemm_log) / max(1, n_inst)
-    flops_per_step = fl / max(1, n_inst)
-    alg_bytes_per_launch = sum(g_[4] for g_ in gemm_log) / max(1, len(gemm_log))
-    # HBM bytes per launch from the rocprofv3 PMC passes (scripts/capture_profiles.sh -> profiles/<round>_gemm_pmc.json).  The file is
-    # used only when it describes THIS workload: same number of GEMM launches per step, same token layout, FLOPs per step within 3 %
-    # (the profiled run draws fewer batches of the same synthetic set)
-    traffic, traffic_note = None, "no PMC file under profiles/ matches this run"
-    pmc_files = sorted((f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_gemm_pmc.json")), reverse=True) \
-        if os.path.isdir(os.path.join(ROOT, "profiles")) else []
-    layout_now = None if (vision or id_tower) else ("padded (all T positions)" if (a.padded or not _engine.UNPAD_DEFAULT) else "unpadded (real tokens only; exact)")
-    for fn in pmc_files:
-        try:
-            with open(os.path.join(ROOT, "profiles", fn)) as fh:
-                pj = json.load(fh)
-            sig = pj.get("signature") or {}
-            # (the profile counts GEMM KERNELS, this file counts ops.gemm_* calls: the two GEMMs inside morec_inbatch_ce_bwd are the difference)
-            if (sig.get("gemm_launches_per_step") is not None and abs(sig["gemm_launches_per_step"] - launches_per_step) < 3
-                    and sig.get("token_layout") == layout_now and sig.get("gemm_flops_per_step")
-                    and abs(sig["gemm_flops_per_step"] / flops_per_step - 1.0) < 0.03):
-                traffic, traffic_note = pj.get("hbm_bytes_per_launch_avg"), f"profiles/{fn}: " + pj.get("correction", "")
-                break
-        except Exception:  # noqa: BLE001
-            continue
-    roof = {"bound": "mfma", "kernel": "gemm8p_kernel + gemm_tn8p_kernel (256 x 256 eight-phase MFMA 32x32x16 tiles) + the small-problem gemm_nt / gemm_tn "
-                                       "kernels: every GEMM launch of the step",
-            "achieved": round(tf, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(tf / peak, 4), "traffic": traffic, "traffic_source": traffic_note,
-            "algorithmic_bytes_per_launch": round(alg_bytes_per_launch),
-            "traffic_over_algorithmic": (round(traffic / alg_bytes_per_launch, 3) if traffic else None),
-            "launches_per_step": int(round(launches_per_step)), "gemm_ms_per_step": round(ms / max(1, n_inst), 3),
-            "gemm_flops_per_step": round(flops_per_step),
-            "measured": f"HIP events around every GEMM launch in an instrumented pass of {n_inst} steps AFTER the headline region (which carries no events); "
-                        "single stream in that pass (the headline region overlaps the weight-gradient GEMMs with the dX chain on a second stream: "
-                        + ("on" if wgrad_was else "off") + ")"}
-    if sustained is not None and sustained.get("power") and sustained["power"].get("sclk_mhz_avg") and sustained["power"].get("device_matched"):
-        ck = sustained["power"]["sclk_mhz_avg"]
-        roof["at_sustained_clock"] = {"sclk_mhz": ck, "peak": round(peak * ck / 2400.0, 1), "frac": round(tf / (peak * ck / 2400.0), 4),
-                                      "note": "the 2.5 PFLOP/s peak is 256 CUs x 4096 FLOP/clk at 2.4 GHz; under this step's load the part holds its power cap at the "
-                                              "shader clock sampled during `sustained` (hwmon freq1_input), which scales what the matrix cores can issue"}
-    ce_ms = sum(e0.elapsed_time(e1) for _, e0, e1 in ce_log)
-    ce_gbs = sum(b for b, _, _ in ce_log) / (ce_ms * 1e-3) / 1e9 if ce_ms > 0 else 0.0
-    # Scoring is MFMA-bound, not HBM-bound: 2 Nr Nc D FLOP per product (1 forward, 3 backward: recompute, dP, dE) over
-    # (Nr + Nc) D bytes of operands = 1300 FLOP/B at the one-GPU size, 2260 at the 8-rank pooled size, against a machine balance
-    # of 2.5e15 / 8e12 = 312 (profiles/r02_scoring_pooled.txt; the logits are never stored).  The algorithmic byte rate is kept for
-    # the record.
-    ce_fl = sum((2.0 if kind == "fwd" else 6.0) * nr * nc * dd for kind, nr, nc, dd in ce_shapes)
-    ce_tf = ce_fl / (ce_ms * 1e-3) / 1e12 if ce_ms > 0 else 0.0
-    roof["scoring"] = {"bound": "mfma", "kernel": "ce8p_kernel<fwd> + ce_combine / ce8p_kernel<bwd> + gemm8p (dE = dl^T P) + gemm_tn8p (dP = dl E) (fused in-batch debiased CE on 256 x 256 "
-                                                   "eight-phase tiles; logits never stored)",
-                       "achieved": round(ce_tf, 1), "peak": peak, "unit": "TFLOP/s", "frac": round(ce_tf / peak, 4),
-                       "algorithmic_GBps": round(ce_gbs, 1), "ms_per_step": round(ce_ms / max(1, n_inst), 4),
-                       "note": "launch-latency class at the one-GPU size (2560 x 2688 logits: 110 tiles for 256 CUs); the size the multi-GPU step runs is "
-                               "`pooled_8_ranks`"}
+    roof = None
+    if a.full:
+        # roofline of the dominant kernel: algorithmic FLOPs of every GEMM launch / its measured duration
+        fl = sum(g_[0] for g_ in gemm_log)
+        ms = sum(g_[1].elapsed_time(g_[2]) for g_ in gemm_log)
+        tf = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+        # fp32x3: three bf16 MFMA passes per fp32 product -> a third of the bf16 peak in fp32-equivalent FLOPs
+        peak = {"bf16": MFMA_PEAK_TFLOPS["bf16"], "fp16": MFMA_PEAK_TFLOPS["fp16"], "fp32": MFMA_PEAK_TFLOPS["f32"],
+                "fp32x3": round(MFMA_PEAK_TFLOPS["bf16"] / 3.0, 1)}[a.dtype16]
+        launches_per_step = len(gemm_log) / max(1, n_inst)
+        flops_per_step = fl / max(1, n_inst)
+        alg_bytes_per_launch = sum(g_[4] for g_ in gemm_log) / max(1, len(gemm_log))
+        # HBM bytes per launch from the rocprofv3 PMC passes (scripts/capture_profiles.sh -> profiles/<round>_gemm_pmc.json).  The file is
+        # used only when it describes THIS workload: same number of GEMM launches per step, same token layout, FLOPs per step within 3 %
+        # (the profiled run draws fewer batches of the same synthetic set)
+        traffic, traffic_note = None, "no PMC file under profiles/ matches this run"
+        pmc_files = sorted((f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_gemm_pmc.json")), reverse=True) \
+            if os.path.isdir(os.path.join(ROOT, "profiles")) else []
+        layout_now = None if (vision or id_tower) else ("padded (all T positions)" if (a.padded or not _engine.UNPAD_DEFAULT) else "unpadded (real tokens only; exact)")
+        for fn in pmc_files:
+            try:
+                with open(os.path.join(ROOT, "profiles", fn)) as fh:
+                    pj = json.load(fh)
+                sig = pj.get("signature") or {}
+                # (the profile counts GEMM KERNELS, this file counts ops.gemm_* calls: the two GEMMs inside morec_inbatch_ce_bwd are the difference)
+                if (sig.get("gemm_launches_per_step") is not None and abs(sig["gemm_launches_per_step"] - launches_per_step) < 3
+                        and sig.get("token_layout") == layout_now and sig.get("gemm_flops_per_step")
+                        and abs(sig["gemm_flops_per_step"] / flops_per_step - 1.0) < 0.03):
+                    traffic, traffic_note = pj.get("hbm_bytes_per_launch_avg"), f"profiles/{fn}: " + pj.get("correction", "")
+                    break
+            except Exception:  # noqa: BLE001
+                continue
+        roof = {"bound": "mfma", "kernel": "gemm8p_kernel + gemm_tn8p_kernel (256 x 256 eight-phase MFMA 32x32x16 tiles) + the small-problem gemm_nt / gemm_tn "
+                                           "kernels: every GEMM launch of the step",
+                "achieved": round(tf, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(tf / peak, 4), "traffic": traffic, "traffic_source": traffic_note,
+                "algorithmic_bytes_per_launch": round(alg_bytes_per_launch),
+                "traffic_over_algorithmic": (round(traffic / alg_bytes_per_launch, 3) if traffic else None),
+                "launches_per_step": int(round(launches_per_step)), "gemm_ms_per_step": round(ms / max(1, n_inst), 3),
+                "gemm_flops_per_step": round(flops_per_step),
+                "measured": f"HIP events around every GEMM launch in an instrumented pass of {n_inst} steps AFTER the headline region (which carries no events); "
+                            "single stream in that pass (the headline region overlaps the weight-gradient GEMMs with the dX chain on a second stream: "
+                            + ("on" if wgrad_was else "off") + ")"}
+        if sustained is not None and sustained.get("power") and sustained["power"].get("sclk_mhz_avg") and sustained["power"].get("device_matched"):
+            ck = sustained["power"]["sclk_mhz_avg"]
+            roof["at_sustained_clock"] = {"sclk_mhz": ck, "peak": round(peak * ck / 2400.0, 1), "frac": round(tf / (peak * ck / 2400.0), 4),
+                                          "note": "the 2.5 PFLOP/s peak is 256 CUs x 4096 FLOP/clk at 2.4 GHz; under this step's load the part holds its power cap at the "
+                                                  "shader clock sampled during `sustained` (hwmon freq1_input), which scales what the matrix cores can issue"}
+        ce_ms = sum(e0.elapsed_time(e1) for _, e0, e1 in ce_log)
+        ce_gbs = sum(b for b, _, _ in ce_log) / (ce_ms * 1e-3) / 1e9 if ce_ms > 0 else 0.0
+        # Scoring is MFMA-bound, not HBM-bound: 2 Nr Nc D FLOP per product (1 forward, 3 backward: recompute, dP, dE) over
+        # (Nr + Nc) D bytes of operands = 1300 FLOP/B at the one-GPU size, 2260 at the 8-rank pooled size, against a machine balance
+        # of 2.5e15 / 8e12 = 312 (profiles/r02_scoring_pooled.txt; the logits are never stored).  The algorithmic byte rate is kept for
+        # the record.
+        ce_fl = sum((2.0 if kind == "fwd" else 6.0) * nr * nc * dd for kind, nr, nc, dd in ce_shapes)
+        ce_tf = ce_fl / (ce_ms * 1e-3) / 1e12 if ce_ms > 0 else 0.0
+        roof["scoring"] = {"bound": "mfma", "kernel": "ce8p_kernel<fwd> + ce_combine / ce8p_kernel<bwd> + gemm8p (dE = dl^T P) + gemm_tn8p (dP = dl E) (fused in-batch debiased CE on 256 x 256 "
+                                                       "eight-phase tiles; logits never stored)",
+                           "achieved": round(ce_tf, 1), "peak": peak, "unit": "TFLOP/s", "frac": round(ce_tf / peak, 4),
+                           "algorithmic_GBps": round(ce_gbs, 1), "ms_per_step": round(ce_ms / max(1, n_inst), 4),
+                           "note": "launch-latency class at the one-GPU size (2560 x 2688 logits: 110 tiles for 256 CUs); the size the multi-GPU step runs is "
+                                   "`pooled_8_ranks`"}
 
-    # the scoring kernels at the 8-rank POOLED size (this rank's B S rows against eight ranks' worth of item vectors, emulated on one
-    # GPU): the size north_star's multi-GPU step runs them at; never part of `value`
-    if not a.no_secondary and not vision and world == 1 and a.dtype16 in ("bf16", "fp16"):
-        try:
-            roof["scoring"]["pooled_8_ranks"] = scoring_pooled(ops, a.batch, S, D, dev, peak, dt=torch.float16 if a.dtype16 == "fp16" else torch.bfloat16)
-        except Exception as e:  # noqa: BLE001
-            roof["scoring"]["pooled_8_ranks"] = {"error": f"{type(e).__name__}: {e}"}
+        # the scoring kernels at the 8-rank POOLED size (this rank's B S rows against eight ranks' worth of item vectors, emulated on one
+        # GPU): the size north_star's multi-GPU step runs them at; never part of `value`
+        if secondary and not vision and world == 1 and a.dtype16 in ("bf16", "fp16"):
+            try:
+                roof["scoring"]["pooled_8_ranks"] = scoring_pooled(ops, a.batch, S, D, dev, peak, dt=torch.float16 if a.dtype16 == "fp16" else torch.bfloat16)
+            except Exception as e:  # noqa: BLE001
+                roof["scoring"]["pooled_8_ranks"] = {"error": f"{type(e).__name__}: {e}"}
 
-    # Is the GEMM rate set by the schedule or by the part's power limit?  The same launch (FFN-up shape of the step, plain epilogue) on N(0, 0.5)
-    # operands and on zeros: identical instruction stream and cycle count, different switching activity (never part of `value`)
-    if not a.no_secondary and not vision and not id_tower and world == 1 and a.dtype16 in ("bf16", "fp16"):
-        try:
-            roof["operand_activity_probe"] = operand_activity_probe(ops, dev, torch.float16 if a.dtype16 == "fp16" else torch.bfloat16)
-        except Exception as e:  # noqa: BLE001
-            roof["operand_activity_probe"] = {"error": f"{type(e).__name__}: {e}"}
+        # Is the GEMM rate set by the schedule or by the part's power limit?  The same launch (FFN-up shape of the step, plain epilogue) on N(0, 0.5)
+        # operands and on zeros: identical instruction stream and cycle count, different switching activity (never part of `value`)
+        if secondary and not vision and not id_tower and world == 1 and a.dtype16 in ("bf16", "fp16"):
+            try:
+                roof["operand_activity_probe"] = operand_activity_probe(ops, dev, torch.float16 if a.dtype16 == "fp16" else torch.bfloat16)
+            except Exception as e:  # noqa: BLE001
+                roof["operand_activity_probe"] = {"error": f"{type(e).__name__}: {e}"}
 
     eval_info = None
-    if not a.no_secondary and not vision and not id_tower and world == 1 and a.dtype16 in ("bf16", "fp16"):
+    if secondary and not vision and not id_tower and world == 1 and a.dtype16 in ("bf16", "fp16"):
         keep = (list(gemm_log), list(ce_log), list(ce_shapes))
         eval_info = eval_lines(model, ops, args, content, a.item_num, S, D, dev, gemm_log, timing_on, peak)
         gemm_log[:], ce_log[:], ce_shapes[:] = keep
@@ -933,7 +949,7 @@ def main():
                                   f"B={a.batch}/GPU, S=20, T=30", "global_batch": world * a.batch, "seq_len": S + 3,
                       "parallelism": f"dp{world}" + ("" if a.no_pool or world == 1 else "+pooled-negatives"),
                       "dropout": "on (p = 0.1 hidden + attention, SASRec and BERT; counter-based masks fused in the kernels)"},
-           "final_loss": round(loss_v, 4), "roofline": roof, "steps_executed": n_run["v"]}
+           "final_loss": round(loss_v, 4), "full": a.full, "roofline": roof, "steps_executed": n_run["v"]}
     if sustained is not None:
         out["sustained"] = sustained
     if eval_info is not None:
@@ -962,12 +978,12 @@ def main():
     # secondary lines (never `value`): the other BASELINE.json configurations, each measured by a child run of this file so that the
     # driver's record carries a time for every config: configs[3] Swin-T (V/train_swin_tiny.py:22-41: B = 64/GPU, 704 images per
     # step), configs[4] Swin-B (B = 32/GPU, 352 images per step), configs[0] IDRec (T/train_id.py:22-26), configs[1] BERT-tiny
-    if not vision and not id_tower and a.dtype16 in ("bf16", "fp16") and not a.no_secondary and world == 1 and a.bert == "base":
+    if not vision and not id_tower and a.dtype16 in ("bf16", "fp16") and secondary and world == 1 and a.bert == "base":
         import subprocess
 
         def child(extra, timeout=240):
             env = None if _DET_SET_BY_CALLER else dict(os.environ, MOREC_DETERMINISTIC="0")
-            r = subprocess.run([sys.executable, os.path.abspath(__file__)] + extra + ["--no-cpu-baseline", "--no-secondary"],
+            r = subprocess.run([sys.executable, os.path.abspath(__file__)] + extra + ["--full", "--no-cpu-baseline", "--no-secondary"],
                                capture_output=True, text=True, timeout=timeout, env=env)
             return json.loads(r.stdout.strip().splitlines()[-1])
 
@@ -1039,10 +1055,10 @@ def main():
                          "dropout": "on (SASRec p = 0.1; Swin DropPath 0 -> 0.1 linear, per-image scales from the counter-based RNG)"}
 
     out["config"]["deterministic"] = _lib_env_flag("MOREC_DETERMINISTIC")
-    if rank == 0 and not a.no_cpu_baseline and (vision or id_tower):
+    if rank == 0 and a.full and not a.no_cpu_baseline and (vision or id_tower):
         out["cpu_baseline"] = {"value": None, "unit": "user-seq/s", "cores": None, "kind": "port",
                                "sample": "not measured for the vision tower (the BASELINE.json metric is the text tower)"}
-    elif rank == 0 and not a.no_cpu_baseline:
+    elif rank == 0 and a.full and not a.no_cpu_baseline:
         # the CPU oracle runs in a child process under a wall-clock limit so it can never block the result line
         import subprocess
         try:

@@ -6,7 +6,7 @@ mkdir -p "$out"
 for rep in 1 2 3; do
   for spec in "$@"; do
     label=${spec%%=*}; envs=${spec#*=}
-    env $envs python bench.py --steps ${STEPS:-12} --warmup 4 --no-cpu-baseline --no-secondary ${BENCH_ARGS} > "$out/${label}_$rep.json" 2>> "$out/err.log"
+    env $envs python bench.py --steps ${STEPS:-12} --warmup 4 --full --no-cpu-baseline --no-secondary ${BENCH_ARGS} > "$out/${label}_$rep.json" 2>> "$out/err.log"
   done
 done
 python - "$out" <<'PY'

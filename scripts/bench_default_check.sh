@@ -1,11 +1,11 @@
 #!/bin/bash
-# the driver's bench command, end to end, with a wall clock and a digest of the line
+# the full bench run (--full: every pass behind the headline), end to end, with a wall clock and a digest of the line
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 O=gpurun_out/${1:-r5i}
 mkdir -p $O
 T0=$(date +%s)
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err
 echo "rc=$? wall=$(( $(date +%s) - T0 ))s"
 python - "$O/bench_default.json" <<'PY'
 import json, sys

@@ -7,18 +7,18 @@ cd /tmp; export TMPDIR=/tmp
 # Single-stream runs for the per-kernel numbers (with the weight-gradient stream on, dW launches overlap the dX chain and the traced
 # durations of both stretch over each other); the default (overlapped) step is traced separately below.
 export MOREC_WGRAD_STREAM=0
-BENCH="python $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-secondary"
+BENCH="python $R/bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-secondary"
 rm -rf /tmp/prof; mkdir -p /tmp/prof
 timeout 200 rocprofv3 --kernel-trace --stats -d /tmp/prof -o kt -- $BENCH > $O/${TAG}_prof_bench_line.json 2> /dev/null
 NS=$(python -c "import json,sys; print(json.loads([l for l in open('$O/${TAG}_prof_bench_line.json') if l.startswith('{')][-1])['steps_executed'])")
-python $R/scripts/prof_summary.py /tmp/prof/kt_results.db $NS "$TAG: MOREC_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats -- bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-secondary ($NS steps traced: 2 warm-up + 4 timed + 5 of the instrumented pass; single stream)" > $O/${TAG}_bench_kernel_stats.csv
+python $R/scripts/prof_summary.py /tmp/prof/kt_results.db $NS "$TAG: MOREC_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats -- bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-secondary ($NS steps traced: 2 warm-up + 4 timed + 5 of the instrumented pass; single stream)" > $O/${TAG}_bench_kernel_stats.csv
 rm -f /tmp/prof/ko_results.db
 MOREC_WGRAD_STREAM=1 timeout 200 rocprofv3 --kernel-trace --stats -d /tmp/prof -o ko -- $BENCH > /dev/null 2>&1
 python $R/scripts/prof_summary.py /tmp/prof/ko_results.db $NS "$TAG: default step (weight-gradient stream ON: kernels of the two streams overlap, their durations add up to more than the step)" > $O/${TAG}_bench_kernel_stats_overlap.csv
 # the fp16_res32 mode (fp32 residual stream): single-stream kernel trace
 rm -f /tmp/prof/kr_results.db
 timeout 200 rocprofv3 --kernel-trace --stats -d /tmp/prof -o kr -- $BENCH --dtype fp16_res32 > /dev/null 2>&1
-python $R/scripts/prof_summary.py /tmp/prof/kr_results.db $NS "$TAG fp16_res32: MOREC_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats -- bench.py --dtype fp16_res32 --steps 4 --warmup 2 --no-cpu-baseline --no-secondary ($NS steps traced; single stream)" > $O/${TAG}_res32_kernel_stats.csv
+python $R/scripts/prof_summary.py /tmp/prof/kr_results.db $NS "$TAG fp16_res32: MOREC_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats -- bench.py --dtype fp16_res32 --steps 4 --warmup 2 --full --no-cpu-baseline --no-secondary ($NS steps traced; single stream)" > $O/${TAG}_res32_kernel_stats.csv
 timeout 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/prof -o pf -- $BENCH > /dev/null 2>&1
 timeout 200 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d /tmp/prof -o pw -- $BENCH > /dev/null 2>&1
 python $R/scripts/pmc_traffic.py /tmp/prof/pf_results.db /tmp/prof/pw_results.db $O/${TAG}_prof_bench_line.json $O/${TAG}_gemm_pmc.json
@@ -39,7 +39,7 @@ python $R/scripts/prof_summary.py /tmp/prof/ks_results.db $NS2 "$TAG swin_tiny B
 # which bench.py matches by signature for the vision lines' roofline.traffic
 for spec in "swin_tiny 64" "swin_base 32"; do
   set -- $spec
-  SB="python $R/bench.py --tower $1 --batch $2 --steps 4 --warmup 2 --no-cpu-baseline --no-secondary"
+  SB="python $R/bench.py --tower $1 --batch $2 --steps 4 --warmup 2 --full --no-cpu-baseline --no-secondary"
   MOREC_WGRAD_STREAM=0 timeout 200 $SB > $O/${TAG}_prof_$1_line.json 2> /dev/null
   rm -f /tmp/prof/sf_results.db /tmp/prof/swr_results.db
   timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/prof -o sf -- $SB > /dev/null 2>&1
@@ -75,5 +75,5 @@ MOREC_ATTN_MFMA64=0 python $R/scripts/attn64_bench.py
 } > $O/${TAG}_attn64.txt 2>&1
 # ID tower kernel trace (two streams, as it runs)
 rm -f /tmp/prof/ki_results.db
-MOREC_WGRAD_STREAM=1 timeout 200 rocprofv3 --kernel-trace --stats -d /tmp/prof -o ki -- python $R/bench.py --tower id --batch 128 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > /dev/null 2>&1
-python $R/scripts/prof_summary.py /tmp/prof/ki_results.db 34 "$TAG id tower: rocprofv3 --kernel-trace --stats -- bench.py --tower id --batch 128 --steps 20 --warmup 5 (34 steps traced, two streams)" > $O/${TAG}_id_tower_kernel_stats.csv
+MOREC_WGRAD_STREAM=1 timeout 200 rocprofv3 --kernel-trace --stats -d /tmp/prof -o ki -- python $R/bench.py --tower id --batch 128 --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary > /dev/null 2>&1
+python $R/scripts/prof_summary.py /tmp/prof/ki_results.db 34 "$TAG id tower: rocprofv3 --kernel-trace --stats -- bench.py --tower id --batch 128 --steps 20 --warmup 5 --full (34 steps traced: 5 warm-up + 20 timed on two streams + 9 of the single-stream instrumented pass)" > $O/${TAG}_id_tower_kernel_stats.csv

@@ -31,6 +31,12 @@ def test_world_size_mismatch_fails_loudly():
     assert "WORLD_SIZE=1" in (r.stderr + r.stdout)
 
 
+def test_sweep_needs_full():
+    """--sweep widens the data-parallel sweep of a --full run; without --full it is refused, not silently dropped."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--sweep", "--launch-check"], capture_output=True, text=True, timeout=300, env=_clean_env())
+    assert r.returncode != 0 and "--full" in r.stderr
+
+
 import pytest  # noqa: E402
 
 
@@ -41,7 +47,8 @@ def test_two_rank_line_on_one_gpu_carries_the_reduce_trace():
     pooled negatives, bucketed gradient reduction from the backward callbacks.  The line must say what ran (2 ranks, weak scaling,
     whole-job throughput) and carry the per-bucket issue / join trace a scaling run is read with."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--share-device", "--backend", "gloo", "--bert", "tiny", "--batch", "16", "--steps", "3",
-                        "--warmup", "2", "--no-secondary", "--no-cpu-baseline", "--sweep"], capture_output=True, text=True, timeout=500, env=_clean_env())
+                        "--warmup", "2", "--full", "--no-secondary", "--no-cpu-baseline", "--sweep"], capture_output=True, text=True, timeout=500,
+                       env=_clean_env())
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["world_size_observed"] == 2 and out["scaling"] == "weak"
@@ -70,12 +77,12 @@ def test_two_rank_line_on_one_gpu_carries_the_reduce_trace():
 @pytest.mark.gpu
 @pytest.mark.timeout(600)
 def test_watchdog_prints_the_headline_alone():
-    """N > 1: when the explanatory passes behind the timed region do not finish in MOREC_BENCH_WATCHDOG_S (here: a limit they cannot meet), rank 0
+    """N > 1, --full: when the explanatory passes behind the timed region do not finish in MOREC_BENCH_WATCHDOG_S (here: a limit they cannot meet), rank 0
     prints the measured headline with `post_headline` saying so and every rank exits 0 -- a hang in a first real multi-GPU run must not take
     the measured number with it."""
     env = dict(_clean_env(), MOREC_BENCH_WATCHDOG_S="0.001")
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--share-device", "--backend", "gloo", "--bert", "tiny", "--batch", "16", "--steps", "3",
-                        "--warmup", "2", "--no-secondary", "--no-cpu-baseline"], capture_output=True, text=True, timeout=500, env=env)
+                        "--warmup", "2", "--full", "--no-secondary", "--no-cpu-baseline"], capture_output=True, text=True, timeout=500, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -89,14 +96,15 @@ def test_watchdog_prints_the_headline_alone():
 def test_dump_outputs_writes_the_last_timed_step(tmp_path):
     """--dump-outputs DIR: after exactly --steps timed steps, the last step's loss and every trained parameter's updated value and gradient
     land in DIR as float .npy files (large tensors as their fixed sample), within the size limit -- and, the headline step running in the
-    deterministic mode, a second run with the same arguments writes the same bits."""
+    deterministic mode, a second run with the same arguments writes the same bits.  A plain run stops after the timed steps; a --full run
+    steps the model again after the dump and writes the same bits too."""
     import zlib
 
     import numpy as np
 
-    def run(d):
+    def run(d, *extra):
         r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--bert", "tiny", "--batch", "16", "--steps", "3", "--warmup", "2", "--no-secondary",
-                            "--no-cpu-baseline", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=250,
+                            "--no-cpu-baseline", "--dump-outputs", str(d), *extra], capture_output=True, text=True, timeout=250,
                            env={k: v for k, v in _clean_env().items() if k != "MOREC_DETERMINISTIC"})
         assert r.returncode == 0, r.stderr[-3000:]
         return json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
@@ -104,8 +112,9 @@ def test_dump_outputs_writes_the_last_timed_step(tmp_path):
     d = tmp_path / "out"
     out = run(d)
     assert out["config"]["deterministic"] is True
-    # 2 warm-up + 3 timed + the instrumented pass after the headline (1 untimed + min(steps, 8) event-timed): the timed region ran 3 steps
-    assert out["steps"] == 3 and out["steps_executed"] == 2 + 3 + 1 + 3 and out["ms_per_step"] > 0
+    # a plain run: 2 warm-up + 3 timed steps and nothing after them
+    assert out["steps"] == 3 and out["steps_executed"] == 2 + 3 and out["ms_per_step"] > 0
+    assert out["full"] is False and out["roofline"] is None
     files = {f.name: np.load(f) for f in d.iterdir()}
     assert sum(f.stat().st_size for f in d.iterdir()) <= 64 * 10 ** 6
     assert all(v.dtype in (np.float32, np.float64) for v in files.values())
@@ -132,4 +141,12 @@ def test_dump_outputs_writes_the_last_timed_step(tmp_path):
     run(d2)
     assert sorted(f.name for f in d2.iterdir()) == sorted(files)
     differ = [k for k, v in files.items() if not np.array_equal(np.load(d2 / k), v)]
+    assert not differ, differ[:5]
+    # --full: 2 warm-up + 3 timed + the instrumented pass after the headline (1 untimed + min(steps, 8) event-timed); the dump is written
+    # before that pass and holds the same bits
+    d3 = tmp_path / "full"
+    out3 = run(d3, "--full")
+    assert out3["steps"] == 3 and out3["steps_executed"] == 2 + 3 + 1 + 3 and out3["full"] is True and out3["roofline"]["launches_per_step"] > 0
+    assert out3["final_loss"] == out["final_loss"] and sorted(f.name for f in d3.iterdir()) == sorted(files)
+    differ = [k for k, v in files.items() if not np.array_equal(np.load(d3 / k), v)]
     assert not differ, differ[:5]
