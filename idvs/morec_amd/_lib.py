@@ -116,6 +116,7 @@ _SIGS = {
     "morec_step_decide": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, _P]),
     "morec_adamw_sp": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P]),
     "morec_eval_rank": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "morec_eval_rank_cand": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "morec_dropout_keep_mask": (C.c_int, [_P, C.c_size_t, C.c_float, C.c_uint64, _P]),
     "morec_probe": (C.c_int, [_P, _P]),
     "morec_swin_attn_fwd": (C.c_int, [C.POINTER(SwinAttnDesc), _P, _P, _P, _P]),

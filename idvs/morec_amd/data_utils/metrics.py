@@ -114,20 +114,23 @@ class PackedEvalUsers:
 
     def slice(self, a, b):
         hist = self.hist[a:b]
-        used = max(1, int((hist >= 0).sum(1).max()) if b > a else 1)     # the chunk's own widest history: what the kernel's LDS table holds
+        used = max(1, int((hist >= 0).sum(1).max()) if b > a else 1)     # the chunk's own widest history: what the kernel walks per tile
         return self.idx[a:b], self.lm[a:b], np.ascontiguousarray(hist[:, :used]), self.target[a:b]
 
 
-def eval_ranks_packed(model, packed: PackedEvalUsers, a, b, item_embeddings, local_rank):
-    """1-based target ranks of users [a, b) of a ``PackedEvalUsers``: user states from the SASRec encoder, ranks by the HIP kernel."""
+def eval_ranks_packed(model, packed: PackedEvalUsers, a, b, item_embeddings, local_rank, cand_emb=None):
+    """1-based target ranks of users [a, b) of a ``PackedEvalUsers``: user states from the SASRec encoder, ranks by the HIP kernel.
+    ``cand_emb`` (new-item evaluation, ``special.py``): the targets are rows of this table, not catalogue items (``eval_rank_cand``)."""
     m = _module(model)
     idx, lm, hist, target = packed.slice(a, b)
     dev = item_embeddings.device
     with torch.no_grad(), ops.fp32_gemm_mode(getattr(m, "fp32_gemm", ops.FP32_GEMM)):
         embs = item_embeddings[torch.from_numpy(idx).to(dev)]                      # [U, S, D] gather (plumbing)
         prec = m.user_encoder(embs, torch.from_numpy(lm).to(dev), local_rank)[:, -1].float().contiguous()
-        return ops.eval_rank(prec, item_embeddings.contiguous(), torch.from_numpy(hist).to(dev),
-                             torch.from_numpy(target).to(dev)).long()
+        hist, target = torch.from_numpy(hist).to(dev), torch.from_numpy(target).to(dev)
+        if cand_emb is not None:
+            return ops.eval_rank_cand(prec, item_embeddings.contiguous(), hist, cand_emb.contiguous(), target).long()
+        return ops.eval_rank(prec, item_embeddings.contiguous(), hist, target).long()
 
 
 def eval_ranks(model, user_history, eval_seq, item_embeddings, users, args, local_rank):
@@ -136,10 +139,9 @@ def eval_ranks(model, user_history, eval_seq, item_embeddings, users, args, loca
     return eval_ranks_packed(model, packed, 0, packed.U, item_embeddings, local_rank)
 
 
-def eval_model(model, user_history, eval_seq, item_embeddings, test_batch_size, args, item_num, Log_file, v_or_t, local_rank):
-    """``metrics.py:77-107``: mean Hit@10 / nDCG@10 over all users (sharded over ranks like the reference's
-    SequentialDistributedSampler, gathered with all_gather).  Returns Hit@10."""
-    model.eval()
+def eval_users(model, user_history, eval_seq, item_embeddings, test_batch_size, args, local_rank, cand_emb=None):
+    """Per-user Hit@10 / nDCG@10 of every user of ``eval_seq`` (sharded over ranks like the reference's SequentialDistributedSampler,
+    gathered with all_gather, the sampler's padding dropped).  ``cand_emb``: see ``eval_ranks_packed``."""
     world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
     rank = dist.get_rank() if world > 1 else 0
     n_users = len(eval_seq)
@@ -150,7 +152,7 @@ def eval_model(model, user_history, eval_seq, item_embeddings, test_batch_size, 
     hits, ndcgs = [], []
     packed = PackedEvalUsers(user_history, eval_seq, mine, args.max_seq_len)      # one vectorised pass over this rank's users
     for s in range(0, len(mine), test_batch_size):
-        ranks = eval_ranks_packed(model, packed, s, min(len(mine), s + test_batch_size), item_embeddings, local_rank)
+        ranks = eval_ranks_packed(model, packed, s, min(len(mine), s + test_batch_size), item_embeddings, local_rank, cand_emb)
         h, n = metrics_from_ranks(ranks)
         hits.append(h)
         ndcgs.append(n)
@@ -161,7 +163,13 @@ def eval_model(model, user_history, eval_seq, item_embeddings, test_batch_size, 
         dist.all_gather(parts_h, hit)
         dist.all_gather(parts_n, ndcg)
         hit, ndcg = torch.cat(parts_h), torch.cat(parts_n)
-    hit, ndcg = hit[:n_users], ndcg[:n_users]       # drop the sampler's padding (metrics.py:33-37 ``[:num_total_examples]``)
+    return hit[:n_users], ndcg[:n_users]       # drop the sampler's padding (metrics.py:33-37 ``[:num_total_examples]``)
+
+
+def eval_model(model, user_history, eval_seq, item_embeddings, test_batch_size, args, item_num, Log_file, v_or_t, local_rank):
+    """``metrics.py:77-107``: mean Hit@10 / nDCG@10 over all users (``eval_users``).  Returns Hit@10."""
+    model.eval()
+    hit, ndcg = eval_users(model, user_history, eval_seq, item_embeddings, test_batch_size, args, local_rank)
     mean_eval = [hit.mean().item(), ndcg.mean().item()]
     if Log_file is not None:
         Log_file.info(v_or_t + "_methods   {}".format("\t".join(["Hit10", "nDCG10"])))

@@ -648,6 +648,18 @@ def eval_rank(prec, item_emb, hist32, target32):
     return rank
 
 
+def eval_rank_cand(prec, item_emb, hist32, cand_emb, cand_idx32):
+    """``morec_eval_rank_cand``: 1-based rank of each user's candidate ``cand_emb[cand_idx32[u]]`` (a vector outside the catalogue)
+    among the catalogue items 1 .. item_num outside the user's history (``special.py``'s new-item evaluation)."""
+    U, D = prec.shape
+    rank = torch.empty(U, device=prec.device, dtype=torch.int32)
+    ts = torch.empty(U, device=prec.device, dtype=torch.float32)
+    check(_lib.lib().morec_eval_rank_cand(_p(_dev(prec)), _p(_dev(item_emb)), _p(_dev(hist32)), hist32.shape[1], _p(_dev(cand_emb)),
+                                          cand_emb.shape[0], _p(_dev(cand_idx32)), _p(rank), _p(ts), U, item_emb.shape[0], D,
+                                          _stream()), "morec_eval_rank_cand")
+    return rank
+
+
 # ---------------------------------------------------------------------------------------------------------
 # Swin vision tower
 # ---------------------------------------------------------------------------------------------------------

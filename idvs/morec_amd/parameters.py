@@ -51,6 +51,15 @@ def build_parser():
     p.add_argument("--images_npy", type=str, default="None",
                    help="uint8 array [item_num + 1, R, R, 3] of decoded, resized item images (row 0 = padding item); stands in for the "
                         "LMDB reader of V/data_utils/dataset.py, whose lmdb / torchvision dependencies are not part of this package")
+    # ============== cold-start / new-item evaluation (V/parameters.py:16-19; data_utils/special.py) ==============
+    p.add_argument("--cold_seqs", type=str, default="None", help="--mode test: user lines whose target is a cold item (evaluated after "
+                   "the test split); with --synthetic N, a path that does not exist yet is written with synthetic lines")
+    p.add_argument("--new_seqs", type=str, default="None", help="--mode test, modal towers: user lines whose last item is a NEW item")
+    p.add_argument("--new_items", type=str, default="None", help="vision: the new items' names (v<int>), one per line; their order = ids")
+    p.add_argument("--new_lmdb_data", type=str, default="None", help="vision: LMDB of the new items' images (needs the optional `lmdb` module)")
+    p.add_argument("--new_images_npy", type=str, default="None",
+                   help="vision: uint8 [n_new + 1, R, R, 3] images of the new items (row 0 unused); stands in for --new_lmdb_data as "
+                        "--images_npy does for the catalogue")
     # ============== MI355X path ==============
     p.add_argument("--compute_dtype", type=str, default="fp16", choices=["bf16", "fp16", "fp32", "fp32x3", "fp16_res32", "bf16_res32"],
                    help="fp16 (default) = IEEE half operands on the MFMA, fp32 accumulate, with the reference's GradScaler loss scaling -- the arithmetic of "

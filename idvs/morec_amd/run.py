@@ -247,6 +247,101 @@ def run_eval(model, item_content, user_history, users_eval, batch_size, item_num
     return hit10
 
 
+def synthetic_item_name(i, vision):
+    """Item names of a ``--synthetic`` catalogue (id i): ``v<i>`` for the vision tower (the form its LMDB keys are derived from),
+    ``N<i>`` otherwise."""
+    return ("v%d" if vision else "N%d") % i
+
+
+def write_synthetic_special(args, item_num, vision, n_users=48, n_new=12, seed=2468):
+    """``--synthetic`` with ``--cold_seqs``: the reference's line formats (``<user>\\t<item names>``) for the cold-start and new-item
+    files, written where a path does not exist yet.  Line lengths 1 .. max_seq_len + 3 (an empty history included); new items are
+    named after ids item_num + 1 .., one new-items line each (vision)."""
+    rng = np.random.default_rng(seed)
+    S = args.max_seq_len
+    lens = rng.integers(1, S + 4, n_users)
+    lens[0] = 1
+    name = lambda i: synthetic_item_name(int(i), vision)
+
+    def write(path, lines):
+        if path != "None" and not os.path.exists(path):
+            with open(path, "w") as f:
+                f.write("".join(lines))
+
+    write(args.cold_seqs, ["u%d\t%s\n" % (u, " ".join(name(i) for i in rng.integers(1, item_num + 1, lens[u]))) for u in range(n_users)])
+    new_lines = []
+    for u in range(n_users):
+        inputs = [name(i) for i in rng.integers(1, item_num + 1, lens[u] - 1)]
+        new_lines.append("u%d\t%s\n" % (u, " ".join(inputs + [name(item_num + 1 + u % n_new)])))
+    write(args.new_seqs, new_lines)
+    write(getattr(args, "new_items", "None"), ["%s\n" % name(item_num + 1 + k) for k in range(n_new)])
+
+
+def synthetic_new_item_docs(args, item_num, n_new=12, seed=1357):
+    """Text content of the synthetic new items (ids item_num + 1 ..) in ``read_news_bert``'s form: per item, one tokenizer output
+    (``input_ids`` / ``attention_mask`` lists) per attribute, ``[]`` for an attribute not in ``--news_attributes``."""
+    rng = np.random.default_rng(seed)
+    docs = {}
+    for k in range(n_new):
+        enc = []
+        for attr, T in (("title", args.num_words_title), ("abstract", args.num_words_abstract), ("body", args.num_words_body)):
+            if attr not in args.news_attributes:
+                enc.append([])
+                continue
+            L = int(rng.integers(3, T + 1))
+            ids = [101] + [int(v) for v in rng.integers(1000, 30522, L - 2)] + [102] + [0] * (T - L)
+            enc.append({"input_ids": ids, "attention_mask": [1] * L + [0] * (T - L)})
+        docs[item_num + 1 + k] = enc
+    return docs
+
+
+def run_eval_special(model, item_content, catalogue, batch_size, item_num, use_modal, vision, args, local_rank):
+    """``--mode test --cold_seqs ...``: the cold-start / new-item protocol of ``data_utils/special.py`` on the loaded checkpoint.  The
+    new items' vectors come from the item tower over their content (text: ``get_doc_input_bert`` tables, vision: ``--new_lmdb_data``
+    or ``--new_images_npy``); the ID tower has no vector for an unseen item and is evaluated on the cold users only (as the reference)."""
+    from .data_utils import eval_model_special, get_doc_input_bert, read_behaviors_special
+    t0 = time.time()
+    new_seqs = args.new_seqs if use_modal else "None"
+    if args.synthetic > 0:
+        write_synthetic_special(args, item_num, vision)
+        if use_modal and not vision:
+            docs = synthetic_new_item_docs(args, item_num)
+            catalogue = dict(catalogue, before_item_id_to_dic=docs,
+                             before_item_name_to_id={synthetic_item_name(i, False): i for i in docs} | catalogue["item_name_to_id"])
+    if use_modal and new_seqs == "None":
+        raise SystemExit("--cold_seqs with a modal tower: --new_seqs is needed too (special.py evaluates both protocols)")
+    if vision:
+        if getattr(args, "new_items", "None") == "None":
+            raise SystemExit("vision --cold_seqs: --new_items <the new items' names> is needed")
+        out = read_behaviors_special(args.cold_seqs, new_seqs, args.new_items, catalogue["item_name_to_id"], Log, use_modal)
+    else:
+        out = read_behaviors_special(args.cold_seqs, new_seqs, catalogue["item_name_to_id"], catalogue.get("before_item_id_to_dic"),
+                                     catalogue.get("before_item_name_to_id"), Log, use_modal)
+    seqs_cold, hist_cold, seqs_new, hist_new, new_content = out
+    item_embeddings = get_item_embeddings(model, item_content, batch_size, args, use_modal, local_rank)
+    new_embeddings = None
+    if use_modal:
+        n_new = len(new_content)
+        if not vision:
+            tables = get_doc_input_bert(new_content, args)                # row 0 = padding item, as for the catalogue
+            new_cont = np.concatenate([x for x in tables if x is not None], axis=1)
+        elif args.new_lmdb_data != "None":
+            from .data_utils import LmdbImageStore, LmdbItemImages
+            new_cont = LmdbItemImages(LmdbImageStore(args.new_lmdb_data), new_content, args.CV_resize)
+        else:
+            R = args.CV_resize
+            new_cont = (np.load(args.new_images_npy, mmap_mode="r") if args.new_images_npy != "None" else
+                        np.random.default_rng(8642).integers(0, 256, (n_new + 1, R, R, 3), dtype=np.uint8) if args.synthetic > 0 else None)
+            if new_cont is None:
+                raise SystemExit("vision --cold_seqs: --new_lmdb_data or --new_images_npy holds the new items' images")
+            assert new_cont.shape == (n_new + 1, R, R, 3) and new_cont.dtype == np.uint8, "--new_images_npy: uint8 [n_new + 1, R, R, 3]"
+        new_embeddings = get_item_embeddings(model, new_cont, batch_size, args, use_modal, local_rank)
+    res = eval_model_special(model, item_embeddings, new_embeddings, batch_size, args, item_num, Log, seqs_cold, hist_cold, seqs_new,
+                             hist_new, local_rank, use_modal)
+    Log.info("cold-start / new-item eval %.1f s" % (time.time() - t0))
+    return res
+
+
 def model_dir_candidates(args, world: int = 1):
     """The reference's checkpoint directory, label for label, first; then the other spellings a checkpoint may sit under.
     TEXT (``T/run.py:326-337``): ``checkpoint_<dir_label>/cpt_<model>_ed_<D>_bs_<batch_size * gpus>_lr_<lr>_Flr_<Flr>_L2_<l2>_FL2_<Fl2>`` with
@@ -340,6 +435,7 @@ def train(args, use_modal, local_rank):
             item_content = (np.load(args.images_npy, mmap_mode="r") if args.images_npy != "None" else
                             np.random.default_rng(4321).integers(0, 256, (item_num + 1, R, R, 3), dtype=np.uint8))
             assert item_content.shape == (item_num + 1, R, R, 3) and item_content.dtype == np.uint8
+        catalogue = dict(item_name_to_id={synthetic_item_name(i, vision): i for i in range(1, item_num + 1)})
     elif use_modal and not vision:                                       # T/run.py:28-98: tokenizer -> fixed-length id / mask tables
         from transformers import BertTokenizer
         from .data_utils import get_doc_input_bert, read_news_bert
@@ -348,23 +444,26 @@ def train(args, use_modal, local_rank):
             raise SystemExit(f"modal run on real data: no tokenizer vocabulary under {tok_dir} (--pretrained_dir / --bert_model_load)")
         tokenizer = BertTokenizer.from_pretrained(tok_dir)
         a, b, c = read_news_bert(os.path.join(args.root_data_dir, args.dataset, args.news), args, tokenizer)
-        item_num, item_id_to_dic, users_train, users_valid, users_test, hist_valid, hist_test, _, pop = read_behaviors(
+        item_num, item_id_to_dic, users_train, users_valid, users_test, hist_valid, hist_test, name_to_id, pop = read_behaviors(
             os.path.join(args.root_data_dir, args.dataset, args.behaviors), a, b, c, S, args.min_seq_len, Log)
         tables = get_doc_input_bert(item_id_to_dic, args)
         item_content = np.concatenate([x for x in tables if x is not None], axis=1)
+        catalogue = dict(item_name_to_id=name_to_id, before_item_id_to_dic=a, before_item_name_to_id=b)
     elif vision:                                                         # V/run.py:62-80: item list -> LMDB keys, images from the LMDB
         from .data_utils import LmdbImageStore, LmdbItemImages, read_images
         if args.image_lmdb == "None":
             raise SystemExit("vision run on real data: --image_lmdb <the LMDB of dataset/HM/build_lmdb_hm.py> (or --synthetic N --images_npy ...)")
         a, b, c = read_images(os.path.join(args.root_data_dir, args.dataset, args.news))
-        item_num, id2key, users_train, users_valid, users_test, hist_valid, hist_test, _, pop = read_behaviors(
+        item_num, id2key, users_train, users_valid, users_test, hist_valid, hist_test, name_to_id, pop = read_behaviors(
             os.path.join(args.root_data_dir, args.dataset, args.behaviors), a, b, c, S, args.min_seq_len, Log)
         item_content = LmdbItemImages(LmdbImageStore(os.path.join(args.root_data_dir, args.dataset, args.image_lmdb)), id2key, args.CV_resize)
+        catalogue = dict(item_name_to_id=name_to_id)
     else:
         a, b, c = read_news(os.path.join(args.root_data_dir, args.dataset, args.news))
-        item_num, _, users_train, users_valid, users_test, hist_valid, hist_test, _, pop = read_behaviors(
+        item_num, _, users_train, users_valid, users_test, hist_valid, hist_test, name_to_id, pop = read_behaviors(
             os.path.join(args.root_data_dir, args.dataset, args.behaviors), a, b, c, S, args.min_seq_len, Log)
         item_content = np.arange(item_num + 1)
+        catalogue = dict(item_name_to_id=name_to_id)
     bert = None
     if vision:
         bert = HipSwinForImageClassification(SwinShape.named(args.CV_model_load), args.embedding_dim)   # V/run.py:47-54
@@ -409,7 +508,10 @@ def train(args, use_modal, local_rank):
     if args.mode == "test":                                             # T/run_test.py:115-128
         if ckpt is None:
             raise SystemExit("--mode test needs --load_ckpt_name epoch-N.pt")
-        return run_eval(model, item_content, hist_test, users_test, 512, item_num, use_modal, args, "test", local_rank)
+        hit10 = run_eval(model, item_content, hist_test, users_test, 512, item_num, use_modal, args, "test", local_rank)
+        if getattr(args, "cold_seqs", "None") != "None":
+            run_eval_special(model, item_content, catalogue, 512, item_num, use_modal, vision, args, local_rank)
+        return hit10
     stepper, optimizer = None, None
     if args.fused_step:
         stepper = TrainStep(model, lr=args.lr, fine_tune_lr=args.fine_tune_lr, l2_weight=args.l2_weight,

@@ -471,11 +471,19 @@ int morec_adamw_sp(float* param, const float* grad, float* exp_avg, float* exp_a
  * masking the history -- count-greater instead of a full argsort.
  * scores = prec[U, D] . item_emb[item_num+1, D]^T are formed tile by tile; rank[u] = 1 + #{items i>=1,
  * i not in history(u), score[u,i] > score[u,target[u]]}.
- * hist: int32 [U, Hmax] padded with -1.
+ * hist: int32 [U, Hmax] padded with -1, any length; repeats and ids outside [1, n_items_plus1) are harmless.
  * ------------------------------------------------------------------------------------------ */
 int morec_eval_rank(const float* prec, const float* item_emb, const int32_t* hist, int Hmax, const int32_t* target,
                     int32_t* rank, float* tscore_ws /* float[U] scratch */, int U, int n_items_plus1, int D,
                     void* stream);
+/* Cold-start / new-item evaluation (T/data_utils/special.py, eval_model_special): the target is a NEW item, a row of a separate
+ * candidate table, ranked against the whole catalogue (the reference appends it to the [item_num+1, D] table per user and
+ * argsorts).  rank[u] = 1 + #{items i in [1, n_items_plus1), i not in history(u) : score[u,i] > prec[u] . cand_emb[cand_idx[u]]}.
+ * The candidate is never masked and no catalogue column is excluded; ties do not count (as in morec_eval_rank).
+ * cand_emb: f32 [n_cand_rows, D]; cand_idx: int32 [U], row reads clamped into [0, n_cand_rows). */
+int morec_eval_rank_cand(const float* prec, const float* item_emb, const int32_t* hist, int Hmax, const float* cand_emb,
+                         int n_cand_rows, const int32_t* cand_idx, int32_t* rank, float* tscore_ws /* float[U] scratch */, int U,
+                         int n_items_plus1, int D, void* stream);
 
 /* test hook: out[i] = 1 iff the dropout hash keeps element index i for (p, seed) */
 int morec_dropout_keep_mask(uint8_t* out, size_t n, float p, uint64_t seed, void* stream);
