@@ -32,6 +32,11 @@ class GemmDesc(C.Structure):
                 ("accumulate", C.c_int), ("split_k", C.c_int), ("alpha", C.c_float), ("aux_deriv", C.c_int)]
 
 
+class GemmPlanInfo(C.Structure):      # morec_gemm_plan_info
+    _fields_ = [("family", C.c_int), ("mode", C.c_int), ("tile_rows", C.c_int), ("tile_cols", C.c_int), ("ngroup", C.c_int),
+                ("colsum_fused", C.c_int), ("family_name", C.c_char_p)]
+
+
 class AttnDesc(C.Structure):
     _fields_ = [("n_seq", C.c_int), ("T", C.c_int), ("n_heads", C.c_int), ("dh", C.c_int), ("causal", C.c_int),
                 ("scale", C.c_float), ("mask_value", C.c_float), ("dtype", C.c_int), ("p_drop", C.c_float),
@@ -69,6 +74,7 @@ _SIGS = {
     "morec_gemm_nt": (C.c_int, [C.POINTER(GemmDesc), _P, _P, _P, _P, _P, _P, _P]),
     "morec_gemm_nt_colsum": (C.c_int, [C.POINTER(GemmDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "morec_gemm_colsum_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "morec_gemm_plan": (C.c_int, [C.POINTER(GemmDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GemmPlanInfo)]),
     "morec_gemm_tn": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "morec_gemm_tn_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "morec_mlp_dact_recompute_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -707,8 +707,7 @@ int morec_attn_f32mfma_launch(const morec_attn_desc* d, const void* qkv, const f
 static void warn_valu_fallback(const morec_attn_desc* d) {
     if (!is_h16(d->dtype)) return;
     static const bool once = [](const morec_attn_desc* q) {
-        const char* e = getenv("MOREC_QUIET");
-        if (!(e && e[0] == '1'))
+        if (!tuning().quiet)
             fprintf(stderr, "libmorec_hip: attention with T = %d, head width %d is outside the MFMA path (T <= 64, head width %% 32 == 0): "
                             "running the VALU kernels for this and every later such call\n", q->T, q->dh);
         return true;

@@ -384,8 +384,7 @@ int attn_spare_blocks(const morec_attn_desc* d);      // attention.hip
 // kernels of attention.hip take it).  MOREC_ATTN_F32_MFMA=0 switches the path off (A/B).
 int morec_attn_f32mfma_launch(const morec_attn_desc* d, const void* qkv, const float* key_keep, void* ctx_or_dctx, void* dqkv, bool backward,
                               hipStream_t s) {
-    static const bool off = [] { const char* e = getenv("MOREC_ATTN_F32_MFMA"); return e && e[0] == '0'; }();
-    if (off || d->dtype != MOREC_F32 || d->T > 32 || d->dh % 16 != 0) return MOREC_E_UNSUPPORTED;
+    if (!tuning().attn_f32_mfma || d->dtype != MOREC_F32 || d->T > 32 || d->dh % 16 != 0) return MOREC_E_UNSUPPORTED;
     const int H = d->n_heads * d->dh;
     if (!aligned16(qkv) || !aligned16(ctx_or_dctx) || (dqkv && !aligned16(dqkv)) || H % 4) return MOREC_E_UNSUPPORTED;
     A32Args a{reinterpret_cast<const float*>(qkv), key_keep, reinterpret_cast<float*>(ctx_or_dctx), reinterpret_cast<float*>(dqkv),

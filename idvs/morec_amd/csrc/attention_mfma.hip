@@ -520,8 +520,7 @@ int morec_attn_mfma64_launch(const morec_attn_desc* d, const void* qkv, const fl
 int morec_attn_mfma_launch(const morec_attn_desc* d, const void* qkv, const float* key_keep, void* ctx_or_dctx,
                            void* dqkv, bool backward, hipStream_t s, float* csum) {
     if (is_h16(d->dtype) && d->dh % 32 == 0 && d->T > 32 && d->T <= 64) {
-        static const bool off = [] { const char* e = getenv("MOREC_ATTN_MFMA64"); return e && e[0] == '0'; }();      // MOREC_ATTN_MFMA64=0: the VALU kernels (A/B)
-        if (!off) return morec_attn_mfma64_launch(d, qkv, key_keep, ctx_or_dctx, dqkv, backward, s, csum);
+        if (tuning().attn_mfma64) return morec_attn_mfma64_launch(d, qkv, key_keep, ctx_or_dctx, dqkv, backward, s, csum);
     }
     if (!is_h16(d->dtype) || d->dh % 32 != 0 || d->T > 32) return MOREC_E_UNSUPPORTED;
     AttnMArgs a{reinterpret_cast<const bf16*>(qkv), key_keep, reinterpret_cast<bf16*>(ctx_or_dctx),

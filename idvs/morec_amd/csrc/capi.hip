@@ -29,17 +29,7 @@ extern "C" int morec_dropout_seed_source(const void* dev_u64) {
     return MOREC_OK;
 }
 
-// ---- deterministic mode (common.hpp) ----------------------------------------------------------------------------------------------
-static int g_deterministic = -1;
-bool morec_deterministic() {
-    if (g_deterministic < 0) {
-        const char* e = getenv("MOREC_DETERMINISTIC");
-        g_deterministic = (e && atoi(e) != 0) ? 1 : 0;
-    }
-    return g_deterministic != 0;
-}
-void morec_set_deterministic(int on) { g_deterministic = on ? 1 : 0; }
-
+// ---- deterministic mode (common.hpp; the switch itself is a row of the knob table, tuning.hip) ---------------------------------------
 // Library-owned partial-sum scratch of the deterministic mode, one buffer per (device, stream) -- launches on a stream are ordered, so they
 // share it.  nullptr = "not available": the callers return an error (never a silent fall-back to the atomic kernels).  Growth frees and
 // reallocates, which a stream that is being CAPTURED must not do (a graph would keep the freed address): under capture a request the

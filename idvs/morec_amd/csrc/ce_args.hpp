@@ -26,8 +26,7 @@ struct Ce8Layout {           // byte offsets into the caller's workspace
     int tiles_m, tiles_n, Ncp, K2, ldr, tn_split;
 };
 
-// 0: automatic (large enough bf16 problems), 1: never, 2: wherever the shape rules allow (tests)
-extern int g_ce8p_mode;
+// tuning key "ce8p": 0 automatic (large enough bf16 problems), 1 never, 2 wherever the shape rules allow (tests)
 bool ce8p_eligible(const morec_ce_desc* d);
 void ce8p_layout(const morec_ce_desc* d, Ce8Layout& L);
 int ce8p_fwd(const morec_ce_desc* d, const void* P, const void* E, const int32_t* row_ids, const int32_t* col_ids, const float* col_logpop,

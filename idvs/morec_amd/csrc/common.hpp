@@ -6,6 +6,7 @@
 #include <math.h>
 #include <type_traits>
 #include "morec_hip.h"
+#include "tuning.hpp"
 
 #define MOREC_WAVE 64
 
@@ -424,7 +425,7 @@ static inline bool by_h16(int dtype, F&& f) {
         if (e__ != hipSuccess) return (int)e__;     \
     } while (0)
 
-// ---- deterministic mode (MOREC_DETERMINISTIC=1 / morec_tuning_set("deterministic", 1); capi.hip).  The reference sets torch's
+// ---- deterministic mode (MOREC_DETERMINISTIC=1 / morec_tuning_set("deterministic", 1); tuning.hip, scratch in capi.hip).  The reference sets torch's
 // deterministic flags (T/run.py:313-314).  The kernels that end in fp32 atomics -- column sums of LayerNorm / bias gradients, the
 // embedding-table scatters -- then leave per-block partials in a library-owned scratch instead and a second launch adds them to the
 // destination in a FIXED order (or, for the scatters, one wave owns a destination row and sums its sources in index order): two runs of

@@ -13,63 +13,77 @@ extern "C" size_t morec_gemm_colsum_workspace_bytes(int M, int N) {
     return (size_t)((M + 31) / 32) * (size_t)N * sizeof(float);      // one partial row per 32-row wave block at most (gemm_small.hip)
 }
 
-extern "C" int morec_gemm_nt_colsum(const morec_gemm_desc* d, const void* A, const void* B, void* C, const float* bias,
-                                    void* aux_out, const void* dact_in, float* colsum_out, float* workspace, void* stream) {
-    if (!d || !A || !B || !C) return MOREC_E_ARG;
-    if (colsum_out) {
-        if (!workspace) return MOREC_E_ARG;
+// The checks of a call in the order callers see them; shared by the launch and by morec_gemm_plan (which has no operands: aligned = true).
+static int check_gemm_desc(const morec_gemm_desc* d, bool aligned, bool dact_in, bool aux_out, bool colsum) {
+    if (colsum) {
         if (d->dact == MOREC_ACT_NONE || d->accumulate != 0 || d->split_k > 1) return MOREC_E_UNSUPPORTED;
         const int os_ = elt_size(d->out_dtype);
         if ((d->N * os_) % 16 || (d->ldc * os_) % 16) return MOREC_E_UNSUPPORTED;     // needs the LDS-staged epilogues
     }
     if (d->M <= 0 || d->N <= 0 || d->K <= 0) return MOREC_E_ARG;
     const int es = elt_size(d->in_dtype), os = elt_size(d->out_dtype);
-    if (!aligned16(A) || !aligned16(B) || !aligned16(C) || (bias && !aligned16(bias))) return MOREC_E_ALIGN;
+    if (!aligned) return MOREC_E_ALIGN;
     if ((d->lda * es) % 16 || (d->ldb * es) % 16 || (d->K * es) % 16) return MOREC_E_ALIGN;
     if (d->N % 4 || (d->ldc * os) % (4 * os) || d->ldc % 4) return MOREC_E_ALIGN;
     if (d->split_k > 1 && d->accumulate != 2) return MOREC_E_ARG;
     if (d->accumulate == 2 && d->out_dtype != MOREC_F32) return MOREC_E_DTYPE;
     if (d->dact != MOREC_ACT_NONE && !dact_in) return MOREC_E_ARG;
     if (d->dact != MOREC_ACT_NONE && d->act != MOREC_ACT_NONE) return MOREC_E_ARG;
-    GemmArgs a;
+    if (d->aux_deriv && (d->act == MOREC_ACT_NONE || !aux_out)) return MOREC_E_ARG;
+    return MOREC_OK;
+}
+
+static bool rows_16_byte_addressable(const morec_gemm_desc* d) {
+    const int os = elt_size(d->out_dtype);
+    return (d->N * os) % 16 == 0 && (d->ldc * os) % 16 == 0;
+}
+
+extern "C" int morec_gemm_nt_colsum(const morec_gemm_desc* d, const void* A, const void* B, void* C, const float* bias,
+                                    void* aux_out, const void* dact_in, float* colsum_out, float* workspace, void* stream) {
+    if (!d || !A || !B || !C) return MOREC_E_ARG;
+    if (colsum_out && !workspace) return MOREC_E_ARG;
+    const bool aligned = aligned16(A) && aligned16(B) && aligned16(C) && (!bias || aligned16(bias));
+    const int rc = check_gemm_desc(d, aligned, dact_in, aux_out, colsum_out);
+    if (rc) return rc;
+    GemmArgs a{};
     a.A = A; a.B = B; a.C = C; a.bias = bias; a.aux_out = aux_out; a.dact_in = dact_in;
     a.M = d->M; a.N = d->N; a.K = d->K; a.lda = d->lda; a.ldb = d->ldb; a.ldc = d->ldc;
     a.act = d->act; a.dact = d->dact; a.accumulate = d->accumulate; a.alpha = d->alpha;
     a.aux_deriv = d->aux_deriv;
-    if (d->aux_deriv && (d->act == MOREC_ACT_NONE || !aux_out)) return MOREC_E_ARG;
     a.colsum = colsum_out ? workspace : nullptr;
     a.colsum_dst = colsum_out;
-    {   // epilogue form: per-wave LDS slices without workgroup barriers pay off where the epilogue is heavy (GELU + the second
-        // output) or the tile row is short (N <= 1024); measured per shape with scripts/gemm_bench.py.  MOREC_GEMM_EPI=w|b forces one.
-        static int we = -1;
-        if (we < 0) { const char* e = getenv("MOREC_GEMM_EPI"); we = !e ? 2 : (e[0] == 'w' ? 1 : 0); }
-        a.wave_epilogue = we == 2 ? ((aux_out != nullptr || d->N <= 1024) ? 1 : 0) : we;
-    }
-    a.vec_store = ((d->N * os) % 16 == 0) && ((d->ldc * os) % 16 == 0) && (!aux_out || aligned16(aux_out));
+    a.vec_store = rows_16_byte_addressable(d) && (!aux_out || aligned16(aux_out));
+    const GemmOperands o{bias != nullptr, aux_out != nullptr, dact_in != nullptr, colsum_out != nullptr, a.vec_store != 0, aligned16(bias)};
+    const GemmPlan p = gemm_plan(*d, o, tuning(), gemm8p_cu_count());
+    a.wave_epilogue = p.wave_epilogue;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    {   // narrow outputs over very many rows (Swin stage 1 / 2): the streaming kernel (gemm_skinny.hip)
-        const int rs = gemm_skinny_try_launch(d, a, s);
-        if (rs != G8_NOT_TAKEN) return rs;
-        const int rw = gemm_skinny_wide_try_launch(d, a, s);      // 288 < N <= 512, K <= 128 (stage-1 fc1 + GELU without a second output)
-        if (rw != G8_NOT_TAKEN) return rw;
+    switch (p.family) {
+        case GEMM_SKINNY: return gemm_skinny_launch(p, a, s);
+        case GEMM_SKINNY_WIDE: return gemm_skinny_wide_launch(p, a, s);
+        case GEMM_TWO_W: return gemm2w_launch(p, a, s);
+        case GEMM_EIGHT_P: return gemm8p_launch(p, a, s);
+        case GEMM_SMALL: return gemm_small_launch(p, a, s);
+        case GEMM_GENERIC:
+            if (p.in_dtype == MOREC_F16) return gemm_nt_f16_launch(p, a, s);
+            if (p.in_dtype == MOREC_F32) return launch_gemm<float, float>(p, a, s);
+            return p.out_dtype == MOREC_BF16 ? launch_gemm<bf16, bf16>(p, a, s) : launch_gemm<bf16, float>(p, a, s);
+        default: return p.error;
     }
-    {   // epilogue-heavy 16-bit products: 256 x 128 tiles, two workgroups per CU (gemm2w.hip)
-        const int r2 = gemm2w_try_launch(d, a, s);
-        if (r2 != G8_NOT_TAKEN) return r2;
-    }
-    {   // bf16, large: the 256 x 256 eight-phase kernel (gemm8p.hip)
-        const int r8 = gemm8p_try_launch(d, a, s);
-        if (r8 != G8_NOT_TAKEN) return r8;
-    }
-    {   // latency-class 16-bit products (the SASRec layers): 64 x 64 tiles on a four-stage ring (gemm_small.hip)
-        const int rs = gemm_small_try_launch(d, a, s);
-        if (rs != G8_NOT_TAKEN) return rs;
-    }
-    if (d->in_dtype == MOREC_F32 && d->out_dtype == MOREC_F32) return launch_gemm<float, float>(d, a, s);
-    if (d->in_dtype == MOREC_BF16 && d->out_dtype == MOREC_BF16) return launch_gemm<bf16, bf16>(d, a, s);
-    if (d->in_dtype == MOREC_BF16 && d->out_dtype == MOREC_F32) return launch_gemm<bf16, float>(d, a, s);
-    if (d->in_dtype == MOREC_F16) return gemm_nt_f16_launch(d, a, s);       // gemm_f16.hip
-    return MOREC_E_DTYPE;
+}
+
+// The planner's answer for a descriptor, without operands and (with n_cu > 0) without a device.
+extern "C" int morec_gemm_plan(const morec_gemm_desc* d, int has_bias, int has_aux, int has_dact_in, int has_colsum, int n_cu,
+                               morec_gemm_plan_info* out) {
+    if (!d || !out) return MOREC_E_ARG;
+    static const char* const names[] = {"unsupported", "skinny", "skinny_wide", "two_w", "eight_p", "small", "generic"};
+    *out = morec_gemm_plan_info{MOREC_GEMM_UNSUPPORTED, 0, 0, 0, 0, 0, names[0]};
+    const int rc = check_gemm_desc(d, true, has_dact_in, has_aux, has_colsum);
+    if (rc) return rc;
+    const GemmOperands o{has_bias != 0, has_aux != 0, has_dact_in != 0, has_colsum != 0, rows_16_byte_addressable(d), true};
+    const GemmPlan p = gemm_plan(*d, o, tuning(), n_cu > 0 ? n_cu : gemm8p_cu_count());
+    if (p.family == GEMM_UNSUPPORTED) return p.error;
+    *out = morec_gemm_plan_info{p.family, p.mode, p.tile_rows, p.tile_cols, p.ngroup, p.colsum, names[p.family]};
+    return MOREC_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -20,8 +20,6 @@
 // end are "refilled" with out-of-range offsets (the DMA writes zeros, no memory traffic), so the counts are the same for every K-tile.
 // One tile per workgroup (a plain grid, XCD-contiguous tile order in column groups): a workgroup's fill and drain are covered by its CU
 // partner the same way its epilogue is.
-#include <stdlib.h>
-#include <string.h>
 #include "gemm8p_core.hpp"
 #include "gemm_args.hpp"
 
@@ -362,61 +360,32 @@ __global__ __launch_bounds__(THREADS2, 2) void gemm2w_kernel(GemmArgs p) {
 }
 
 template <typename TI, int ACT, bool CS>
-int launch2w(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s) {
-    a.tiles_m = (d->M + WM - 1) / WM;
-    a.tiles_n = (d->N + WN - 1) / WN;
+int launch2w(const GemmPlan& p, GemmArgs& a, hipStream_t s) {
+    a.tiles_m = (a.M + WM - 1) / WM;
+    a.tiles_n = (a.N + WN - 1) / WN;
     static const bool attr = [] {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm2w_kernel<TI, TI, ACT, CS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS2);
         return true;
     }();
     (void)attr;
-    a.ngroup = a.tiles_n <= 8 ? 0 : 8;
+    a.ngroup = p.ngroup;
     hipLaunchKernelGGL((gemm2w_kernel<TI, TI, ACT, CS>), dim3(a.tiles_m * a.tiles_n), dim3(THREADS2), LDS2, s, a);
     MOREC_CHECK_LAUNCH();
-    if constexpr (CS) return colsum_f32_launch(a.colsum, a.colsum_dst, a.tiles_m * 2, d->N, s);
+    if constexpr (CS) return colsum_f32_launch(a.colsum, a.colsum_dst, a.tiles_m * 2, a.N, s);
     return MOREC_OK;
 }
+static_assert(WM == gplan::W2_TM && WN == gplan::W2_TN && KE == gplan::W2_KE, "gemm_plan.hpp");
 }  // namespace
 
-// tuning key "gemm2w" / MOREC_GEMM2W: 0 = automatic (the epilogue-heavy products), 1 = never, 2 = every eligible product
-int g_mode2w = -1;
-int gemm2w_try_launch(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s) {
-    if (g_mode2w < 0) {
-        const char* e = getenv("MOREC_GEMM2W");
-        g_mode2w = e ? atoi(e) : 0;
+// epilogues: plain / bias (0), GELU with an optional second output (1), x dact_in with optional column sums (5) -- gemm_plan.hpp, rule 3
+int gemm2w_launch(const GemmPlan& p, GemmArgs& a, hipStream_t s) {
+    a.debug = tuning().gemm2w_stagger;
+    if (p.in_dtype == MOREC_F16) {
+        if (p.mode == 5) return p.colsum ? launch2w<f16, 5, true>(p, a, s) : launch2w<f16, 5, false>(p, a, s);
+        if (p.mode == 1) return launch2w<f16, 1, false>(p, a, s);
+        return launch2w<f16, 0, false>(p, a, s);
     }
-    if (g_mode2w == 1) return G8_NOT_TAKEN;
-    if (!is_h16(d->in_dtype) || d->out_dtype != d->in_dtype || a.accumulate != 0 || !a.vec_store || d->split_k > 1) return G8_NOT_TAKEN;
-    if (d->K % KE || d->K < KE || d->N % 8 || d->M < 1) return G8_NOT_TAKEN;
-    if (d->dact != MOREC_ACT_NONE && d->dact != MOREC_DACT_MUL) return G8_NOT_TAKEN;
-    if (d->dact == MOREC_DACT_MUL && a.bias) return G8_NOT_TAKEN;
-    if (d->act == MOREC_ACT_RELU || (a.aux_out && d->act != MOREC_ACT_GELU)) return G8_NOT_TAKEN;
-    if (a.colsum && (d->dact != MOREC_DACT_MUL || d->M < 128)) return G8_NOT_TAKEN;
-    const long tiles = (long)((d->M + WM - 1) / WM) * ((d->N + WN - 1) / WN);
-    if (tiles < 64) return G8_NOT_TAKEN;
-    const int mode = d->dact == MOREC_DACT_MUL ? 5 : d->act == MOREC_ACT_GELU ? 1 : 0;
-    if (g_mode2w != 2) {
-        // Automatic: where this kernel measured FASTER than gemm8p on random operands (profiles/r06_gemm2w_shapes.txt).  Both kernels hold the part's
-        // power limit on random fp16 data (same binary on zero operands: gemm2w 1.43 PFLOP/s, gemm8p 1.18 at N = 3072, K = 768, against 0.93 / 0.96
-        // on N(0, 0.5) operands: profiles/r06_gemm_power_probe.txt), so what is left to win is work, not schedule:
-        //  (a) plain products whose N fills 256-wide tiles badly (N = 384: three 128-wide tiles instead of two 256-wide ones, a quarter of whose
-        //      MFMAs, LDS and DMA traffic are padding): Swin-T stage 3, 1.11 - 1.30 x;
-        //  (b) x act' + column sums over fewer rows (Swin-T stage 4, Swin-B stage 3): 1.04 - 1.07 x.
-        const long waste = (long)((d->N + 255) / 256) * 256 - d->N;
-        const bool narrow = mode == 0 && !a.colsum && waste * 4 >= d->N && d->M >= 8192 && d->K <= 2048;
-        const bool dmul = mode == 5 && d->M >= 16384 && ((d->M <= 40000 && d->K <= 768) || (d->M <= 70000 && d->K <= 512));
-        if (!narrow && !dmul) return G8_NOT_TAKEN;
-    }
-    {
-        static const int stagger = [] { const char* e = getenv("MOREC_GEMM2W_STAGGER"); return e ? atoi(e) : 0; }();
-        a.debug = stagger;
-    }
-    if (d->in_dtype == MOREC_F16) {
-        if (mode == 5) return a.colsum ? launch2w<f16, 5, true>(d, a, s) : launch2w<f16, 5, false>(d, a, s);
-        if (mode == 1) return launch2w<f16, 1, false>(d, a, s);
-        return launch2w<f16, 0, false>(d, a, s);
-    }
-    if (mode == 5) return a.colsum ? launch2w<bf16, 5, true>(d, a, s) : launch2w<bf16, 5, false>(d, a, s);
-    if (mode == 1) return launch2w<bf16, 1, false>(d, a, s);
-    return launch2w<bf16, 0, false>(d, a, s);
+    if (p.mode == 5) return p.colsum ? launch2w<bf16, 5, true>(p, a, s) : launch2w<bf16, 5, false>(p, a, s);
+    if (p.mode == 1) return launch2w<bf16, 1, false>(p, a, s);
+    return launch2w<bf16, 0, false>(p, a, s);
 }

@@ -23,8 +23,6 @@
 //      phase 0: B-second of K-tile t+1   phase 1: A-second of t+1   phase 2: A-first of t+2   phase 3: B-first of t+2
 // Every refill is issued 5-6 phases before its first read; a wave may read a region one phase after the counted wait that
 // retires it (its own pieces) + the barrier behind that wait (everybody else's).
-#include <stdlib.h>
-#include <string.h>
 #include <mutex>
 #include "gemm8p_core.hpp"
 #include "gemm_args.hpp"
@@ -66,7 +64,7 @@ struct TileXY {
     int krem;      // elements of K inside the unit's last K-tile (64 unless the unit ends at a K that is not a multiple of 64)
 };
 
-// TMR: rows of a tile -- 256, or 224 / 192 (wave row 1 owns three / two 32-row blocks instead of four): "tile height", below, at launch8p.
+// TMR: rows of a tile -- 256, or 224 / 192 (wave row 1 owns three / two 32-row blocks instead of four): "tile height" in gemm_plan.hpp (pick_tmr).
 template <typename TI, typename TO, int ACT, bool CS, int TMR = 256>
 __device__ __forceinline__ void tile_body(const GemmArgs& p, char* smem, const bf16* __restrict__ Acur, const bf16* __restrict__ Bcur,
                                           const bf16* __restrict__ Anext, const bf16* __restrict__ Bnext, const TileXY cur, const TileXY nxt,
@@ -555,184 +553,67 @@ static void tail_workspace(hipStream_t s, int n_cu, GemmArgs& a) {
     ++n_slots;
 }
 
-int g_reserve_cus = 0;      // tuning key "gemm8p_reserve_cus"
-int gemm8p_cu_count() {     // CUs the persistent grid uses right now (device count rounded to the 8 XCDs, minus the reserved ones)
-    static const int n_dev = [] {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        n &= ~7;
-        return n < 8 ? 8 : n;
-    }();
-    const int n = n_dev - (g_reserve_cus & ~7);
-    return n < 8 ? 8 : n;
-}
-// tuning key "gemm8p_ngroup": 0 = row-major tile order, -1 = automatic column groups (default: FETCH_SIZE per launch -20 % on the QKV
-// projection, -24 % on FFN-up + GELU, -23 % on its backward at equal launch times; profiles/r03_gemm8p_tile_order_pmc.txt), n = groups of n N-tiles
-int g_ngroup = -1;
+static_assert(TM == gplan::P8_TM && TN == gplan::P8_TN && KE == gplan::P8_KE, "gemm_plan.hpp");
 
-// ---- tile height.  A launch is ceil(tiles / CUs) ROUNDS of tiles; with 256-row tiles the encoder's N = 768 products at ~55 k token rows
-// are 645 tiles = 2.52 rounds, i.e. THREE rounds of tile time for 2.52 rounds of work (16 % of the launch is idle CUs), N = 3072 is 10.08
-// rounds -> eleven.  The number of rounds is an integer either way, but the tile's height need not be 256: with 224-row tiles (wave row 1
-// owns three 32-row blocks instead of four; its fourth block's MFMAs are branched around, everything else -- barriers, DMA, LDS image --
-// is the 256-row schedule) the same N = 768 product is 738 tiles = 2.88 rounds of 7/8-size tiles: three rounds x 0.875.  pick_tmr takes
-// the height in {256, 224, 192} with the smallest rounds x (K-tiles x height / 256 + fixed per-tile cost in K-tile units), 256 on ties.
-// The result is the same numbers bit for bit (a tile boundary does not enter any sum).  MOREC_GEMM8P_TMR=0 / tuning key "gemm8p_tmr" 0: off.
-int g_tmr_mode = -1;      // -1: read MOREC_GEMM8P_TMR on first use; 0: always 256; 1: automatic; 224 / 192: forced where an instantiation exists
-static int pick_tmr(int M, int tiles_n, int nk, int n_cu) {
-    if (g_tmr_mode < 0) {
-        const char* e = getenv("MOREC_GEMM8P_TMR");
-        g_tmr_mode = e ? atoi(e) : 1;
-    }
-    if (g_tmr_mode == 0) return TM;
-    if (g_tmr_mode == 224 || g_tmr_mode == 192) return g_tmr_mode;
-    const double fixed = 4.0;      // prologue + first barrier + epilogue of a tile, in K-tile times (profiles/r03_gemm8p_stamps.txt: ~8.4 k of 2.25 k cycles)
-    int best = TM;
-    double best_cost = 0.0;
-    for (int t : {256, 224, 192}) {
-        const long tiles = (long)((M + t - 1) / t) * tiles_n;
-        if (tiles <= n_cu && t != TM) continue;                                        // a single round: nothing to balance
-        const double cost = (double)((tiles + n_cu - 1) / n_cu) * ((double)nk * t / 256.0 + fixed);
-        if (t == TM || cost < best_cost * 0.985) { if (t == TM || cost < best_cost) { best = t; best_cost = cost; } }
-    }
-    return best;
-}
-
+// (tile height, tile order and tail split are chosen in gemm_plan.hpp: pick_tmr, rule 4)
 template <typename TI, typename TO, int ACT, bool CS, int TMR = 256>
-int launch8p(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s) {
-    constexpr bool PART = TMR != TM;
-    const int tmr = TMR;
+int launch8p(const GemmPlan& p, GemmArgs& a, hipStream_t s) {
     a.tmr = TMR;
-    a.tiles_m = (d->M + tmr - 1) / tmr;
-    a.tiles_n = (d->N + TN - 1) / TN;
-    static const int n_cu_dev = [] {      // thread-safe one-time set-up (function-local static)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8p_kernel<TI, TO, ACT, CS, TMR>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  LDS_TOTAL);
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        n &= ~7;      // a multiple of the 8 XCDs: workgroup b and its later tiles b + k * grid stay on XCD b % 8
-        return n < 8 ? 8 : n;
-    }();
-    // morec_tuning_set("gemm8p_reserve_cus", r): leave r CUs (rounded to a multiple of 8) out of the persistent grid -- room for the
-    // workgroups of a concurrent RCCL ring kernel when the step runs data-parallel (a persistent 160-KiB-LDS workgroup per CU
-    // otherwise owns the whole chip until its launch ends)
-    int n_cu = n_cu_dev - (g_reserve_cus & ~7);
-    if (n_cu < 8) n_cu = 8;
+    a.tiles_m = (a.M + TMR - 1) / TMR;
+    a.tiles_n = (a.N + TN - 1) / TN;
+    static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8p_kernel<TI, TO, ACT, CS, TMR>),
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);      // thread-safe one-time set-up
+    (void)attr_rc;
+    // the persistent grid: gemm8p_cu_count() workgroups.  morec_tuning_set("gemm8p_reserve_cus", r) leaves r CUs (rounded to a multiple
+    // of 8) out of it -- room for the workgroups of a concurrent RCCL ring kernel when the step runs data-parallel (a persistent
+    // 160-KiB-LDS workgroup per CU otherwise owns the whole chip until its launch ends)
+    const int n_cu = p.n_cu;
     const int nwg = a.tiles_m * a.tiles_n;
-    {   // column groups of the tile order: automatic = groups of about 6 N-tiles (a 32-CU XCD then works on a ~5 x 6 block)
-        const int ng = (a.tiles_n + 5) / 6;
-        a.ngroup = g_ngroup < 0 ? (a.tiles_n + ng - 1) / ng : g_ngroup;
-    }
+    a.ngroup = p.ngroup;
     a.tail_ws = nullptr;
     a.tail_cnt = nullptr;
-    // Tail split: OPT-IN (tuning key "gemm8p_tail_split" / MOREC_GEMM8P_TAIL_SPLIT=1).  It is as accurate as the unsplit sum (same
-    // error against an exact product) but rounds 0.02 % of the outputs the other way, and a 12-layer bf16 encoder at random init
-    // turns that into +-1e-2 on the step-0 loss (tests/test_bench_mode_parity_gpu.py); the default keeps the summation order of
-    // the two-buffer kernels (bit-identical outputs) for 0.35 % of the step time.
-    if (!PART && a.tail_split && nwg > n_cu && nwg % n_cu && 2 * (nwg % n_cu) <= n_cu && d->K >= 24 * KE && !(a.debug & 128)) tail_workspace(s, n_cu, a);
+    if (p.tail_split) tail_workspace(s, n_cu, a);
     hipLaunchKernelGGL((gemm8p_kernel<TI, TO, ACT, CS, TMR>), dim3(nwg < n_cu ? nwg : n_cu), dim3(THREADS), LDS_TOTAL, s, a);
     MOREC_CHECK_LAUNCH();
-    if constexpr (CS) return colsum_f32_launch(a.colsum, a.colsum_dst, a.tiles_m * 2, d->N, s);
+    if constexpr (CS) return colsum_f32_launch(a.colsum, a.colsum_dst, a.tiles_m * 2, a.N, s);
     return MOREC_OK;
-}
-}  // namespace
-
-// 0: automatic (eligible large problems), 1: never, 2: every eligible problem regardless of size
-static int g_mode8p = -1, g_debug8p = 0, g_tail_bias = 2, g_tail_split = 0;
-extern int g_mode2w;      // gemm2w.hip
-extern int g_mode_small;  // gemm_small.hip
-static unsigned long long g_stamps = 0;
-extern "C" int morec_tuning_set(const char* key, int value) {
-    if (!key) return MOREC_E_ARG;
-    if (!strcmp(key, "deterministic")) { morec_set_deterministic(value); return MOREC_OK; }
-    if (!strcmp(key, "gemm8p")) { g_mode8p = value; return MOREC_OK; }
-    if (!strcmp(key, "gemm2w")) { g_mode2w = value; return MOREC_OK; }
-    if (!strcmp(key, "gemm_small")) { g_mode_small = value; return MOREC_OK; }
-    if (!strcmp(key, "gemm8p_debug")) { g_debug8p = value; return MOREC_OK; }
-    if (!strcmp(key, "gemm8p_tail_split")) { g_tail_split = value != 0; return MOREC_OK; }
-    if (!strcmp(key, "ce8p")) { g_ce8p_mode = value; return MOREC_OK; }
-    if (!strcmp(key, "gemm_skinny")) { g_skinny_mode = value; return MOREC_OK; }
-    if (!strcmp(key, "gemm8p_ngroup")) { g_ngroup = value; return MOREC_OK; }
-    if (!strcmp(key, "gemm8p_tmr")) { g_tmr_mode = (value == 0 || value == 1 || value == 224 || value == 192) ? value : 1; return MOREC_OK; }
-    if (!strcmp(key, "gemm8p_reserve_cus")) { g_reserve_cus = value < 0 ? 0 : value > 128 ? 128 : value; return MOREC_OK; }
-    if (!strcmp(key, "gemm8p_tail_bias")) { g_tail_bias = value < 0 ? 0 : value > 16 ? 16 : value; return MOREC_OK; }
-    // device buffer (16 x 8 bytes per workgroup) that receives s_memtime stamps of wave 0: address in two halves
-    if (!strcmp(key, "gemm8p_stamps_lo")) { g_stamps = (g_stamps & 0xffffffff00000000ull) | (unsigned)value; return MOREC_OK; }
-    if (!strcmp(key, "gemm8p_stamps_hi")) { g_stamps = (g_stamps & 0xffffffffull) | ((unsigned long long)(unsigned)value << 32); return MOREC_OK; }
-    return MOREC_E_UNSUPPORTED;
-}
-
-int gemm8p_mode() {
-    if (g_mode8p < 0) {
-        const char* e = getenv("MOREC_GEMM8P");
-        g_mode8p = e ? atoi(e) : 0;
-        if (const char* d = getenv("MOREC_GEMM8P_DEBUG")) g_debug8p = atoi(d);     // ablation bits for whole-step A/B runs
-        if (const char* t = getenv("MOREC_GEMM8P_TAIL_SPLIT")) g_tail_split = atoi(t) != 0;
-        if (const char* n = getenv("MOREC_GEMM8P_NGROUP")) g_ngroup = atoi(n);
-        if (const char* c = getenv("MOREC_CE8P")) g_ce8p_mode = atoi(c);
-        if (const char* r = getenv("MOREC_GEMM8P_RESERVE_CUS")) { const int v = atoi(r); g_reserve_cus = v < 0 ? 0 : v > 128 ? 128 : v; }
-    }
-    return g_mode8p;
 }
 
 template <typename TI>
-static int dispatch8p(const morec_gemm_desc* d, GemmArgs& a, int mode, hipStream_t s) {
-    // tile height (see pick_tmr): the PART instantiations exist for the three kernels of the encoder step -- plain, FFN-up + GELU (+ act'),
-    // x act' + column sums -- with 16-bit outputs
-    a.tmr = TM;
-    if (d->out_dtype == h16<TI>::dtype && ((mode == 0 && !a.colsum) || (mode == 1 && !a.colsum) || (mode == 5 && a.colsum))) {
-        const int t = pick_tmr(d->M, (d->N + TN - 1) / TN, (d->K + KE - 1) / KE, gemm8p_cu_count());
-        if (t == 224) {
-            if (mode == 0) return launch8p<TI, TI, 0, false, 224>(d, a, s);
-            if (mode == 1) return launch8p<TI, TI, 1, false, 224>(d, a, s);
-            return launch8p<TI, TI, 5, true, 224>(d, a, s);
-        }
-        if (t == 192) {
-            if (mode == 0) return launch8p<TI, TI, 0, false, 192>(d, a, s);
-            if (mode == 1) return launch8p<TI, TI, 1, false, 192>(d, a, s);
-            return launch8p<TI, TI, 5, true, 192>(d, a, s);
-        }
+int dispatch8p(const GemmPlan& p, GemmArgs& a, hipStream_t s) {
+    const int mode = p.mode;
+    if (p.tile_rows == 224) {
+        if (mode == 0) return launch8p<TI, TI, 0, false, 224>(p, a, s);
+        if (mode == 1) return launch8p<TI, TI, 1, false, 224>(p, a, s);
+        return launch8p<TI, TI, 5, true, 224>(p, a, s);
     }
-    if (d->out_dtype == MOREC_F32) {
-        if (mode != 0 || a.colsum) return G8_NOT_TAKEN;
-        return launch8p<TI, float, 0, false>(d, a, s);
+    if (p.tile_rows == 192) {
+        if (mode == 0) return launch8p<TI, TI, 0, false, 192>(p, a, s);
+        if (mode == 1) return launch8p<TI, TI, 1, false, 192>(p, a, s);
+        return launch8p<TI, TI, 5, true, 192>(p, a, s);
     }
-    if (d->out_dtype != h16<TI>::dtype) return G8_NOT_TAKEN;
-    if (a.colsum) {
-        if (mode == 3) return launch8p<TI, TI, 3, true>(d, a, s);
-        if (mode == 4) return launch8p<TI, TI, 4, true>(d, a, s);
-        if (mode == 5) return launch8p<TI, TI, 5, true>(d, a, s);
-        return G8_NOT_TAKEN;
+    if (p.out_dtype == MOREC_F32) return launch8p<TI, float, 0, false>(p, a, s);
+    if (p.colsum) {
+        if (mode == 3) return launch8p<TI, TI, 3, true>(p, a, s);
+        if (mode == 4) return launch8p<TI, TI, 4, true>(p, a, s);
+        return launch8p<TI, TI, 5, true>(p, a, s);
     }
     switch (mode) {
-        case 1: return launch8p<TI, TI, 1, false>(d, a, s);
-        case 2: return launch8p<TI, TI, 2, false>(d, a, s);
-        case 3: return launch8p<TI, TI, 3, false>(d, a, s);
-        case 4: return launch8p<TI, TI, 4, false>(d, a, s);
-        case 5: return launch8p<TI, TI, 5, false>(d, a, s);
-        default: return launch8p<TI, TI, 0, false>(d, a, s);
+        case 1: return launch8p<TI, TI, 1, false>(p, a, s);
+        case 2: return launch8p<TI, TI, 2, false>(p, a, s);
+        case 3: return launch8p<TI, TI, 3, false>(p, a, s);
+        case 4: return launch8p<TI, TI, 4, false>(p, a, s);
+        case 5: return launch8p<TI, TI, 5, false>(p, a, s);
+        default: return launch8p<TI, TI, 0, false>(p, a, s);
     }
 }
+}  // namespace
 
-int gemm8p_try_launch(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s) {
-    (void)gemm8p_mode();
-    if (g_mode8p == 1) return G8_NOT_TAKEN;
-    if (!is_h16(d->in_dtype) || a.accumulate != 0 || !a.vec_store || d->split_k > 1) return G8_NOT_TAKEN;
-    if (d->K % 8 || d->K <= KE || d->N < 64 || d->M < 1) return G8_NOT_TAKEN;      // 16-byte slots; at least two K-tiles (the last may be partial)
-    const long tiles = (long)((d->M + TM - 1) / TM) * ((d->N + TN - 1) / TN);
-    if (a.colsum && d->M < 128) return G8_NOT_TAKEN;      // partial-row workspace is sized per 64 rows
-    // automatic: enough tiles to fill the 256 CUs, and at most a quarter of the tile columns past N (N = 192, 384, 576 of the Swin
-    // stages: faster here than in the two-buffer kernel; N = 96 is not -- profiles/r02_swin_gemm_shapes_modes.txt)
-    // (long-K problems already from 160 tiles: the scoring backward's dE = dl^T P, 168 tiles of 40 K-tiles each)
-    if (g_mode8p != 2 && (tiles < (d->K >= 2048 ? 160 : 192) || ((d->N + TN - 1) / TN) * TN * 100L > d->N * 134L)) return G8_NOT_TAKEN;
-    if (d->dact != MOREC_ACT_NONE && a.bias) return G8_NOT_TAKEN;      // no bias register set in the derivative epilogues
-    const int mode = d->dact == MOREC_ACT_GELU ? 3 : d->dact == MOREC_ACT_RELU ? 4 : d->dact == MOREC_DACT_MUL ? 5
-                     : d->act == MOREC_ACT_GELU ? 1 : d->act == MOREC_ACT_RELU ? 2 : 0;
-    a.debug = g_debug8p;
-    a.tail_bias = g_tail_bias;
-    a.tail_split = g_tail_split;
-    a.stamps = reinterpret_cast<unsigned long long*>(g_stamps);
-    if (d->in_dtype == MOREC_F16) return dispatch8p<f16>(d, a, mode, s);
-    return dispatch8p<bf16>(d, a, mode, s);
+int gemm8p_launch(const GemmPlan& p, GemmArgs& a, hipStream_t s) {
+    const Tuning& t = tuning();
+    a.debug = t.gemm8p_debug;
+    a.tail_bias = t.gemm8p_tail_bias;
+    a.tail_split = t.gemm8p_tail_split;
+    a.stamps = reinterpret_cast<unsigned long long*>(t.gemm8p_stamps());
+    return p.in_dtype == MOREC_F16 ? dispatch8p<f16>(p, a, s) : dispatch8p<bf16>(p, a, s);
 }

@@ -1,7 +1,8 @@
 // gemm_args.hpp -- kernel argument block shared by the NT GEMM kernels (gemm.hip: two-buffer main loop;
-// gemm8p.hip: the 256 x 256 eight-phase main loop).
+// gemm8p.hip: the 256 x 256 eight-phase main loop) and the launchers morec_gemm_nt switches over.
 #pragma once
 #include "common.hpp"
+#include "gemm_plan.hpp"
 
 struct GemmArgs {
     const void* A;
@@ -27,19 +28,16 @@ struct GemmArgs {
     int tail_bias;   // gemm8p tail split: the consumer takes (nk + tail_bias) / 2 of the nk K-tiles
     int* tail_cnt;   // gemm8p tail split: one arrival counter per tail tile (zero between launches)
     int ngroup;      // gemm8p: N-tiles per column group of the tile order (0 / >= tiles_n: plain row-major order)
-    int tmr;         // gemm8p: rows of an output tile (256, or 224 / 192: the PART instantiations -- see gemm8p.hip "tile height")
+    int tmr;         // gemm8p: rows of an output tile (256, or 224 / 192: the PART instantiations -- see gemm_plan.hpp "tile height")
 };
 
-// gemm8p.hip: runs the launch on the eight-phase kernel when the problem is eligible (returns MOREC_OK / an error) or
-// reports "not eligible" with G8_NOT_TAKEN so that the caller falls through to the generic kernels.
-#define G8_NOT_TAKEN 0x7fff0001
-int gemm8p_try_launch(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s);
-int gemm2w_try_launch(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s);      // gemm2w.hip: 256 x 128 tiles, two workgroups per CU (epilogue-heavy products)
-int gemm_small_try_launch(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s);       // gemm_small.hip: 64 x 64 tiles, four-stage ring (latency-class products)
-int gemm_skinny_try_launch(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s);      // gemm_skinny.hip: N <= 128, K <= 384, plain product
-int gemm_skinny_wide_try_launch(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s); // gemm_skinny_wide.hip: 288 < N <= 512, K <= 128, bias / GELU
-extern int g_skinny_mode;
-int gemm_nt_f16_launch(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s);      // gemm_f16.hip
+// One launcher per kernel family; gemm_plan() (gemm_plan.hpp) has already chosen the family and its parameters.
+int gemm_skinny_launch(const GemmPlan& p, GemmArgs& a, hipStream_t s);         // gemm_skinny.hip
+int gemm_skinny_wide_launch(const GemmPlan& p, GemmArgs& a, hipStream_t s);    // gemm_skinny_wide.hip
+int gemm2w_launch(const GemmPlan& p, GemmArgs& a, hipStream_t s);          // gemm2w.hip
+int gemm8p_launch(const GemmPlan& p, GemmArgs& a, hipStream_t s);        // gemm8p.hip
+int gemm_small_launch(const GemmPlan& p, GemmArgs& a, hipStream_t s);          // gemm_small.hip
+int gemm_nt_f16_launch(const GemmPlan& p, GemmArgs& a, hipStream_t s);    // gemm_f16.hip
 int colsum_f32_launch(const float* in, float* out, int rows, int N, hipStream_t s);
 // morec_gemm_tn with a choice of output type for the slab fold (gemm_tn.hip)
 int gemm_tn_launch(const void* DY, const void* X, void* C, int c_dtype, int M, int N, int K, int ldy, int ldx, int ldc, int dtype, int split_m,

@@ -2,8 +2,6 @@
 // small problems, split-K accumulation and narrow N of the fp16 mode; large ones run on the eight-phase kernel (gemm8p.hip).
 #include "gemm_nt_generic.hpp"
 
-int gemm_nt_f16_launch(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s) {
-    if (d->out_dtype == MOREC_F16) return launch_gemm<f16, f16>(d, a, s);
-    if (d->out_dtype == MOREC_F32) return launch_gemm<f16, float>(d, a, s);
-    return MOREC_E_DTYPE;
+int gemm_nt_f16_launch(const GemmPlan& p, GemmArgs& a, hipStream_t s) {
+    return p.out_dtype == MOREC_F16 ? launch_gemm<f16, f16>(p, a, s) : launch_gemm<f16, float>(p, a, s);
 }

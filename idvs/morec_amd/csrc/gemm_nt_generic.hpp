@@ -1,7 +1,6 @@
 // gemm_nt_generic.hpp -- the two-buffer NT GEMM kernel + its tile-shape / epilogue dispatch, shared by gemm.hip (fp32 and bf16
 // operands) and gemm_f16.hip (fp16 operands: a translation unit of its own so that the two sets of instantiations compile in parallel).
 #pragma once
-#include <stdlib.h>
 #include "gemm_core.hpp"
 #include "gemm_args.hpp"
 
@@ -276,14 +275,13 @@ __global__ __launch_bounds__(G::THREADS) void gemm_nt_kernel(GemmArgs p) {
 
 
 template <typename G, typename TI, typename TO, int ACT, bool CS = false>
-inline int launch_gemm_act(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s) {
-    const int split = d->split_k < 1 ? 1 : d->split_k;
-    int kchunk = (d->K + split - 1) / split;
+inline int launch_gemm_act(const GemmPlan& p, GemmArgs& a, hipStream_t s) {
+    int kchunk = (a.K + p.split_k - 1) / p.split_k;
     kchunk = ((kchunk + G::KE - 1) / G::KE) * G::KE;
     a.kchunk = kchunk;
-    const int zs = (d->K + kchunk - 1) / kchunk;
-    a.tiles_m = (d->M + G::TM - 1) / G::TM;
-    a.tiles_n = (d->N + G::TN - 1) / G::TN;
+    const int zs = (a.K + kchunk - 1) / kchunk;
+    a.tiles_m = (a.M + G::TM - 1) / G::TM;
+    a.tiles_n = (a.N + G::TN - 1) / G::TN;
     // one-time attribute set-up behind a function-local static: thread-safe first call (C++11), re-entrant afterwards
     static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_kernel<G, TI, TO, ACT, CS>),
                                                           hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
@@ -293,51 +291,38 @@ inline int launch_gemm_act(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s)
     MOREC_CHECK_LAUNCH();
     if constexpr (CS) {   // fold the partial rows: [tiles_m * WM (wave epilogue) | tiles_m (block epilogue)] x N -> colsum_dst +=
         const int rows = a.wave_epilogue ? a.tiles_m * G::WM : a.tiles_m;
-        return colsum_f32_launch(a.colsum, a.colsum_dst, rows, d->N, s);
+        return colsum_f32_launch(a.colsum, a.colsum_dst, rows, a.N, s);
     }
     return MOREC_OK;
 }
 
+// (bf16 operands -> fp32 output carries every epilogue as well: the fp32x3 mode's GEMMs, include/morec_hip.h morec_split_bf16x3)
 template <typename G, typename TI, typename TO>
-inline int launch_gemm_cfg(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s) {
-    const int mode = d->dact == MOREC_ACT_GELU ? 3 : d->dact == MOREC_ACT_RELU ? 4 : d->dact == MOREC_DACT_MUL ? 5
-                     : d->act == MOREC_ACT_GELU ? 1 : d->act == MOREC_ACT_RELU ? 2 : 0;
-    {   // (bf16 operands -> fp32 output carries every epilogue as well: the fp32x3 mode's GEMMs, include/morec_hip.h morec_split_bf16x3)
-        if (a.colsum) {     // fused bias gradient: only behind the activation-derivative epilogues
-            if (mode == 3) return launch_gemm_act<G, TI, TO, 3, true>(d, a, s);
-            if (mode == 4) return launch_gemm_act<G, TI, TO, 4, true>(d, a, s);
-            if (mode == 5) return launch_gemm_act<G, TI, TO, 5, true>(d, a, s);
-            return MOREC_E_UNSUPPORTED;
-        }
-        switch (mode) {
-            case 1: return launch_gemm_act<G, TI, TO, 1>(d, a, s);
-            case 2: return launch_gemm_act<G, TI, TO, 2>(d, a, s);
-            case 3: return launch_gemm_act<G, TI, TO, 3>(d, a, s);
-            case 4: return launch_gemm_act<G, TI, TO, 4>(d, a, s);
-            case 5: return launch_gemm_act<G, TI, TO, 5>(d, a, s);
-            default: return launch_gemm_act<G, TI, TO, 0>(d, a, s);
-        }
+inline int launch_gemm_cfg(const GemmPlan& p, GemmArgs& a, hipStream_t s) {
+    if (p.colsum) {     // fused bias gradient: only behind the activation-derivative epilogues (the planner refuses the others)
+        if (p.mode == 3) return launch_gemm_act<G, TI, TO, 3, true>(p, a, s);
+        if (p.mode == 4) return launch_gemm_act<G, TI, TO, 4, true>(p, a, s);
+        return launch_gemm_act<G, TI, TO, 5, true>(p, a, s);
+    }
+    switch (p.mode) {
+        case 1: return launch_gemm_act<G, TI, TO, 1>(p, a, s);
+        case 2: return launch_gemm_act<G, TI, TO, 2>(p, a, s);
+        case 3: return launch_gemm_act<G, TI, TO, 3>(p, a, s);
+        case 4: return launch_gemm_act<G, TI, TO, 4>(p, a, s);
+        case 5: return launch_gemm_act<G, TI, TO, 5>(p, a, s);
+        default: return launch_gemm_act<G, TI, TO, 0>(p, a, s);
     }
 }
 
-// 256 x 256 tiles when the problem is large enough to fill the 256 CUs with them, 128 x 128 tiles otherwise
+// the two-buffer kernel in the tile shape the planner chose (gemm_plan.hpp, rule 6).  The cases stand in the order in which the shapes
+// have always been instantiated: the device code then keeps its function numbering and scripts/isa_compare.py can compare it verbatim.
 template <typename TI, typename TO>
-inline int launch_gemm(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s) {
-    const long big_tiles = (long)((d->M + 255) / 256) * ((d->N + 255) / 256) * (d->split_k < 1 ? 1 : d->split_k);
-    static int force = -1;
-    if (force < 0) { const char* e = getenv("MOREC_GEMM_TILE"); force = e ? atoi(e) : 0; }   // 128 / 256: tuning override
-    if (force == 128) return launch_gemm_cfg<GemmTile<TI, 2>, TI, TO>(d, a, s);
-    if (force == 256) return launch_gemm_cfg<GemmTileCfg<TI, 2, 4, 8, 4>, TI, TO>(d, a, s);
-    if (force == 129) return launch_gemm_cfg<GemmTileCfg<TI, 2, 4, 4, 2>, TI, TO>(d, a, s);    // 128 x 128, 8 waves of 64 x 32
-    if (force == 2128) return launch_gemm_cfg<GemmTileCfg<TI, 4, 2, 4, 4, 1>, TI, TO>(d, a, s);  // 256 x 128, 8 waves, 2 workgroups per CU
-    if (force == 1024) return launch_gemm_cfg<GemmTileCfg<TI, 4, 4, 4, 4>, TI, TO>(d, a, s);   // 256 x 256, 16 waves of 64 x 64
-    // narrow outputs (N <= 128: the Swin stage-1 projections) and very short K (<= 96) are streaming problems: a 256-wide
-    // tile would be mostly padding / a 3-step main loop, and two independent 128 x 128 workgroups per CU overlap one's loads
-    // with the other's stores (measured per shape in scripts/swin_gemm_shapes.py)
-    if (d->N <= 128 || d->K <= 96) return launch_gemm_cfg<GemmTileCfg<TI, 2, 4, 4, 2>, TI, TO>(d, a, s);
-    // 256 x 256 as 16 waves of 64 x 64 (4 waves per SIMD, 118 VGPRs): 3 - 14 % faster than 8 waves of 128 x 64 on every encoder
-    // shape (scripts/gemm_bench.py) -- the extra waves cover each other's LDS / barrier waits
-    if (big_tiles >= 192) return launch_gemm_cfg<GemmTileCfg<TI, 4, 4, 4, 4>, TI, TO>(d, a, s);
-    return launch_gemm_cfg<GemmTileCfg<TI, 2, 4, 4, 2>, TI, TO>(d, a, s);   // 128 x 128 as 8 waves of 64 x 32 (same reasoning)
+inline int launch_gemm(const GemmPlan& p, GemmArgs& a, hipStream_t s) {
+    switch (p.generic_tile) {
+        case GEMM_TILE_128_W4: return launch_gemm_cfg<GemmTile<TI, 2>, TI, TO>(p, a, s);
+        case GEMM_TILE_256_W8: return launch_gemm_cfg<GemmTileCfg<TI, 2, 4, 8, 4>, TI, TO>(p, a, s);
+        default: return launch_gemm_cfg<GemmTileCfg<TI, 2, 4, 4, 2>, TI, TO>(p, a, s);      // GEMM_TILE_128_W8
+        case GEMM_TILE_256x128: return launch_gemm_cfg<GemmTileCfg<TI, 4, 2, 4, 4, 1>, TI, TO>(p, a, s);
+        case GEMM_TILE_256_W16: return launch_gemm_cfg<GemmTileCfg<TI, 4, 4, 4, 4>, TI, TO>(p, a, s);
+    }
 }
-

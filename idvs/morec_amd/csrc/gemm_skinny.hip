@@ -11,7 +11,6 @@
 // (column half) on v_mfma_f32_16x16x32_{bf16,f16}; two workgroups per CU (<= 80 KiB of LDS each).  The output tile goes through a
 // double-buffered LDS staging area so that the global stores are 16-byte lanes along rows (a 32 x N tile is one contiguous run of
 // memory when ldc == N).  Persistent grid: workgroup b takes tiles b, b + grid, ...
-#include <stdlib.h>
 #include "gemm_core.hpp"
 #include "gemm_args.hpp"
 
@@ -174,25 +173,23 @@ template <typename T16, int KS, int NBH>
 int launch_skinny(const SkArgs& a, hipStream_t s) {
     constexpr int SP = ((KS * 4 + 7) / 8) * 8;
     constexpr int LDS = NST * TR * SP * 16 + 2 * TR * (32 * NBH) * 2;
-    static const int n_cu = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_kernel<T16, KS, NBH>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        return n;
-    }();
+    static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_skinny_kernel<T16, KS, NBH>),
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    (void)attr_rc;
+    const int n_cu = device_cu_count();
     const int grid = a.tiles < 2 * n_cu ? a.tiles : 2 * n_cu;
     hipLaunchKernelGGL((gemm_skinny_kernel<T16, KS, NBH>), dim3(grid), dim3(THREADS), LDS, s, a);
     MOREC_CHECK_LAUNCH();
     return MOREC_OK;
 }
 
+// the k-step classes that are instantiated; the planner admits K <= 384 (12 k-steps), and K <= 96 (3) for the wide outputs (NBH 9)
 template <typename T16, int NBH>
 int dispatch_ks(const SkArgs& a, int ks, hipStream_t s) {
-    if constexpr (NBH > 4) {      // wide outputs (N <= 288: the stage-1 q|k|v projection) only with short K: 9 column blocks x 3 k-steps of B = 108 registers
+    if constexpr (NBH > 4) {
         if (ks <= 2) return launch_skinny<T16, 2, NBH>(a, s);
         if (ks == 3) return launch_skinny<T16, 3, NBH>(a, s);
-        return G8_NOT_TAKEN;
+        return MOREC_E_UNSUPPORTED;
     }
     switch (ks) {
         case 1: case 2: return launch_skinny<T16, 2, NBH>(a, s);
@@ -202,36 +199,19 @@ int dispatch_ks(const SkArgs& a, int ks, hipStream_t s) {
         case 7: case 8: return launch_skinny<T16, 8, NBH>(a, s);
         case 9: return launch_skinny<T16, 9, NBH>(a, s);
         case 10: case 11: case 12: return launch_skinny<T16, 12, NBH>(a, s);
-        default: return G8_NOT_TAKEN;
+        default: return MOREC_E_UNSUPPORTED;
     }
 }
+static_assert(TR == gplan::SK_TR, "gemm_plan.hpp");
 }  // namespace
 
-// tuning key "gemm_skinny": 0 = automatic (default), 1 = never
-int g_skinny_mode = -1;
-
 // Plain products and products with a bias (no activation / accumulation / second output): what the Swin engine asks of its narrow GEMMs.
-int gemm_skinny_try_launch(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s) {
-    if (g_skinny_mode < 0) {
-        const char* e = getenv("MOREC_GEMM_SKINNY");
-        g_skinny_mode = e ? atoi(e) : 0;
-    }
-    if (g_skinny_mode == 1) return G8_NOT_TAKEN;
-    if (!is_h16(d->in_dtype) || d->out_dtype != d->in_dtype) return G8_NOT_TAKEN;
-    if (a.aux_out || a.dact_in || a.colsum || d->act != MOREC_ACT_NONE || d->dact != MOREC_ACT_NONE || a.accumulate != 0 || d->split_k > 1 ||
-        d->alpha != 1.0f)
-        return G8_NOT_TAKEN;
-    if (d->N > 288 || d->N < 64 || d->N % 8 || d->K % 8 || d->K > 384 || d->M < 8192) return G8_NOT_TAKEN;
-    if (d->N > 128 && d->K > 96) return G8_NOT_TAKEN;
-    if (a.bias && (d->N % 4 || (reinterpret_cast<uintptr_t>(a.bias) & 15u))) return G8_NOT_TAKEN;
-    if (d->lda % 8 || d->ldb % 8 || d->ldc % 8) return G8_NOT_TAKEN;
-    if ((long)TR * d->lda * 2 >= 0x7fffffffL) return G8_NOT_TAKEN;
+int gemm_skinny_launch(const GemmPlan& p, GemmArgs& a, hipStream_t s) {
     SkArgs k;
     k.A = reinterpret_cast<const bf16*>(a.A); k.B = reinterpret_cast<const bf16*>(a.B); k.C = reinterpret_cast<bf16*>(a.C);
     k.bias = a.bias;
-    k.M = d->M; k.N = d->N; k.K = d->K; k.lda = d->lda; k.ldb = d->ldb; k.ldc = d->ldc; k.tiles = (d->M + TR - 1) / TR;
-    const int ks = (d->K + 31) / 32;
-    const int nbh = d->N <= 96 ? 3 : (d->N <= 128 ? 4 : 9);
-    if (d->in_dtype == MOREC_F16) return nbh == 3 ? dispatch_ks<f16, 3>(k, ks, s) : nbh == 4 ? dispatch_ks<f16, 4>(k, ks, s) : dispatch_ks<f16, 9>(k, ks, s);
+    k.M = a.M; k.N = a.N; k.K = a.K; k.lda = a.lda; k.ldb = a.ldb; k.ldc = a.ldc; k.tiles = (a.M + TR - 1) / TR;
+    const int nbh = p.nbh, ks = p.ksteps;
+    if (p.in_dtype == MOREC_F16) return nbh == 3 ? dispatch_ks<f16, 3>(k, ks, s) : nbh == 4 ? dispatch_ks<f16, 4>(k, ks, s) : dispatch_ks<f16, 9>(k, ks, s);
     return nbh == 3 ? dispatch_ks<bf16, 3>(k, ks, s) : nbh == 4 ? dispatch_ks<bf16, 4>(k, ks, s) : dispatch_ks<bf16, 9>(k, ks, s);
 }

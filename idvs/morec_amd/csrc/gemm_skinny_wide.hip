@@ -13,7 +13,6 @@
 // registers as MFMA fragments for the whole launch (held once per workgroup, not once per row block), A tiles stream through an
 // LDS ring by LDS-DMA with counted vmcnt, the output tile leaves through double-buffered LDS staging as 16-byte row pieces.
 // One workgroup per CU (dual: 144 fragment + 48 accumulator registers at C = 128), persistent grid.
-#include <stdlib.h>
 #include "gemm_core.hpp"
 #include "gemm_args.hpp"
 
@@ -233,12 +232,7 @@ __global__ __launch_bounds__(THREADS, OCC) void gemm_skinny_wide_kernel(WArgs p)
 }
 
 int wide_grid(int tiles, int occ) {
-    static const int n_cu = [] {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        return n;
-    }();
+    const int n_cu = device_cu_count();
     return tiles < occ * n_cu ? tiles : occ * n_cu;
 }
 
@@ -273,9 +267,11 @@ int dispatch_wide(WArgs& a, float* colsum_out, hipStream_t s) {
         if constexpr (DUAL) return launch_wide<T16, 6, 3, ACT, true, 3, 1, 2>(a, colsum_out, s);
         else return launch_wide<T16, 6, 6, ACT, false, 3, 1>(a, colsum_out, s);
     }
-    return G8_NOT_TAKEN;
+    return MOREC_E_UNSUPPORTED;
 }
+static_assert(TR == gplan::SK_TR, "gemm_plan.hpp");
 
+// the shapes of the recompute call; gemm_plan.hpp (rule 2) has the same bounds for the single product
 bool wide_shape_ok(int M, int N, int K, int lda, int ldb, int ldc) {
     if (N <= 288 || N > 768 || N % 8 || K % 8 || K > 192 || K < 32 || M < 8192) return false;
     if (lda % 8 || ldb % 8 || ldc % 8) return false;
@@ -284,22 +280,13 @@ bool wide_shape_ok(int M, int N, int K, int lda, int ldb, int ldc) {
 }
 }  // namespace
 
-// GELU(A . B^T + bias) without a second output: called from morec_gemm_nt after gemm_skinny_try_launch
-int gemm_skinny_wide_try_launch(const morec_gemm_desc* d, GemmArgs& a, hipStream_t s) {
-    if (g_skinny_mode == 1 || g_skinny_mode == 2) return G8_NOT_TAKEN;
-    if (!is_h16(d->in_dtype) || d->out_dtype != d->in_dtype) return G8_NOT_TAKEN;
-    // only the GELU product: a plain / bias-only product of these widths is faster on the tile kernel (measured: Swin-B stage-1 q|k|v 306 vs 334 us);
-    // what the streaming form buys is the epilogue-heavy, write-heavy launch
-    if (a.aux_out || a.dact_in || a.colsum || d->act != MOREC_ACT_GELU || d->dact != MOREC_ACT_NONE || a.accumulate != 0 || d->split_k > 1 ||
-        d->alpha != 1.0f)
-        return G8_NOT_TAKEN;
-    if (!wide_shape_ok(d->M, d->N, d->K, d->lda, d->ldb, d->ldc)) return G8_NOT_TAKEN;
-    if (a.bias && (d->N % 4 || (reinterpret_cast<uintptr_t>(a.bias) & 15u))) return G8_NOT_TAKEN;
+// GELU(A . B^T + bias) without a second output
+int gemm_skinny_wide_launch(const GemmPlan& p, GemmArgs& a, hipStream_t s) {
     WArgs k{};
     k.A = reinterpret_cast<const bf16*>(a.A); k.B = reinterpret_cast<const bf16*>(a.B); k.C = reinterpret_cast<bf16*>(a.C);
     k.bias = a.bias;
-    k.M = d->M; k.N = d->N; k.K = d->K; k.lda = d->lda; k.ldb = d->ldb; k.ldc = d->ldc; k.tiles = (d->M + TR - 1) / TR;
-    return d->in_dtype == MOREC_F16 ? dispatch_wide<f16, 1, false>(k, nullptr, s) : dispatch_wide<bf16, 1, false>(k, nullptr, s);
+    k.M = a.M; k.N = a.N; k.K = a.K; k.lda = a.lda; k.ldb = a.ldb; k.ldc = a.ldc; k.tiles = (a.M + TR - 1) / TR;
+    return p.in_dtype == MOREC_F16 ? dispatch_wide<f16, 1, false>(k, nullptr, s) : dispatch_wide<bf16, 1, false>(k, nullptr, s);
 }
 
 namespace {
@@ -314,11 +301,7 @@ bool dual_class_exists(int M, int N, int K, int dtype) {
 // Swin-T 1286 + 1025 -> 620 + 840 ... 980 us, Swin-B 640 + 501 -> 443 + 554); at K = 192 (Swin-T stage 2) the two column slices make the backward
 // launch slower than the act' read it replaces (500 + 418 -> 368 + 530 us), so the answer is no although morec_mlp_dact_recompute accepts the shape.
 extern "C" int morec_mlp_dact_recompute_supported(int M, int N, int K, int dtype) {
-    if (g_skinny_mode < 0) {
-        const char* e = getenv("MOREC_GEMM_SKINNY");
-        g_skinny_mode = e ? atoi(e) : 0;
-    }
-    if (g_skinny_mode == 1 || g_skinny_mode == 2) return 0;
+    if (tuning().gemm_skinny == 1 || tuning().gemm_skinny == 2) return 0;
     return (K <= 128 && dual_class_exists(M, N, K, dtype)) ? 1 : 0;
 }
 
@@ -341,6 +324,5 @@ extern "C" int morec_mlp_dact_recompute(const void* dY, const void* W2t, const v
     k.bias = b1;
     k.M = M; k.N = N; k.K = K; k.lda = K; k.ldb = K; k.ldc = N; k.lda2 = K; k.ldb2 = K; k.tiles = (M + TR - 1) / TR;
     k.colsum_ws = colsum_out ? workspace : nullptr;
-    const int rc = dtype == MOREC_F16 ? dispatch_wide<f16, 1, true>(k, colsum_out, s) : dispatch_wide<bf16, 1, true>(k, colsum_out, s);
-    return rc == G8_NOT_TAKEN ? MOREC_E_UNSUPPORTED : rc;
+    return dtype == MOREC_F16 ? dispatch_wide<f16, 1, true>(k, colsum_out, s) : dispatch_wide<bf16, 1, true>(k, colsum_out, s);
 }

@@ -223,13 +223,13 @@ int gemm_tn_launch(const void* DY, const void* X, void* C, int c_dtype, int M, i
     if (a.slabs && (K % 4 || !aligned16(workspace))) return MOREC_E_ALIGN;
     if (c_dtype != MOREC_F32 && (!a.slabs || accumulate)) return MOREC_E_UNSUPPORTED;
     if (zs > 1 && !a.slabs && !accumulate) return MOREC_E_ARG;
-    int r8 = G8_NOT_TAKEN;
+    int r8 = MOREC_E_UNSUPPORTED;      // = not eligible
     if (a.slabs)                    // split-m partials -> slabs: the eight-phase kernel (gemm_tn8p.hip) when the launch is large enough
         r8 = gemm_tn8p_try_launch(a.DY, a.X, a.slabs, (size_t)N * K, M, N, K, ldy, ldx, K, mchunk, zs, dtype, reinterpret_cast<hipStream_t>(stream));
     else if (zs == 1 && !accumulate)
         r8 = gemm_tn8p_try_launch(a.DY, a.X, a.C, 0, M, N, K, ldy, ldx, ldc, mchunk, 1, dtype, reinterpret_cast<hipStream_t>(stream));
-    if (r8 != G8_NOT_TAKEN && r8 != MOREC_OK) return r8;
-    if (r8 == G8_NOT_TAKEN) {
+    if (r8 != MOREC_E_UNSUPPORTED && r8 != MOREC_OK) return r8;
+    if (r8 == MOREC_E_UNSUPPORTED) {
         by_h16(dtype, [&](auto* t) {
             using T = MOREC_TAG_T(t);
             static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TN);   // thread-safe one-time set-up

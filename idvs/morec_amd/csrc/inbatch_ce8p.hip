@@ -322,15 +322,13 @@ int n_cus() {
 }
 }  // namespace
 
-int g_ce8p_mode = 0;
-
 bool ce8p_eligible(const morec_ce_desc* d) {
     const long Nr = (long)d->B * d->S;
-    if (g_ce8p_mode == 1) return false;
+    if (tuning().ce8p == 1) return false;
     if (!is_h16(d->dtype) || d->D % 8 || d->D <= KE || d->Nc % 8 || Nr % 8) return false;
     if ((long)d->Nc * d->D * 2 >= 0x7fffffffL || Nr * d->D * 2 >= 0x7fffffffL) return false;      // 32-bit DMA offsets within a panel run
     // enough 256 x 256 tiles to give most CUs one (below that the 128 x 128 kernels fill the chip better)
-    if (g_ce8p_mode == 2) return true;
+    if (tuning().ce8p == 2) return true;
     return ((Nr + 255) / 256) * (((long)d->Nc + 255) / 256) >= 96;
 }
 

@@ -684,8 +684,7 @@ int morec_swin_attn_mfma_launch(const morec_swin_attn_desc* d, const void* qkv, 
     // 1 ... 4 windows per wavefront the deep stages get from tiles / 8192 that was a third of its time -- at least 8 there (Swin-T stage 3, 704 images:
     // 182 -> 148 us; Swin-B's stage 2, 352 images: 183 -> 145 us; profiles/r05_swin_attn_pmc.txt).  The forward has no such tail and loses 8-17 % to the
     // smaller grid, so it keeps the plain rule.  MOREC_SWIN_WPW_MIN overrides the backward's floor.
-    static const int wpw_min_bwd = [] { const char* e = getenv("MOREC_SWIN_WPW_MIN"); return e ? std::max(1, atoi(e)) : 8; }();
-    a.wpw = (int)std::max<long>(backward ? wpw_min_bwd : 1, std::min<long>(32, tiles / 8192));
+    a.wpw = (int)std::max<long>(backward ? tuning().swin_wpw_min : 1, std::min<long>(32, tiles / 8192));
     a.gx = (a.n_win_total + 4 * a.wpw - 1) / (4 * a.wpw);
     if (csum_rows_needed) *csum_rows_needed = a.gx * 4;
     a.csum = (backward && csum && csum_rows >= (long)a.gx * 4) ? csum : nullptr;
@@ -699,7 +698,7 @@ int morec_swin_attn_mfma_launch(const morec_swin_attn_desc* d, const void* qkv, 
         if (!a.dbias_part) return (int)hipErrorOutOfMemory;
     }
     const size_t lds = (size_t)NT * BP * sizeof(float) + 4 * (2 * TILE + PTILE);
-    static const int wide = [] { const char* e = getenv("MOREC_SWIN_BWD_WIDE"); return e ? atoi(e) : 1; }();
+    const int wide = tuning().swin_bwd_wide;
     by_h16(d->dtype, [&](auto* t) {
         using T = MOREC_TAG_T(t);
         if (!backward) {

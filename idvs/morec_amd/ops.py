@@ -224,6 +224,17 @@ def gemm_nt(a, b, *, bias=None, act=ACT_NONE, out=None, out_dtype=None, aux_out=
 _DR_WS = {}
 
 
+def gemm_plan(M, N, K, dtype=torch.bfloat16, *, out_dtype=None, bias=False, aux=False, dact_in=False, colsum=False, act=ACT_NONE,
+              dact=ACT_NONE, accumulate=0, split_k=1, alpha=1.0, lda=None, ldb=None, ldc=None, n_cu=0):
+    """Which kernel ``gemm_nt`` would run for this product (``morec_gemm_plan``): a dict of family name, epilogue mode, tile rows / columns,
+    ngroup and the fused-column-sum flag.  ``n_cu`` > 0 answers for a chip of that many CUs without touching a device."""
+    d = _lib.GemmDesc(M, N, K, lda or K, ldb or K, ldc or N, code(dtype), code(out_dtype or dtype), act, dact, accumulate, split_k, alpha, 0)
+    info = _lib.GemmPlanInfo()
+    check(_lib.lib().morec_gemm_plan(C.byref(d), int(bias), int(aux), int(dact_in), int(colsum), n_cu, C.byref(info)), "morec_gemm_plan")
+    return {"family": info.family_name.decode(), "mode": info.mode, "tile_rows": info.tile_rows, "tile_cols": info.tile_cols,
+            "ngroup": info.ngroup, "colsum_fused": bool(info.colsum_fused)}
+
+
 def mlp_dact_recompute_supported(M, N, K, dtype):
     """Does ``mlp_dact_recompute`` take this shape (Swin stage-1 / stage-2 MLP: 288 < N <= 768, K <= 192, M >= 8192, 16-bit)?  The forward then
     runs fc1 + GELU WITHOUT the act'(pre) output."""

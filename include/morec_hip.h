@@ -25,13 +25,13 @@
  *
  * State the library keeps (everything else is stateless and re-entrant; first-call set-up of a kernel's launch attributes is
  * behind thread-safe function-local statics).  One process drives one GPU (the reference's process model, T/run.py:305-321):
- *   1. process-wide kernel-SELECTION knobs, morec_tuning_set() and the environment variables read once at the first GEMM
- *      launch: MOREC_GEMM8P (0 automatic | 1 never | 2 always the eight-phase kernel), MOREC_GEMM8P_TAIL_SPLIT (0 | 1),
- *      MOREC_GEMM8P_NGROUP (tile order), MOREC_GEMM8P_RESERVE_CUS, MOREC_GEMM_SKINNY, MOREC_CE8P, MOREC_GEMM8P_DEBUG (ablation bits), MOREC_GEMM_TILE /
- *      MOREC_GEMM_EPI (two-buffer kernel variants), MOREC_SWIN_BWD_WIDE.  Every selectable kernel computes the same function
- *      to the same accuracy; "gemm8p_tail_split" = 1 is the only knob that changes the fp32 SUMMATION ORDER (and with it the
- *      last-bit rounding pattern of bf16 outputs), which is why it is off unless asked for.  Set knobs before the first
- *      launch or between steps, not concurrently with launches;
+ *   1. process-wide knobs: ONE table (csrc/tuning.hip; the keys and MOREC_* variables are listed at morec_tuning_set below).  The
+ *      environment is read once, thread-safely, the first time the table is touched -- by a launch or by morec_tuning_set --
+ *      and supplies the defaults; a morec_tuning_set call wins over it from then on, whichever came first.  (Before, each
+ *      variable was read lazily at some first use, so whether a set key or its variable won depended on the order of calls.)
+ *      Every selectable kernel computes the same function to the same accuracy; "gemm8p_tail_split" = 1 is the only knob that
+ *      changes the fp32 SUMMATION ORDER (and with it the last-bit rounding pattern of bf16 outputs), which is why it is off
+ *      unless asked for.  Set knobs before the first launch or between steps, not concurrently with launches;
  *   2. with "gemm8p_tail_split" = 1 only: one device scratch allocation per stream (the only memory the library ever allocates);
  *   3. morec_comm handles (below): created and destroyed by the caller;
  *   4. the dropout seed source (morec_dropout_seed_source): one device pointer, NULL by default;
@@ -69,22 +69,43 @@ extern "C" {
 
 const char* morec_strerror(int code);
 int morec_version(void);
-/* Process-wide kernel-selection knobs (measurement / A-B aid; see "State the library keeps" above).  Keys:
- *   "gemm8p"             0 = automatic, 1 = never use the 256 x 256 eight-phase GEMM, 2 = use it wherever it is eligible;
- *   "gemm2w"             0 = automatic, 1 = never use the 256 x 128 two-workgroups-per-CU GEMM (gemm2w.hip: the epilogue-heavy products --
- *                        GELU + act' outputs, x act' + column sums -- with >= 1024 tiles), 2 = every eligible 16-bit product; env MOREC_GEMM2W;
- *   "gemm_small"         0 = automatic, 1 = never use the 64 x 64 four-stage-ring GEMM (gemm_small.hip: the narrow long-K products of the SASRec
- *                        layers, N-tiles of 128 x 128 < 128 and K >= 1024), 2 = every eligible 16-bit product; outputs bit-identical; env MOREC_GEMM_SMALL;
- *   "gemm8p_tail_split"  1 = split the last, partly filled round of tiles along K between two workgroups (K >= 1536);
- *   "gemm8p_tail_bias"   share of K the first part takes in that split;
- *   "gemm8p_ngroup"      tile order: -1 = automatic column groups (default), 0 = row-major, n = column groups of n N-tiles;
- *   "gemm8p_reserve_cus" CUs (multiple of 8) left out of the persistent grid for a concurrent RCCL kernel;
- *   "gemm_skinny"        0 = automatic, 2 = gemm_skinny only (no gemm_skinny_wide / recompute), 1 = never use the streaming kernels for narrow outputs (gemm_skinny: N <= 288, K <= 384; gemm_skinny_wide:
- *                        N <= 768, K <= 192, GELU(product + bias); M >= 8192) -- morec_mlp_dact_recompute_supported() then answers 0;
- *   "ce8p"               scoring kernels: 0 = automatic, 1 = always the 128 x 128 kernels, 2 = the 256 x 256 eight-phase kernels
- *                        wherever the shape rules allow (bf16, D > 64, D % 8 == Nc % 8 == (B S) % 8 == 0);
- *   "deterministic"      1 = fixed summation order everywhere (state item 6), 0 = off; overrides MOREC_DETERMINISTIC;
- *   "gemm8p_debug", "gemm8p_stamps_lo/hi"  ablation bits / device address of a cycle-stamp buffer (diagnostics).
+/* Process-wide knobs (measurement / A-B aid; see "State the library keeps" above).  key | values | environment variable | default.
+ * Which NT GEMM kernel runs is decided by one function, gemm_plan() in csrc/gemm_plan.hpp; its rules are tried in the order
+ * skinny, skinny_wide, two_w, eight_p, small, generic, and morec_gemm_plan() below answers for a descriptor without a GPU.
+ *   "gemm8p"             0 automatic | 1 never | 2 wherever eligible                                   MOREC_GEMM8P              0
+ *                        the 256 x 256 eight-phase GEMM (16-bit operands, K % 8 == 0, K > 64, N >= 64, plain stores).  Automatic: at least
+ *                        192 tiles of 256 x 256 (160 when K >= 2048) and at most 34 % of the tile columns past N.  Also gemm_tn's eight-phase kernel;
+ *   "gemm2w"             0 automatic | 1 never | 2 every eligible product                              MOREC_GEMM2W              0
+ *                        the 256 x 128 two-workgroups-per-CU GEMM (16-bit in and out, K % 64 == 0, >= 64 tiles; plain / bias, GELU (+ second
+ *                        output), x dact_in (+ column sums)).  Automatic: plain products with M >= 8192, K <= 2048 whose N leaves at least a
+ *                        fifth of its 256-wide tiles empty (4 x padding >= N: N = 384, and also 128, 192, 320, 576), and x dact_in products
+ *                        with 16384 <= M <= 40000, K <= 768 or M <= 70000, K <= 512.  It is asked BEFORE gemm8p;
+ *   "gemm_small"         0 automatic | 1 never | 2 every eligible product                              MOREC_GEMM_SMALL          0
+ *                        the 64 x 64 four-stage-ring GEMM (16-bit in and out, K >= 64).  Automatic: at most 128 tiles of 128 x 128, K >= 1024,
+ *                        N >= 256, no second output, no column sums (the SASRec layers); outputs bit-identical to the 128 x 128 kernel's;
+ *   "gemm_skinny"        0 automatic | 1 never | 2 gemm_skinny only                                    MOREC_GEMM_SKINNY         0
+ *                        the streaming kernels, M >= 8192, 16-bit in and out, alpha 1, pitches % 8 == 0.  gemm_skinny: plain / bias products,
+ *                        64 <= N <= 128 with K <= 384, or N <= 288 with K <= 96.  gemm_skinny_wide: GELU(product + bias) without a second
+ *                        output, 288 < N <= 768, 32 <= K <= 192.  With 1 or 2 morec_mlp_dact_recompute_supported() answers 0;
+ *   "ce8p"               0 automatic | 1 always the 128 x 128 kernels | 2 wherever the shapes allow    MOREC_CE8P                0
+ *                        scoring kernels on 256 x 256 eight-phase tiles (16-bit, D > 64, D % 8 == Nc % 8 == (B S) % 8 == 0);
+ *   "gemm8p_tmr"         0 always 256-row tiles | 1 automatic | 224 | 192 (other values: 1)            MOREC_GEMM8P_TMR          1
+ *   "gemm8p_ngroup"      tile order: -1 automatic column groups | 0 row-major | n groups of n N-tiles  MOREC_GEMM8P_NGROUP       -1
+ *   "gemm8p_reserve_cus" 0..128 CUs (multiple of 8) left out of the persistent grid for a concurrent RCCL kernel   MOREC_GEMM8P_RESERVE_CUS   0
+ *   "gemm8p_tail_split"  1 = split the last, partly filled round of tiles along K between two workgroups (K >= 1536)   MOREC_GEMM8P_TAIL_SPLIT   0
+ *   "gemm8p_tail_bias"   0..16: share of K the first part takes in that split                          -                         2
+ *   "gemm8p_debug"       ablation bits (diagnostics)                                                   MOREC_GEMM8P_DEBUG        0
+ *   "gemm8p_stamps_lo", "gemm8p_stamps_hi"  device address of a cycle-stamp buffer, in halves          -                         0
+ *   "deterministic"      1 = fixed summation order everywhere (state item 6) | 0 off                   MOREC_DETERMINISTIC       0
+ * Environment only:
+ *   MOREC_GEMM_TILE      one tile shape for every two-buffer GEMM: 128 | 129 | 256 | 1024 | 2128 (csrc/gemm_plan.hpp)          0 = automatic
+ *   MOREC_GEMM_EPI       w = per-wave epilogue, anything else = block epilogue, in the two-buffer GEMMs                      unset = automatic
+ *   MOREC_GEMM2W_STAGGER first-round stagger experiment of gemm2w                                                           0
+ *   MOREC_TN8P_SKIP      0 = never the block-skipping variant of gemm_tn's eight-phase kernel                                1
+ *   MOREC_ATTN_MFMA64, MOREC_ATTN_F32_MFMA   0 = the VALU attention kernels for 32 < T <= 64 / for fp32                      1
+ *   MOREC_SWIN_WPW_MIN   fewest windows per workgroup of the window-attention backward (>= 1)                                8
+ *   MOREC_SWIN_BWD_WIDE  0 = the narrow window-attention backward                                                            1
+ *   MOREC_QUIET          1 = no once-per-process notes on stderr                                                             0
  * Returns MOREC_E_UNSUPPORTED for an unknown key.  No reference counterpart (the reference has no kernels). */
 int morec_tuning_set(const char* key, int value);
 /* Deterministic mode: make the partial-sum scratch of `stream` hold at least n_floats (call outside graph capture; under capture the
@@ -126,6 +147,30 @@ int morec_gemm_nt(const morec_gemm_desc* d, const void* A, const void* B, void* 
 size_t morec_gemm_colsum_workspace_bytes(int M, int N);
 int morec_gemm_nt_colsum(const morec_gemm_desc* d, const void* A, const void* B, void* C, const float* bias,
                          void* aux_out, const void* dact_in, float* colsum_out, float* workspace, void* stream);
+
+/* Which kernel morec_gemm_nt(_colsum) would run for this descriptor, asked of the same function the launch uses (csrc/gemm_plan.hpp)
+ * with the knobs as they stand.  has_*: whether bias / aux_out / dact_in / colsum_out would be passed; operands are assumed 16-byte
+ * aligned, pitches are those of d.  n_cu: CUs of gemm8p's persistent grid (it enters its tile height); <= 0 asks the current device,
+ * > 0 touches no device, so the call works on a machine without a GPU.  Returns what the launch would return before launching
+ * (MOREC_OK, or the MOREC_E_* of a refused descriptor, with family MOREC_GEMM_UNSUPPORTED).
+ * No reference counterpart (the reference has no kernels to select). */
+#define MOREC_GEMM_UNSUPPORTED 0
+#define MOREC_GEMM_SKINNY 1      /* gemm_skinny.hip: tile = 32 rows x (32 nbh) columns, nbh = 3 | 4 | 9 */
+#define MOREC_GEMM_SKINNY_WIDE 2 /* gemm_skinny_wide.hip: tile = 32 whole rows */
+#define MOREC_GEMM_TWO_W 3       /* gemm2w.hip: 256 x 128 */
+#define MOREC_GEMM_EIGHT_P 4     /* gemm8p.hip: 256 | 224 | 192 rows x 256 */
+#define MOREC_GEMM_SMALL 5       /* gemm_small.hip: 64 x 64 */
+#define MOREC_GEMM_GENERIC 6     /* two-buffer kernels: 128 x 128, 256 x 256 (256 x 128 only under MOREC_GEMM_TILE) */
+typedef struct {
+    int family;        /* MOREC_GEMM_* */
+    int mode;          /* epilogue: 0 plain (+ bias), 1 GELU, 2 ReLU, 3 x GELU'(dact_in), 4 x ReLU'(dact_in), 5 x dact_in */
+    int tile_rows, tile_cols;
+    int ngroup;        /* eight_p, two_w: N-tiles per column group of the tile order, 0 = row-major */
+    int colsum_fused;  /* the column sums ride on the epilogue */
+    const char* family_name; /* "skinny", "skinny_wide", "two_w", "eight_p", "small", "generic", "unsupported" (static storage) */
+} morec_gemm_plan_info;
+int morec_gemm_plan(const morec_gemm_desc* d, int has_bias, int has_aux, int has_dact_in, int has_colsum, int n_cu,
+                    morec_gemm_plan_info* out);
 
 /* Backward of  g = act(X . W1^T + b1) -> fc2  WITHOUT a stored act'(pre) tensor (GELU only):
  *   dU[M, N] = (dY[M, K] . W2t[N, K]^T) * act'(X[M, K] . W1[N, K]^T + b1[N]),   colsum_out[n] += sum_m dU[m, n]  (= d b1)
