@@ -71,6 +71,11 @@ _SIGS = {
     "morec_tuning_set": (C.c_int, [C.c_char_p, C.c_int]),
     "morec_det_scratch_reserve": (C.c_int, [C.c_size_t, C.c_void_p]),
     "morec_stream_wait_stream": (C.c_int, [_P, _P]),
+    "morec_fold_defer_begin": (C.c_int, [_P]),
+    "morec_fold_defer_active": (C.c_int, []),
+    "morec_fold_flush": (C.c_int, [_P]),
+    "morec_fold_defer_end": (C.c_int, []),
+    "morec_fold_stats": (C.c_int, [_P]),
     "morec_gemm_nt": (C.c_int, [C.POINTER(GemmDesc), _P, _P, _P, _P, _P, _P, _P]),
     "morec_gemm_nt_colsum": (C.c_int, [C.POINTER(GemmDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "morec_gemm_colsum_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),

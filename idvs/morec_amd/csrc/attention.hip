@@ -766,6 +766,8 @@ extern "C" int morec_attn_bwd_dbias(const morec_attn_desc* d, const void* qkv, c
     const int H3 = 3 * d->n_heads * d->dh;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (ws && ws_bytes >= (size_t)d->n_seq * H3 * sizeof(float)) {
+        ws = morec_fold_workspace(ws, (size_t)d->n_seq * H3, s);
+        if (!ws) return (int)hipErrorOutOfMemory;
         rc = morec_attn_mfma_launch(d, qkv, key_keep, const_cast<void*>(dctx), dqkv, true, s, ws);
         if (rc == MOREC_OK) return colsum_f32_launch(ws, dbias, d->n_seq, H3, s);
         if (rc != MOREC_E_UNSUPPORTED) return rc;

@@ -433,10 +433,26 @@ static inline bool by_h16(int dtype, F&& f) {
 bool morec_deterministic();
 void morec_set_deterministic(int on);
 // fp32 scratch of at least n floats for launches on stream s (one buffer per (device, stream): launches of one stream are ordered, two
-// streams must not share); nullptr on allocation failure.  Grows by re-allocation behind a stream synchronisation.
+// streams must not share); nullptr on allocation failure.  Grows by re-allocation behind a stream synchronisation.  Under a deferred-fold
+// scope on s: a region of its own per call, intact until the scope ends.
 float* morec_det_scratch(hipStream_t s, size_t n);
 // dst[j] += part[0 * stride + j] + part[1 * stride + j] + ... (p ascending; j < n): plain read-modify-write, one thread per element
+// For PARAMETER gradients only: under a deferred-fold scope on s the add happens at the next morec_fold_flush, not in stream order.
 int morec_det_fold_add(const float* part, float* dst, int n_parts, size_t n, size_t stride, hipStream_t s);
+// The same, always launched in place: for a dst that a later kernel of the backward pass reads (the window attention's bias tiles).
+int morec_det_fold_add_now(const float* part, float* dst, int n_parts, size_t n, size_t stride, hipStream_t s);
+// Deferred folds (capi.hip; include/morec_hip.h: morec_fold_defer_begin).  While a scope is open on s, morec_det_scratch(s, ..) hands out
+// regions of the scope's bump allocator (morec_fold_scratch) and morec_det_fold_add / colsum_f32_launch queue a job instead of launching.
+// morec_fold_defer: true = queued (rpb == 0: a fold of cnt partial rows; rpb > 0: column sums of cnt rows of src in row blocks of rpb, then
+// the fold over the row blocks); false = no scope on s, the caller launches in place.
+bool morec_fold_deferring(hipStream_t s);
+float* morec_fold_scratch(hipStream_t s, size_t n);
+bool morec_fold_defer(const float* src, float* dst, size_t n, int cnt, size_t stride, int rpb, hipStream_t s);
+// The workspace whose rows a deferred column-sum job will read: under a scope on s a region of the scope's scratch takes the place of the
+// caller's buffer (which the caller is free to reuse as soon as the call returns); nullptr = that scratch is not available.
+static inline float* morec_fold_workspace(float* ws, size_t n_floats, hipStream_t s) {
+    return (ws && morec_deterministic() && morec_fold_deferring(s)) ? morec_fold_scratch(s, n_floats) : ws;
+}
 
 // XCD-aware workgroup -> tile mapping: the dispatcher round-robins consecutive workgroup ids over
 // the 8 XCDs (private L2 each); remap so that each XCD walks a CONTIGUOUS run of tiles, i.e. the

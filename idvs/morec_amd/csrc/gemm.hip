@@ -10,7 +10,9 @@ extern "C" int morec_gemm_nt(const morec_gemm_desc* d, const void* A, const void
 }
 
 extern "C" size_t morec_gemm_colsum_workspace_bytes(int M, int N) {
-    return (size_t)((M + 31) / 32) * (size_t)N * sizeof(float);      // one partial row per 32-row wave block at most (gemm_small.hip)
+    // one partial row per 32-row wave block at most (gemm_small.hip), counted over WHOLE tiles of up to 256 rows (a 24-row product on 128-row tiles
+    // with two wave rows writes 2 partial rows, not 1), + 8: gemm_skinny_wide rounds its worker count up to a multiple of 8
+    return ((size_t)((M + 255) / 256) * 8 + 8) * (size_t)N * sizeof(float);
 }
 
 // The checks of a call in the order callers see them; shared by the launch and by morec_gemm_plan (which has no operands: aligned = true).
@@ -50,6 +52,10 @@ extern "C" int morec_gemm_nt_colsum(const morec_gemm_desc* d, const void* A, con
     a.M = d->M; a.N = d->N; a.K = d->K; a.lda = d->lda; a.ldb = d->ldb; a.ldc = d->ldc;
     a.act = d->act; a.dact = d->dact; a.accumulate = d->accumulate; a.alpha = d->alpha;
     a.aux_deriv = d->aux_deriv;
+    if (colsum_out) {
+        workspace = morec_fold_workspace(workspace, morec_gemm_colsum_workspace_bytes(d->M, d->N) / sizeof(float), reinterpret_cast<hipStream_t>(stream));
+        if (!workspace) return (int)hipErrorOutOfMemory;
+    }
     a.colsum = colsum_out ? workspace : nullptr;
     a.colsum_dst = colsum_out;
     a.vec_store = rows_16_byte_addressable(d) && (!aux_out || aligned16(aux_out));
@@ -301,6 +307,8 @@ int colsum_f32_launch(const float* in, float* out, int rows, int N, hipStream_t 
     rpb = rpb < 16 ? 16 : rpb > 512 ? 512 : rpb;
     if ((long)rows * N <= (1L << 20) && rows <= 512) rpb = 512;     // small folds: one block per column group, i.e. a fixed summation order
     dim3 grid(cb, (rows + rpb - 1) / rpb);
+    // an open deferred-fold scope on s: the column sums and their fold become one job of the next morec_fold_flush (`in` stays the caller's)
+    if (morec_deterministic() && morec_fold_defer(in, out, (size_t)N, rows, (size_t)N, rpb, s)) return MOREC_OK;
     if (grid.y > 1 && morec_deterministic()) {      // several row blocks per column: their partials through the scratch, folded in order
         float* part = morec_det_scratch(s, (size_t)grid.y * N);
         if (!part) return (int)hipErrorOutOfMemory;
@@ -320,7 +328,8 @@ extern "C" int morec_colsum(const void* in, float* out, int M, int N, int ld, in
     dim3 grid((N + 63) / 64, (M + rpb - 1) / rpb);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     float* part = nullptr;
-    if (grid.y > 1 && morec_deterministic()) {
+    // (under a deferred-fold scope also a single row block goes through a partial row: its add into `out` keeps its place in the queue)
+    if (morec_deterministic() && (grid.y > 1 || morec_fold_deferring(s))) {
         part = morec_det_scratch(s, (size_t)grid.y * N);
         if (!part) return (int)hipErrorOutOfMemory;
     }

@@ -323,6 +323,10 @@ extern "C" int morec_mlp_dact_recompute(const void* dY, const void* W2t, const v
     k.A2 = reinterpret_cast<const bf16*>(X); k.B2 = reinterpret_cast<const bf16*>(W1);
     k.bias = b1;
     k.M = M; k.N = N; k.K = K; k.lda = K; k.ldb = K; k.ldc = N; k.lda2 = K; k.ldb2 = K; k.tiles = (M + TR - 1) / TR;
+    if (colsum_out) {
+        workspace = morec_fold_workspace(workspace, morec_mlp_dact_recompute_workspace_bytes(N) / sizeof(float), s);
+        if (!workspace) return (int)hipErrorOutOfMemory;
+    }
     k.colsum_ws = colsum_out ? workspace : nullptr;
     return dtype == MOREC_F16 ? dispatch_wide<f16, 1, true>(k, colsum_out, s) : dispatch_wide<bf16, 1, true>(k, colsum_out, s);
 }

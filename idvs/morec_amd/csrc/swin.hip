@@ -538,7 +538,7 @@ extern "C" int morec_swin_attn_bwd(const morec_swin_attn_desc* d, const void* qk
     MOREC_CHECK_LAUNCH();
     if (a.dbias_part)
         for (int h = 0; h < d->heads; ++h) {
-            rc = morec_det_fold_add(a.dbias_part + (size_t)h * gx * NT2, dbias_t + (size_t)h * NT2, gx, (size_t)NT2, (size_t)NT2, s);
+            rc = morec_det_fold_add_now(a.dbias_part + (size_t)h * gx * NT2, dbias_t + (size_t)h * NT2, gx, (size_t)NT2, (size_t)NT2, s);
             if (rc) return rc;
         }
     return MOREC_OK;
@@ -695,6 +695,8 @@ extern "C" int morec_swin_attn_bwd_dbias(const morec_swin_attn_desc* d, const vo
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (ws) {
         int need = 0;
+        ws = morec_fold_workspace(ws, ws_bytes / sizeof(float), s);
+        if (!ws) return (int)hipErrorOutOfMemory;
         rc = morec_swin_attn_mfma_launch(d, qkv, bias_t, const_cast<void*>(ctx), dctx, dqkv, dbias_t, true, s, ws,
                                          (long)(ws_bytes / (C3 * sizeof(float))), &need);
         if (rc == MOREC_OK) return colsum_f32_launch(ws, dbqkv, need, C3, s);

@@ -717,7 +717,7 @@ int morec_swin_attn_mfma_launch(const morec_swin_attn_desc* d, const void* qkv, 
     MOREC_CHECK_LAUNCH();
     if (a.dbias_part)      // deterministic mode: the workgroups' tiles in window-group order, one fold per head
         for (int h = 0; h < d->heads; ++h) {
-            const int rc = morec_det_fold_add(a.dbias_part + (size_t)h * a.gx * (NT * NT), dbias_t + (size_t)h * (NT * NT), a.gx, (size_t)(NT * NT), (size_t)(NT * NT), s);
+            const int rc = morec_det_fold_add_now(a.dbias_part + (size_t)h * a.gx * (NT * NT), dbias_t + (size_t)h * (NT * NT), a.gx, (size_t)(NT * NT), (size_t)(NT * NT), s);
             if (rc) return rc;
         }
     return MOREC_OK;

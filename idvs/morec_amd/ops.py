@@ -59,6 +59,30 @@ def stream_wait_stream(waiting, signal=None):
     check(_lib.lib().morec_stream_wait_stream(waiting, _stream() if signal is None else signal), "morec_stream_wait_stream")
 
 
+def fold_defer_begin() -> bool:
+    """Open the library's deferred-fold scope on torch's current stream (``morec_fold_defer_begin``): until ``fold_defer_end`` the
+    fixed-order folds of the deterministic mode issued on that stream are queued, and ``fold_flush`` launches them.  False: nothing was
+    opened (knob off, atomic mode, stream under graph capture) and every call behaves as usual."""
+    h = _lib.lib()
+    check(h.morec_fold_defer_begin(_stream()), "morec_fold_defer_begin")
+    return bool(h.morec_fold_defer_active())
+
+
+def fold_flush(stream=None):
+    """Launch the folds queued so far on ``stream`` (raw handle; default: torch's current stream).  The caller orders that stream behind the producers."""
+    check(_lib.lib().morec_fold_flush(_stream() if stream is None else stream), "morec_fold_flush")
+
+
+def fold_defer_end():
+    check(_lib.lib().morec_fold_defer_end(), "morec_fold_defer_end")
+
+
+def fold_stats() -> dict:
+    out = (C.c_ulonglong * 4)()
+    check(_lib.lib().morec_fold_stats(out), "morec_fold_stats")
+    return {"allocations": out[0], "scratch_bytes": out[1], "jobs": out[2], "launches": out[3]}
+
+
 def _dev(t):
     if not t.is_cuda:
         raise _lib.MorecError("libmorec_hip needs device tensors (no CPU fallback)")

@@ -221,6 +221,7 @@ class TrainStep:
         env_r = os.environ.get("MOREC_GEMM8P_RESERVE_CUS")
         self.reserve_cus = (int(env_r) if env_r is not None else 16) if rccl_ring else 0
         self._reserved = False
+        self._fold_open = False
         comm = comm if comm is not None else os.environ.get("MOREC_COMM", "")
         self.comm = self.comm_grad = self._grad_stream = None
         if comm == "rccl" and self.collectives and self.device.type == "cuda":
@@ -471,25 +472,34 @@ class TrainStep:
             gscale = self._gscale(n_valid)
         loss_sum, saved_c = engine.ce_forward(ci, P, Epool, dE_fp32=(self.collectives and self.pool))
         self._reserve(True)      # the backward pass starts: bucket collectives may run beside its GEMMs from here on
-        dP, dEpool = engine.ce_backward(ci, P, Epool, saved_c, gscale, 1.0)
-        dE = reduce_scatter_dE(dEpool, self.world, self.rank, self.dtype, self.comm) if (self.collectives and self.pool) else dEpool
-        dx = engine.sasrec_backward(p, prep_s, saved_s, dP, grads, engine.UE)
-        dE.view(B, S + 1, D)[:, :-1, :].add_(dx.view(B, S, D))      # the two sources of dE (T/model/model.py:39-41,49)
-        if dedup:   # slot gradients -> distinct-item gradients (fp32 accumulation), back to the compute dtype for the encoder
-            dE_u = torch.zeros((E_u.shape[0], D), device=dE.device, dtype=torch.float32)
-            ops.scatter_add_rows_(dE.contiguous(), inv32, dE_u, -1)
-            dE = dE_u if self.dtype == torch.float32 else ops.cast(dE_u, self.dtype)
-        if self.vision:
-            swin_engine.swin_backward(p, prep_b, saved_b, dE, grads, swin_engine.IN, on_ready=self._on_ready)
-        elif m.use_modal:
-            # mean over attributes: each pass receives dE / n; the passes share every parameter, their gradients ACCUMULATE in the arenas, so
-            # a bucket is final -- reduced over ranks / stepped -- only behind the LAST pass
-            d_pass = dE if len(passes) == 1 else ops.scaled_sum([dE.contiguous()], 1.0 / len(passes))
-            for ai, (_, saved_a) in enumerate(passes):
-                engine.bert_backward(p, prep_b, saved_a, d_pass, grads, engine.TE, on_ready=self._on_ready if ai == len(passes) - 1 else None)
-        else:
-            ops.scatter_add_rows_(dE, idx32, grads["id_embedding.weight"], 0)
-        engine.WgradStream.join(self.device)       # the weight gradients of the side stream are final from here on
+        # Deterministic mode: the fixed-order folds into bias / LayerNorm / position gradients leave the backward chain -- queued by the
+        # library from here on, launched once per finished bucket on the weight-gradient stream (``_fold_flush``), the rest in front of the join
+        self._fold_open = ops.fold_defer_begin()
+        try:
+            dP, dEpool = engine.ce_backward(ci, P, Epool, saved_c, gscale, 1.0)
+            dE = reduce_scatter_dE(dEpool, self.world, self.rank, self.dtype, self.comm) if (self.collectives and self.pool) else dEpool
+            dx = engine.sasrec_backward(p, prep_s, saved_s, dP, grads, engine.UE)
+            dE.view(B, S + 1, D)[:, :-1, :].add_(dx.view(B, S, D))      # the two sources of dE (T/model/model.py:39-41,49)
+            if dedup:   # slot gradients -> distinct-item gradients (fp32 accumulation), back to the compute dtype for the encoder
+                dE_u = torch.zeros((E_u.shape[0], D), device=dE.device, dtype=torch.float32)
+                ops.scatter_add_rows_(dE.contiguous(), inv32, dE_u, -1)
+                dE = dE_u if self.dtype == torch.float32 else ops.cast(dE_u, self.dtype)
+            if self.vision:
+                swin_engine.swin_backward(p, prep_b, saved_b, dE, grads, swin_engine.IN, on_ready=self._on_ready)
+            elif m.use_modal:
+                # mean over attributes: each pass receives dE / n; the passes share every parameter, their gradients ACCUMULATE in the arenas, so
+                # a bucket is final -- reduced over ranks / stepped -- only behind the LAST pass
+                d_pass = dE if len(passes) == 1 else ops.scaled_sum([dE.contiguous()], 1.0 / len(passes))
+                for ai, (_, saved_a) in enumerate(passes):
+                    engine.bert_backward(p, prep_b, saved_a, d_pass, grads, engine.TE, on_ready=self._on_ready if ai == len(passes) - 1 else None)
+            else:
+                ops.scatter_add_rows_(dE, idx32, grads["id_embedding.weight"], 0)
+            self._fold_flush()
+            engine.WgradStream.join(self.device)       # the weight gradients of the side stream are final from here on
+        finally:
+            if self._fold_open:      # behind the join: the main stream has waited for every flush, the partial-row scratch may be handed out again
+                self._fold_open = False
+                ops.fold_defer_end()
         ops.x3_cache_clear()
         return loss_sum[0] / n_valid
 
@@ -550,8 +560,24 @@ class TrainStep:
             self._pending.append(dist.all_reduce(t, async_op=True))
         self._reduced.append((gi, lo, hi))
 
+    def _fold_flush(self):
+        """Launch the folds the library has queued since the last flush (``ops.fold_defer_begin``): on the weight-gradient stream, behind
+        what the main stream holds now; on the main stream when there is no side stream.  Whatever is issued to the side stream afterwards
+        (a bucket's collective, its early AdamW) finds the bucket's bias / LayerNorm gradients final."""
+        if not self._fold_open:
+            return
+        side = engine.WgradStream.get(self.device)
+        if side is None:
+            ops.fold_flush()
+            return
+        sh = side.cuda_stream
+        ops.stream_wait_stream(sh)
+        ops.fold_flush(sh)
+        engine.WgradStream._dirty.add(self.device)
+
     def _on_ready(self, key):
         """Backward-pass callback of the engines: start reducing the gradients that have just become final."""
+        self._fold_flush()
         if not self.collectives:
             self._early_adamw(key)
             return

@@ -39,7 +39,9 @@
  *   6. deterministic mode only (morec_tuning_set("deterministic", 1) / MOREC_DETERMINISTIC=1; the reference sets torch's
  *      deterministic flags, T/run.py:313-314): one partial-sum scratch per (device, stream), grown on demand OUTSIDE graph capture
  *      (morec_det_scratch_reserve).  In this mode no kernel falls back to atomics: a call that cannot run its fixed-order form
- *      (scratch unavailable, no token order, row width outside the vector layout) returns an error instead.
+ *      (scratch unavailable, no token order, row width outside the vector layout) returns an error instead;
+ *   7. deterministic mode only: the deferred-fold scope (morec_fold_defer_begin): one host-side job list and one device scratch that is
+ *      sized during the first steps and then kept.
  */
 #ifndef MOREC_HIP_H
 #define MOREC_HIP_H
@@ -97,6 +99,7 @@ int morec_version(void);
  *   "gemm8p_debug"       ablation bits (diagnostics)                                                   MOREC_GEMM8P_DEBUG        0
  *   "gemm8p_stamps_lo", "gemm8p_stamps_hi"  device address of a cycle-stamp buffer, in halves          -                         0
  *   "deterministic"      1 = fixed summation order everywhere (state item 6) | 0 off                   MOREC_DETERMINISTIC       0
+ *   "fold_defer"         1 = morec_fold_defer_begin opens a scope (state item 7) | 0 = it never does   MOREC_FOLD_DEFER          1
  * Environment only:
  *   MOREC_GEMM_TILE      one tile shape for every two-buffer GEMM: 128 | 129 | 256 | 1024 | 2128 (csrc/gemm_plan.hpp)          0 = automatic
  *   MOREC_GEMM_EPI       w = per-wave epilogue, anything else = block epilogue, in the two-buffer GEMMs                      unset = automatic
@@ -112,6 +115,30 @@ int morec_tuning_set(const char* key, int value);
  * scratch cannot grow and a launch that needs more returns hipErrorOutOfMemory).  The largest user of the encoder step is the LayerNorm
  * backward: blocks x 3 x N floats.  No reference counterpart (torch.use_deterministic_algorithms, T/run.py:313-314, has no workspace API). */
 int morec_det_scratch_reserve(size_t n_floats, void* stream);
+/* Deferred folds (deterministic mode; knob "fold_defer").  The fixed-order folds of the deterministic mode -- the partial rows of the
+ * LayerNorm backward, the per-tile / per-sequence column sums behind morec_gemm_nt_colsum and morec_attn_bwd_dbias, morec_colsum, the
+ * position / type rows -- all add into PARAMETER gradients, which nothing in a backward pass reads (the per-head bias tiles of the window
+ * attention feed morec_swin_bias_reduce and are always folded in place).  Between morec_fold_defer_begin(stream)
+ * and morec_fold_defer_end() these calls, when issued on `stream`, launch their producing kernel as usual but only QUEUE the fold;
+ * morec_fold_flush(run_on) launches everything queued so far as one kernel per 64 jobs on the stream `run_on` (any stream: the caller orders it
+ * behind the producers, e.g. morec_stream_wait_stream(run_on, stream)).  Jobs that add into the same destination run in queue order, and
+ * every job sums in the order of the in-place launch: the gradients are bit-identical to those of the same calls outside a scope.
+ * RULES: (1) a gradient written through a deferred job is DEFINED only after the flush that holds its job has run; (2) the partial rows live
+ * in a library-owned scratch that is rewound by morec_fold_defer_end: call it only where `stream` has been made to wait for every stream a
+ * flush ran on (or that stream is `stream` itself), and flush before it -- jobs still queued at the end are dropped.  (The workspace handed to
+ * morec_gemm_nt_colsum / morec_mlp_dact_recompute / morec_attn_bwd_dbias / morec_swin_attn_bwd_dbias is not used under a scope: a region of
+ * the library's scratch takes its place, so the caller may reuse its buffer at once, as outside a scope.)
+ * morec_fold_defer_begin opens nothing -- every call behaves as without it -- when the knob is 0, outside the deterministic mode, or while
+ * `stream` is being captured into a graph (a captured step keeps its folds in place); morec_fold_defer_active() tells (1 / 0).  One scope
+ * per process at a time (a second stream: MOREC_E_UNSUPPORTED).  The scratch grows by hipMalloc while the first scopes find their size and
+ * is merged into one buffer at the end of such a scope (a device synchronisation); afterwards a scope allocates nothing.
+ * morec_fold_stats: out4 = {device allocations made for the scratch so far, its size in bytes, jobs queued so far, flush launches so far}.
+ * No reference counterpart (torch.use_deterministic_algorithms has no such notion). */
+int morec_fold_defer_begin(void* stream);
+int morec_fold_defer_active(void);
+int morec_fold_flush(void* run_on);
+int morec_fold_defer_end(void);
+int morec_fold_stats(unsigned long long* out4);
 
 /* ------------------------------------------------------------------------------------------
  * GEMM  C[M,N] (+)= alpha * A[M,K] . B[N,K]^T  (both operands K-contiguous, "NT")
@@ -141,7 +168,7 @@ int morec_gemm_nt(const morec_gemm_desc* d, const void* A, const void* B, void* 
  * this is that layer's bias gradient (autograd of nn.Linear: db = dY.sum(0)) without a second pass over C.  The sums are
  * taken from the output tile while it is staged in LDS (the values as rounded to the output dtype), one partial row per
  * row block of the kernel's epilogue (32 ... 256 rows) into `workspace` (morec_gemm_colsum_workspace_bytes(M, N) bytes, fp32: sized for the
- * smallest block, 32 rows), folded by a second small launch.
+ * smallest block, 32 rows, over whole tiles of up to 256 rows), folded by a second small launch.
  * colsum_out == NULL: plain morec_gemm_nt.  MOREC_E_UNSUPPORTED unless dact != NONE, accumulate == 0, split_k <= 1 and
  * the output rows are 16-byte addressable. */
 size_t morec_gemm_colsum_workspace_bytes(int M, int N);
