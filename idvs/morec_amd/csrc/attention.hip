@@ -693,7 +693,7 @@ int check_desc(const morec_attn_desc* d) {
 // blocks appended behind the (sequence, head) grid: 16 spare rows each (morec_attn_desc.spare_rows_max)
 int attn_spare_blocks(const morec_attn_desc* d) { return (d->cu_seqlens && d->total_rows > 0) ? (d->spare_rows_max + 15) / 16 : 0; }
 
-// bf16 fast path on the matrix cores (attention_mfma.hip); MOREC_E_UNSUPPORTED = shape outside it
+// 16-bit path on the matrix cores (attention_mfma.hip: T <= 64, head width a multiple of 32); MOREC_E_UNSUPPORTED = shape outside it
 int morec_attn_mfma_launch(const morec_attn_desc* d, const void* qkv, const float* key_keep, void* ctx_or_dctx,
                            void* dqkv, bool backward, hipStream_t s, float* csum = nullptr);
 int colsum_f32_launch(const float* in, float* out, int rows, int N, hipStream_t s);
@@ -701,9 +701,9 @@ int colsum_f32_launch(const float* in, float* out, int rows, int N, hipStream_t 
 int morec_attn_f32mfma_launch(const morec_attn_desc* d, const void* qkv, const float* key_keep, void* ctx_or_dctx, void* dqkv, bool backward,
                               hipStream_t s);
 
-// A 16-bit problem outside the matrix-core path's shape rules (T <= 32, head width a multiple of 32) runs on the exact-fp32 VALU
+// A 16-bit problem outside the matrix-core path's shape rules (T <= 64, head width a multiple of 32) runs on the exact-fp32 VALU
 // kernels -- correct, several times slower.  Said ONCE per process on stderr (MOREC_QUIET=1 silences it) so that e.g. a run with
-// num_words_title > 32 does not lose the MFMA attention without a trace.
+// num_words_title > 64 does not lose the MFMA attention without a trace.
 static void warn_valu_fallback(const morec_attn_desc* d) {
     if (!is_h16(d->dtype)) return;
     static const bool once = [](const morec_attn_desc* q) {
@@ -715,23 +715,28 @@ static void warn_valu_fallback(const morec_attn_desc* d) {
     (void)once;
 }
 
+// The one place that picks the kernels of a checked call: 16-bit MFMA, else fp32 MFMA, else (with the warning above) the strip
+// kernels for T > 64 and the VALU tile kernels below that.
+template <bool BWD>
+static int attn_dispatch(const morec_attn_desc* d, const void* qkv, const float* key_keep, void* ctx_or_dctx, void* dqkv, hipStream_t s) {
+    int rc = morec_attn_mfma_launch(d, qkv, key_keep, ctx_or_dctx, dqkv, BWD, s);
+    if (rc != MOREC_E_UNSUPPORTED) return rc;
+    rc = morec_attn_f32mfma_launch(d, qkv, key_keep, ctx_or_dctx, dqkv, BWD, s);
+    if (rc != MOREC_E_UNSUPPORTED) return rc;
+    warn_valu_fallback(d);
+    AttnArgs a{qkv, key_keep, ctx_or_dctx, dqkv, d->n_seq, d->T, d->n_heads, d->dh, d->causal, d->scale, d->mask_value,
+               make_drop(d->p_drop, d->seed), d->cu_seqlens, d->total_rows};
+    dim3 grid(d->n_seq * d->n_heads + attn_spare_blocks(d));
+    if (d->T > Tile<8>::TP) return launch_long<BWD>(d, a, grid, s);
+    return launch_valu<BWD>(d, a, grid, s);
+}
+
 extern "C" int morec_attn_fwd(const morec_attn_desc* d, const void* qkv, const float* key_keep, void* ctx,
                               void* stream) {
     int rc = check_desc(d);
     if (rc) return rc;
     if (!qkv || !key_keep || !ctx) return MOREC_E_ARG;
-    AttnArgs a{qkv, key_keep, ctx, nullptr, d->n_seq, d->T, d->n_heads, d->dh, d->causal, d->scale, d->mask_value,
-               make_drop(d->p_drop, d->seed), d->cu_seqlens, d->total_rows};
-    dim3 grid(d->n_seq * d->n_heads + attn_spare_blocks(d)), block(64);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    rc = morec_attn_mfma_launch(d, qkv, key_keep, ctx, nullptr, false, s);
-    if (rc != MOREC_E_UNSUPPORTED) return rc;
-    rc = morec_attn_f32mfma_launch(d, qkv, key_keep, ctx, nullptr, false, s);
-    if (rc != MOREC_E_UNSUPPORTED) return rc;
-    warn_valu_fallback(d);
-    (void)block;
-    if (d->T > Tile<8>::TP) return launch_long<false>(d, a, grid, s);
-    return launch_valu<false>(d, a, grid, s);
+    return attn_dispatch<false>(d, qkv, key_keep, ctx, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int morec_attn_bwd(const morec_attn_desc* d, const void* qkv, const float* key_keep, const void* dctx,
@@ -739,18 +744,7 @@ extern "C" int morec_attn_bwd(const morec_attn_desc* d, const void* qkv, const f
     int rc = check_desc(d);
     if (rc) return rc;
     if (!qkv || !key_keep || !dctx || !dqkv) return MOREC_E_ARG;
-    AttnArgs a{qkv, key_keep, const_cast<void*>(dctx), dqkv, d->n_seq, d->T, d->n_heads, d->dh, d->causal, d->scale,
-               d->mask_value, make_drop(d->p_drop, d->seed), d->cu_seqlens, d->total_rows};
-    dim3 grid(d->n_seq * d->n_heads + attn_spare_blocks(d)), block(64);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    rc = morec_attn_mfma_launch(d, qkv, key_keep, const_cast<void*>(dctx), dqkv, true, s);
-    if (rc != MOREC_E_UNSUPPORTED) return rc;
-    rc = morec_attn_f32mfma_launch(d, qkv, key_keep, const_cast<void*>(dctx), dqkv, true, s);
-    if (rc != MOREC_E_UNSUPPORTED) return rc;
-    warn_valu_fallback(d);
-    (void)block;
-    if (d->T > Tile<8>::TP) return launch_long<true>(d, a, grid, s);
-    return launch_valu<true>(d, a, grid, s);
+    return attn_dispatch<true>(d, qkv, key_keep, const_cast<void*>(dctx), dqkv, reinterpret_cast<hipStream_t>(stream));
 }
 
 // morec_attn_bwd + the bias gradient of the fused q|k|v projection: dbias[3 H] += column sums of the dqkv rows (MFMA path: fp32

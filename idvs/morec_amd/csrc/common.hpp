@@ -225,6 +225,14 @@ __device__ __forceinline__ float rows4_max(float v) {
     permlane32_swap(a, b);
     return fmaxf(a, b);
 }
+// sum over the 16 lanes of a DPP row (every lane ends up with the total): quad butterflies, then the two mirrors
+__device__ __forceinline__ float row16_sum(float v) {
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));    // quad_perm [1,0,3,2]
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, true));    // quad_perm [2,3,0,1]
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, true));   // row_half_mirror
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xf, 0xf, true));   // row_mirror
+    return v;
+}
 
 // erf GELU (HF "gelu" / nn.GELU: 0.5 x (1 + erf(x / sqrt 2))) and its derivative.
 // erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, i.e. at the fp32 rounding level of the result): one v_rcp, one

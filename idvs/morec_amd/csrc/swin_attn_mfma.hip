@@ -349,15 +349,6 @@ __device__ __forceinline__ uint4 pack_part(const f32x4_t (&p)[4][NTI], int t, in
 
 // The 16 operand rows (q, k, v, dO: 16 bytes each per lane and 16-token block) of one (window, head).  Unguarded loads: padded
 // tokens re-read token 0's rows (see the forward kernel).
-// sum over the 16 lanes of a DPP row (every lane ends up with the total): quad butterflies, then the two mirrors
-__device__ __forceinline__ float row16_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));    // quad_perm [1,0,3,2]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, true));    // quad_perm [2,3,0,1]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, true));   // row_half_mirror
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xf, 0xf, true));   // row_mirror
-    return v;
-}
-
 struct BwdFrags { uint4 q[4], k[4], v[4], o[4]; };
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 __device__ __forceinline__ uint4 as_uint4(u32x4_t v) { return make_uint4(v[0], v[1], v[2], v[3]); }

@@ -1,4 +1,4 @@
-"""Attention at T = 50 (abstracts / bodies): attention_mfma64.hip vs the VALU fallback (MOREC_ATTN_MFMA64=0 in a second process), BERT-base heads."""
+"""Attention at T = 50 (abstracts / bodies): attention_mfma.hip's 64-row kernels vs the VALU fallback (MOREC_ATTN_MFMA64=0 in a second process), BERT-base heads."""
 import math
 import os
 import sys

@@ -69,7 +69,7 @@ echo "# python scripts/tmr_bench.py  -- per launch: <gemm8p_tmr mode>:<time>/<TF
 python $R/scripts/tmr_bench.py
 } > $O/${TAG}_tile_height.txt 2>&1
 {
-echo "# python scripts/attn64_bench.py (T = 50, 2688 titles, 12 heads x 64, fp16, dropout 0.1): attention_mfma64.hip, then MOREC_ATTN_MFMA64=0 (exact-fp32 VALU kernels)"
+echo "# python scripts/attn64_bench.py (T = 50, 2688 titles, 12 heads x 64, fp16, dropout 0.1): attention_mfma.hip's 64-row kernels, then MOREC_ATTN_MFMA64=0 (exact-fp32 VALU kernels)"
 python $R/scripts/attn64_bench.py
 MOREC_ATTN_MFMA64=0 python $R/scripts/attn64_bench.py
 } > $O/${TAG}_attn64.txt 2>&1
