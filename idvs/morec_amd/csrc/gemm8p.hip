@@ -1,7 +1,9 @@
 // gemm8p.hip -- the encoder GEMMs' main loop: 256 x 256 output tile, K advanced 64 elements per K-tile, eight waves as
-// 2 (m) x 4 (n), 128 x 64 outputs per wave on v_mfma_f32_32x32x16_bf16, a K-tile split in FOUR phases
+// 2 (m) x 4 (n), 128 x 64 outputs per wave on v_mfma_f32_16x16x32 (default) or v_mfma_f32_32x32x16 (template parameter MF, knob "gemm8p_mfma":
+// same tiles, LDS image, DMA, barriers and epilogue staging; 3 - 7 % faster per launch on the 16-row shape under the chip's power limit,
+// profiles/mfma_shape_launches.txt), a K-tile split in FOUR phases
 //      { ds_read a register sub-tile | issue one 16-KiB LDS-DMA half-tile | counted vmcnt }  s_barrier
-//      { 8 MFMA 32x32x16 = one 64 x 32 quadrant of the wave tile over the whole K-tile }     s_barrier
+//      { 16 MFMA 16x16x32 / 8 MFMA 32x32x16 = one 64 x 32 quadrant of the wave tile over the whole K-tile }     s_barrier
 // with the two wave rows running ONE BARRIER APART: while waves 0-3 (one per SIMD) are in their MFMA segment, waves 4-7 (their
 // SIMD partners) are in their read / DMA segment and vice versa, so every SIMD's matrix pipe always has a wave feeding it and
 // the LDS / DMA issue of one wave is covered by its partner's MFMAs.  The DMA queue is never drained inside the loop: every
@@ -15,6 +17,8 @@
 // 16-byte slot s of row r holds logical slot s ^ ((r >> 1) & 7): with 32-row MFMA fragments (lane -> row lane & 31) the 16
 // lanes of every ds_read_b128 service group then cover all 64 banks exactly once.  The LDS-DMA writes lane-linearly, so the
 // permutation is applied to the per-lane SOURCE address and again to the read address (an involution; destination linear).
+// With 16-row fragments (lane -> row lane & 15, slot 4 ks + (lane >> 4)) the 16 rows of a service group take 8 physical slots x 2 row parities:
+// again all 64 banks once by this addressing (the counter shows no MORE conflicts than the 32-row shape: profiles/mfma_shape_step.txt).
 //
 // Half-tiles are cut by CONSUMPTION ORDER, not by wave: "A-first" = rows every wave reads in phase 0 (its first 64 of 128),
 // "A-second" = the rows read in phase 2, "B-first" / "B-second" = the first / second 32 of every wave's 64 columns (read in
@@ -35,7 +39,8 @@ using namespace g8;
 // the next tile is issued BEFORE the epilogue of the finished one, so the first fill of the pipeline (7.4 k cycles when it
 // was exposed: profiles/r02_gemm8p_stamps.txt), the workgroup turnover and most of the store drain overlap the epilogue.
 //
-// Epilogue: wave-private.  acc[Mi][Ni][4 g + r] = C[m0 + wr*128 + Mi*32 + (lane & 31)][n0 + wc*64 + Ni*32 + 8 g + 4 (lane >> 5) + r].
+// Epilogue: wave-private.  acc[Mi][Ni][4 g + r] = C[m0 + wr*128 + Mi*32 + (lane & 31)][n0 + wc*64 + Ni*32 + 8 g + 4 (lane >> 5) + r]  (MF = 32;
+// MF = 16: acc[Mi][Ni][4 (2 mi2 + ni2) + r] = C[... + Mi*32 + 16 mi2 + (lane & 15)][... + Ni*32 + 16 ni2 + 4 (lane >> 4) + r], struct Grp below).
 // Every 32-row block goes through the wave's own 4-KiB LDS slice ([32 rows][128 B], 16-byte slots XOR-swizzled with row & 7;
 // above the K-tile buffers) so that all global traffic (the stores, and the loads of the activation-derivative operand) is
 // 16-byte lanes along rows: full 128-byte lines per row per instruction.  128 B = 64 bf16 columns (one pass per block) or
@@ -64,8 +69,21 @@ struct TileXY {
     int krem;      // elements of K inside the unit's last K-tile (64 unless the unit ends at a K that is not a multiple of 64)
 };
 
+// Accumulator group q (four consecutive columns of one row per lane) of pass ps of a 32-row block, per MFMA shape MF and output element size ES:
+//   MF = 32: row lane & 31, columns 8 g + 4 (lane >> 5) .. + 3 of 32-column block ni; registers 4 g .. 4 g + 3 of acc[Mi][ni]; g = q % 4 (ES = 2) / q
+//   MF = 16: row 16 half + (lane & 15), columns 16 ni2 + 4 (lane >> 4) .. + 3 of block ni; registers 4 (2 half + ni2) .. + 3; q = 4 half + 2 ni + ni2
+//            (ES = 2) / 2 half + ni2 (ES = 4, ni = ps)
+template <int MF, int ES>
+struct Grp {
+    static constexpr int ni(int q, int ps) { return ES == 2 ? (MF == 32 ? q / 4 : (q & 3) >> 1) : ps; }
+    static constexpr int e0(int q) { return MF == 32 ? 4 * (ES == 2 ? q % 4 : q) : 4 * (ES == 2 ? 2 * (q >> 2) + (q & 1) : q); }
+    static constexpr int bi(int q) { return MF == 32 ? (ES == 2 ? q % 4 : q) : (q & 1); }       // bias vector bv[ni][bi]
+    static constexpr int half(int q) { return MF == 32 ? 0 : (ES == 2 ? q >> 2 : q >> 1); }
+};
+
 // TMR: rows of a tile -- 256, or 224 / 192 (wave row 1 owns three / two 32-row blocks instead of four): "tile height" in gemm_plan.hpp (pick_tmr).
-template <typename TI, typename TO, int ACT, bool CS, int TMR = 256>
+// MF: MFMA shape of the main loop (gemm8p_core.hpp mfma_quadrant); the epilogue differs only in which accumulator registers hold which outputs (Grp, cell)
+template <typename TI, typename TO, int ACT, bool CS, int TMR = 256, int MF = 32>
 __device__ __forceinline__ void tile_body(const GemmArgs& p, char* smem, const bf16* __restrict__ Acur, const bf16* __restrict__ Bcur,
                                           const bf16* __restrict__ Anext, const bf16* __restrict__ Bnext, const TileXY cur, const TileXY nxt,
                                           const bool first) {
@@ -77,6 +95,7 @@ __device__ __forceinline__ void tile_body(const GemmArgs& p, char* smem, const b
     constexpr int PC = 128 / ES;                 // columns per pass: 64 (bf16) / 32 (f32)
     constexpr int NPASS = 64 / PC;               // passes per 32-row block: 1 / 2
     constexpr int NG = PC / 8;                   // 4-element accumulator groups of this lane per pass: 8 / 4
+    using G = Grp<MF, ES>;
     struct Vecs { u32x4_t q[4]; };
     const int m0 = cur.m0, n0 = cur.n0;
     G8_STAMPW(0, cur.wg);
@@ -90,7 +109,7 @@ __device__ __forceinline__ void tile_body(const GemmArgs& p, char* smem, const b
             bias_l = bp[min(n0 + ((tid_m >> 6) & 3) * 64 + (tid_m & 63), p.N - 1)];
         }
         Ctx c;
-        make_ctx(c, tid_m, Acur, Bcur, min(p.M - m0, tmr), p.N - n0, p.lda, p.ldb, cur.krem);
+        make_ctx<MF>(c, tid_m, Acur, Bcur, min(p.M - m0, tmr), p.N - n0, p.lda, p.ldb, cur.krem);
         if (first) issue_prologue(c, smem, cur.nkt);      // later tiles: issued by the previous tile's body, ahead of its epilogue
         // global stores of the previous tile's epilogue (issued behind this tile's prologue): 4 per pass and output
         constexpr int NST = 16 * (int)sizeof(TO) / 2;
@@ -98,11 +117,11 @@ __device__ __forceinline__ void tile_body(const GemmArgs& p, char* smem, const b
         const int wr_m = __builtin_amdgcn_readfirstlane(tid_m >> 8);
         unsigned long long* st_m = p.stamps ? p.stamps + (size_t)cur.wg * 16 : nullptr;
         if constexpr (!PART) {
-            mainloop8p<TI>(c, wr_m, cur.nkt, younger, smem, acc, st_m);
+            mainloop8p<TI, 0, MF>(c, wr_m, cur.nkt, younger, smem, acc, st_m);
         } else {      // ONE branch, outside the loop: wave row 0 runs the full wave tile, wave row 1 the instantiation without its absent blocks
             (void)younger;
-            if (wr_m == 0) mainloop8p_s<TI, 0, 0, 4>(c, 0, cur.nkt, smem, acc, st_m);
-            else mainloop8p_s<TI, 0, 0, nb1>(c, 1, cur.nkt, smem, acc, st_m);
+            if (wr_m == 0) mainloop8p_s<TI, 0, 0, 4, MF>(c, 0, cur.nkt, smem, acc, st_m);
+            else mainloop8p_s<TI, 0, 0, nb1, MF>(c, 1, cur.nkt, smem, acc, st_m);
         }
     }
     G8_STAMPW(1, cur.wg);
@@ -162,7 +181,8 @@ __device__ __forceinline__ void tile_body(const GemmArgs& p, char* smem, const b
     // here (a dozen integer ops) instead of being kept alive -- i.e. spilled -- across the main loop.
     int tid_e = threadIdx.x;
     asm volatile("" : "+v"(tid_e));
-    const int lane = tid_e & 63, r5 = lane & 31, h = lane >> 5;
+    // r5 = this lane's row of a 32-row block (MF = 16: of its first 16-row half), h = which run of four columns of every group of 8 (MF = 16: 16)
+    const int lane = tid_e & 63, r5 = MF == 32 ? lane & 31 : lane & 15, h = MF == 32 ? lane >> 5 : lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid_e >> 6);
     const int wr = wave >> 2, wc = wave & 3;
     char* ws = smem + LDS_BYTES + wave * SLICE;
@@ -179,8 +199,13 @@ __device__ __forceinline__ void tile_body(const GemmArgs& p, char* smem, const b
     const int rs_off = rs_row * 128 + ((rs_slot ^ (rs_row & 7)) << 4);    // + i * 1024 (row + 8 keeps row & 7)
     // accumulator side: group q of a pass = columns 8 q + 4 h .. + 3 of the pass (bf16: 8 bytes, slot q; f32: 16 bytes, slot 2 q + h)
     auto cell = [&](int q) {
-        const int slot = ES == 2 ? q : 2 * q + h;
-        return reinterpret_cast<TO*>(ws + r5 * 128 + ((slot ^ (r5 & 7)) << 4) + (ES == 2 ? 8 * h : 0));
+        if constexpr (MF == 32) {
+            const int slot = ES == 2 ? q : 2 * q + h;
+            return reinterpret_cast<TO*>(ws + r5 * 128 + ((slot ^ (r5 & 7)) << 4) + (ES == 2 ? 8 * h : 0));
+        } else {      // 8-byte cells (bf16): slot 2 (q & 3) + (h >> 1), half h & 1; 16-byte cells (f32): slot 4 (q & 1) + h.  Rows r and r + 8 share a bank group (two-way by the addressing; not measured separately)
+            const int slot = ES == 2 ? 2 * (q & 3) + (h >> 1) : 4 * (q & 1) + h;
+            return reinterpret_cast<TO*>(ws + (16 * G::half(q) + r5) * 128 + ((slot ^ (r5 & 7)) << 4) + (ES == 2 ? 8 * (h & 1) : 0));
+        }
     };
     const int cur_tm = m0 / tmr;
     const int mw = m0 + wr * 128, nw = n0 + wc * 64;
@@ -246,7 +271,9 @@ __device__ __forceinline__ void tile_body(const GemmArgs& p, char* smem, const b
 #pragma unroll
         for (int Ni = 0; Ni < 2; ++Ni)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) bv[Ni][g] = *reinterpret_cast<const float4*>(ws + (Ni * 32 + g * 8 + 4 * h) * 4);
+            for (int g = 0; g < 4; ++g)      // MF = 16: two vectors per 32-column block (columns 16 g + 4 h .. + 3)
+                bv[Ni][g] = (MF == 32 || g < 2) ? *reinterpret_cast<const float4*>(ws + (Ni * 32 + g * (MF == 32 ? 8 : 16) + 4 * h) * 4)
+                                                : make_float4(0.f, 0.f, 0.f, 0.f);
         wfence();
     } else {
 #pragma unroll
@@ -271,7 +298,7 @@ __device__ __forceinline__ void tile_body(const GemmArgs& p, char* smem, const b
         int tid_n = threadIdx.x;
         asm volatile("" : "+v"(tid_n));
         Ctx cn;
-        make_ctx(cn, tid_n, Anext, Bnext, min(p.M - nxt.m0, tmr), p.N - nxt.n0, p.lda, p.ldb, nxt.krem);
+        make_ctx<MF>(cn, tid_n, Anext, Bnext, min(p.M - nxt.m0, tmr), p.N - nxt.n0, p.lda, p.ldb, nxt.krem);
         issue_prologue(cn, smem, nxt.nkt);
     }
     if (p.debug & 2) {      // ablation: no epilogue (the store keeps the accumulators alive)
@@ -285,7 +312,7 @@ __device__ __forceinline__ void tile_body(const GemmArgs& p, char* smem, const b
         if constexpr (PART) {
             if (Mi >= nblk) break;      // (wave-uniform) blocks past the tile's rows: never computed
         }
-        [[maybe_unused]] const bool row_ok = (mw + Mi * 32 + r5) < m_end;
+        [[maybe_unused]] const bool row_ok[2] = {(mw + Mi * 32 + r5) < m_end, (mw + Mi * 32 + 16 + r5) < m_end};      // per 16-row half (MF = 32: [0])
 #pragma unroll
         for (int ps = 0; ps < NPASS; ++ps) {
             pin();      // nothing of this pass may be computed ahead of the previous one (128 fresh values on top of the accumulators)
@@ -304,13 +331,13 @@ __device__ __forceinline__ void tile_body(const GemmArgs& p, char* smem, const b
                     uint2 park[NG];
 #pragma unroll
                     for (int q = 0; q < NG; ++q) {
-                        const int Ni = q / 4, g = q % 4;
-                        const float4 b = bv[Ni][g];
+                        const int Ni = G::ni(q, ps), e0 = G::e0(q);
+                        const float4 b = bv[Ni][G::bi(q)];
                         float v[4], d[4];
-                        v[0] = fmaf(acc[Mi][Ni][4 * g + 0], p.alpha, b.x);
-                        v[1] = fmaf(acc[Mi][Ni][4 * g + 1], p.alpha, b.y);
-                        v[2] = fmaf(acc[Mi][Ni][4 * g + 2], p.alpha, b.z);
-                        v[3] = fmaf(acc[Mi][Ni][4 * g + 3], p.alpha, b.w);
+                        v[0] = fmaf(acc[Mi][Ni][e0 + 0], p.alpha, b.x);
+                        v[1] = fmaf(acc[Mi][Ni][e0 + 1], p.alpha, b.y);
+                        v[2] = fmaf(acc[Mi][Ni][e0 + 2], p.alpha, b.z);
+                        v[3] = fmaf(acc[Mi][Ni][e0 + 3], p.alpha, b.w);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) d[r] = v[r];
                         if (p.aux_deriv) {
@@ -344,13 +371,13 @@ __device__ __forceinline__ void tile_body(const GemmArgs& p, char* smem, const b
                 } else {
 #pragma unroll
                     for (int q = 0; q < NG; ++q) {
-                        const int Ni = ES == 2 ? q / 4 : ps, g = ES == 2 ? q % 4 : q;
-                        const float4 b = bv[Ni][g];
+                        const int Ni = G::ni(q, ps), e0 = G::e0(q);
+                        const float4 b = bv[Ni][G::bi(q)];
                         float pre[4];
-                        pre[0] = fmaf(acc[Mi][Ni][4 * g + 0], p.alpha, b.x);
-                        pre[1] = fmaf(acc[Mi][Ni][4 * g + 1], p.alpha, b.y);
-                        pre[2] = fmaf(acc[Mi][Ni][4 * g + 2], p.alpha, b.z);
-                        pre[3] = fmaf(acc[Mi][Ni][4 * g + 3], p.alpha, b.w);
+                        pre[0] = fmaf(acc[Mi][Ni][e0 + 0], p.alpha, b.x);
+                        pre[1] = fmaf(acc[Mi][Ni][e0 + 1], p.alpha, b.y);
+                        pre[2] = fmaf(acc[Mi][Ni][e0 + 2], p.alpha, b.z);
+                        pre[3] = fmaf(acc[Mi][Ni][e0 + 3], p.alpha, b.w);
                         io<TO>::store4(cell(q), pre);
                         if (q & 1) pin();
                     }
@@ -376,13 +403,13 @@ __device__ __forceinline__ void tile_body(const GemmArgs& p, char* smem, const b
             }
 #pragma unroll
             for (int q = 0; q < NG; ++q) {
-                const int Ni = ES == 2 ? q / 4 : ps, g = ES == 2 ? q % 4 : q;
-                const float4 b = bv[Ni][g];
+                const int Ni = G::ni(q, ps), e0 = G::e0(q);
+                const float4 b = bv[Ni][G::bi(q)];
                 float v[4];
-                v[0] = fmaf(acc[Mi][Ni][4 * g + 0], p.alpha, b.x);
-                v[1] = fmaf(acc[Mi][Ni][4 * g + 1], p.alpha, b.y);
-                v[2] = fmaf(acc[Mi][Ni][4 * g + 2], p.alpha, b.z);
-                v[3] = fmaf(acc[Mi][Ni][4 * g + 3], p.alpha, b.w);
+                v[0] = fmaf(acc[Mi][Ni][e0 + 0], p.alpha, b.x);
+                v[1] = fmaf(acc[Mi][Ni][e0 + 1], p.alpha, b.y);
+                v[2] = fmaf(acc[Mi][Ni][e0 + 2], p.alpha, b.z);
+                v[3] = fmaf(acc[Mi][Ni][e0 + 3], p.alpha, b.w);
                 if constexpr (ACT == 1) {
                     gelu4(v);
                 } else if constexpr (ACT == 2) {
@@ -409,7 +436,7 @@ __device__ __forceinline__ void tile_body(const GemmArgs& p, char* smem, const b
                 }
                 if constexpr (CS) {     // rows past M hold copies of row M - 1 (clamped loads): keep them out of the column sums
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = row_ok ? v[r] : 0.f;
+                    for (int r = 0; r < 4; ++r) v[r] = row_ok[G::half(q)] ? v[r] : 0.f;
                 }
                 io<TO>::store4(cell(q), v);
                 if (ACT != 5 && (q & 1)) pin();
@@ -461,7 +488,7 @@ __device__ __forceinline__ void tile_body(const GemmArgs& p, char* smem, const b
     }
 }
 
-template <typename TI, typename TO, int ACT, bool CS, int TMR = 256>
+template <typename TI, typename TO, int ACT, bool CS, int TMR = 256, int MF = 32>
 __global__ __launch_bounds__(THREADS) void gemm8p_kernel(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int nwg = p.tiles_m * p.tiles_n;
@@ -522,7 +549,7 @@ __global__ __launch_bounds__(THREADS) void gemm8p_kernel(GemmArgs p) {
     for (int i = 0; i < n_units; ++i) {
         const bool more = i + 1 < n_units;
         const TileXY nxt = more ? unit_at(i + 1) : cur;
-        tile_body<TI, TO, ACT, CS, TMR>(p, smem, A + (size_t)cur.m0 * p.lda + cur.k0 * KE, B + (size_t)cur.n0 * p.ldb + cur.k0 * KE,
+        tile_body<TI, TO, ACT, CS, TMR, MF>(p, smem, A + (size_t)cur.m0 * p.lda + cur.k0 * KE, B + (size_t)cur.n0 * p.ldb + cur.k0 * KE,
                                A + (size_t)nxt.m0 * p.lda + nxt.k0 * KE, B + (size_t)nxt.n0 * p.ldb + nxt.k0 * KE, cur, nxt, i == 0);
         cur = nxt;
     }
@@ -556,12 +583,12 @@ static void tail_workspace(hipStream_t s, int n_cu, GemmArgs& a) {
 static_assert(TM == gplan::P8_TM && TN == gplan::P8_TN && KE == gplan::P8_KE, "gemm_plan.hpp");
 
 // (tile height, tile order and tail split are chosen in gemm_plan.hpp: pick_tmr, rule 4)
-template <typename TI, typename TO, int ACT, bool CS, int TMR = 256>
+template <typename TI, typename TO, int ACT, bool CS, int TMR = 256, int MF = 32>
 int launch8p(const GemmPlan& p, GemmArgs& a, hipStream_t s) {
     a.tmr = TMR;
     a.tiles_m = (a.M + TMR - 1) / TMR;
     a.tiles_n = (a.N + TN - 1) / TN;
-    static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8p_kernel<TI, TO, ACT, CS, TMR>),
+    static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8p_kernel<TI, TO, ACT, CS, TMR, MF>),
                                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);      // thread-safe one-time set-up
     (void)attr_rc;
     // the persistent grid: gemm8p_cu_count() workgroups.  morec_tuning_set("gemm8p_reserve_cus", r) leaves r CUs (rounded to a multiple
@@ -573,38 +600,38 @@ int launch8p(const GemmPlan& p, GemmArgs& a, hipStream_t s) {
     a.tail_ws = nullptr;
     a.tail_cnt = nullptr;
     if (p.tail_split) tail_workspace(s, n_cu, a);
-    hipLaunchKernelGGL((gemm8p_kernel<TI, TO, ACT, CS, TMR>), dim3(nwg < n_cu ? nwg : n_cu), dim3(THREADS), LDS_TOTAL, s, a);
+    hipLaunchKernelGGL((gemm8p_kernel<TI, TO, ACT, CS, TMR, MF>), dim3(nwg < n_cu ? nwg : n_cu), dim3(THREADS), LDS_TOTAL, s, a);
     MOREC_CHECK_LAUNCH();
     if constexpr (CS) return colsum_f32_launch(a.colsum, a.colsum_dst, a.tiles_m * 2, a.N, s);
     return MOREC_OK;
 }
 
-template <typename TI>
+template <typename TI, int MF>
 int dispatch8p(const GemmPlan& p, GemmArgs& a, hipStream_t s) {
     const int mode = p.mode;
     if (p.tile_rows == 224) {
-        if (mode == 0) return launch8p<TI, TI, 0, false, 224>(p, a, s);
-        if (mode == 1) return launch8p<TI, TI, 1, false, 224>(p, a, s);
-        return launch8p<TI, TI, 5, true, 224>(p, a, s);
+        if (mode == 0) return launch8p<TI, TI, 0, false, 224, MF>(p, a, s);
+        if (mode == 1) return launch8p<TI, TI, 1, false, 224, MF>(p, a, s);
+        return launch8p<TI, TI, 5, true, 224, MF>(p, a, s);
     }
     if (p.tile_rows == 192) {
-        if (mode == 0) return launch8p<TI, TI, 0, false, 192>(p, a, s);
-        if (mode == 1) return launch8p<TI, TI, 1, false, 192>(p, a, s);
-        return launch8p<TI, TI, 5, true, 192>(p, a, s);
+        if (mode == 0) return launch8p<TI, TI, 0, false, 192, MF>(p, a, s);
+        if (mode == 1) return launch8p<TI, TI, 1, false, 192, MF>(p, a, s);
+        return launch8p<TI, TI, 5, true, 192, MF>(p, a, s);
     }
-    if (p.out_dtype == MOREC_F32) return launch8p<TI, float, 0, false>(p, a, s);
+    if (p.out_dtype == MOREC_F32) return launch8p<TI, float, 0, false, 256, MF>(p, a, s);
     if (p.colsum) {
-        if (mode == 3) return launch8p<TI, TI, 3, true>(p, a, s);
-        if (mode == 4) return launch8p<TI, TI, 4, true>(p, a, s);
-        return launch8p<TI, TI, 5, true>(p, a, s);
+        if (mode == 3) return launch8p<TI, TI, 3, true, 256, MF>(p, a, s);
+        if (mode == 4) return launch8p<TI, TI, 4, true, 256, MF>(p, a, s);
+        return launch8p<TI, TI, 5, true, 256, MF>(p, a, s);
     }
     switch (mode) {
-        case 1: return launch8p<TI, TI, 1, false>(p, a, s);
-        case 2: return launch8p<TI, TI, 2, false>(p, a, s);
-        case 3: return launch8p<TI, TI, 3, false>(p, a, s);
-        case 4: return launch8p<TI, TI, 4, false>(p, a, s);
-        case 5: return launch8p<TI, TI, 5, false>(p, a, s);
-        default: return launch8p<TI, TI, 0, false>(p, a, s);
+        case 1: return launch8p<TI, TI, 1, false, 256, MF>(p, a, s);
+        case 2: return launch8p<TI, TI, 2, false, 256, MF>(p, a, s);
+        case 3: return launch8p<TI, TI, 3, false, 256, MF>(p, a, s);
+        case 4: return launch8p<TI, TI, 4, false, 256, MF>(p, a, s);
+        case 5: return launch8p<TI, TI, 5, false, 256, MF>(p, a, s);
+        default: return launch8p<TI, TI, 0, false, 256, MF>(p, a, s);
     }
 }
 }  // namespace
@@ -615,5 +642,6 @@ int gemm8p_launch(const GemmPlan& p, GemmArgs& a, hipStream_t s) {
     a.tail_bias = t.gemm8p_tail_bias;
     a.tail_split = t.gemm8p_tail_split;
     a.stamps = reinterpret_cast<unsigned long long*>(t.gemm8p_stamps());
-    return p.in_dtype == MOREC_F16 ? dispatch8p<f16>(p, a, s) : dispatch8p<bf16>(p, a, s);
+    if (p.mfma == 16) return p.in_dtype == MOREC_F16 ? dispatch8p<f16, 16>(p, a, s) : dispatch8p<bf16, 16>(p, a, s);
+    return p.in_dtype == MOREC_F16 ? dispatch8p<f16, 32>(p, a, s) : dispatch8p<bf16, 32>(p, a, s);
 }

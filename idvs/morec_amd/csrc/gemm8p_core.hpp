@@ -51,7 +51,8 @@ struct Ctx {
     uint32_t a1[2], a2[2], b1[2], b2[2];         // per-lane byte offsets of the wave's two pieces of each half-tile
     int dA1, dA2, dB1, dB2;                      // wave-uniform LDS offsets (within a buffer) of those pieces
     int aoff, boff;                              // LDS offsets (within a buffer) of the wave's first A row / first B row
-    int loff[4];                                 // per-lane fragment offset of MFMA k-step ks: row (lane & 31), swizzled slot
+    int loff[4];                                 // per-lane fragment offsets.  MF = 32: k-step ks, row (lane & 31), swizzled slot 2 ks + (lane >> 5);
+                                                 // MF = 16: entry 2 sb + ks, row 16 sb + (lane & 15), swizzled slot 4 ks + (lane >> 4)
     uint32_t pz[2];                              // 0x80000000 where this lane's slot of piece j lies past K in the LAST K-tile, else 0
 };
 
@@ -63,13 +64,36 @@ __device__ __forceinline__ uint4 lds16(const char* p) { return *reinterpret_cast
 // height").  Compile time: a run-time branch around MFMAs makes the accumulators loop-carried through phi nodes and hipcc spills ~150 of
 // them (measured: 576-704 bytes of scratch per lane, launches 7x slower); the caller branches ONCE, outside the main loop, between two
 // instantiations.  Barriers, DMA and the fragment reads are those of the full tile; the accumulators of absent blocks are never read.
-template <typename T16, int M0, int NQ, bool ZERO, int NBW = 4>
+// MF = MFMA shape: 32 = eight v_mfma_f32_32x32x16 per quadrant (four k-steps of 16), 16 = sixteen v_mfma_f32_16x16x32 (two k-steps of 32 over
+// 2 x 2 blocks of 16 x 16 inside every 32 x 32 block; the block's sixteen accumulator registers are four f32x4, entry 2 mi2 + ni2).  The same
+// twelve 16-byte fragments per quadrant either way (Ctx::loff); fa[mi][2 mi2 + ks], fb[2 ni2 + ks] for MF = 16.  The 16-row shape takes the
+// K-tile's 64 products in two instructions of 32 where the 32-row one takes four of 16: the instruction set does not promise the same rounding, but
+// on MI355X every output measured bit-identical between the two (profiles/mfma_shape_step.txt).
+template <typename T16, int M0, int NQ, bool ZERO, int NBW = 4, int MF = 32>
 __device__ __forceinline__ void mfma_quadrant(f32x16_t (&acc)[4][2], const uint4 (&fa)[2][4], const uint4 (&fb)[4]) {
+    static_assert(MF == 32 || MF == 16, "MFMA shape");
     if constexpr (M0 >= NBW) return;
     constexpr int NMI = (M0 + 1 < NBW) ? 2 : 1;
 #ifndef G8_NO_SETPRIO      // (experiment builds only: scripts/shadow_build.sh)
     __builtin_amdgcn_s_setprio(1);
 #endif
+    if constexpr (MF == 16) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int mi = 0; mi < NMI; ++mi)
+#pragma unroll
+                for (int sb = 0; sb < 4; ++sb) {      // sb = 2 mi2 + ni2; operand-swapped like the 32-row form: ONE m (lane & 15), four consecutive n
+                    f32x16_t& blk = acc[M0 + mi][NQ];
+                    f32x4_t cin;
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) cin[v] = (ZERO && ks == 0) ? 0.f : blk[4 * sb + v];
+                    const f32x4_t d = h16<T16>::mma16(__builtin_bit_cast(bf16x8_t, fb[2 * (sb & 1) + ks]),
+                                                      __builtin_bit_cast(bf16x8_t, fa[mi][2 * (sb >> 1) + ks]), cin);
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) blk[4 * sb + v] = d[v];
+                }
+    } else {
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
@@ -83,6 +107,7 @@ __device__ __forceinline__ void mfma_quadrant(f32x16_t (&acc)[4][2], const uint4
             }
             acc[M0 + mi][NQ] = h16<T16>::mma32(__builtin_bit_cast(bf16x8_t, fb[ks]), __builtin_bit_cast(bf16x8_t, fa[mi][ks]), cin);
         }
+    }
 #ifndef G8_NO_SETPRIO
     __builtin_amdgcn_s_setprio(0);
 #endif
@@ -127,7 +152,7 @@ __device__ __forceinline__ void vm_wait_tail() {
 // One K-tile out of the buffer at byte offset `cb` (0 or BUF_BYTES); kb = byte offset of this K-tile within a row.
 // last2 (REM == 2 only): K-tile t + 2, refilled in phases 2 / 3, is the last one of K.
 // BAUX: cache policy of the B-panel loads (see dma2)
-template <typename T16, int REM, int SLACK = 0, bool ZERO = false, int BAUX = 0, int NBW = 4>
+template <typename T16, int REM, int SLACK = 0, bool ZERO = false, int BAUX = 0, int NBW = 4, int MF = 32>
 __device__ __forceinline__ void ktile(char* smem, const Ctx& c, int cb, int kb, f32x16_t (&acc)[4][2], bool last2 G8_GS_PARAM) {
     const uint32_t m1 = REM == 1 ? 0xffffffffu : 0u;           // K-tile t + 1 is the last one exactly when REM == 1
     const uint32_t m2 = last2 ? 0xffffffffu : 0u;
@@ -153,7 +178,7 @@ __device__ __forceinline__ void ktile(char* smem, const Ctx& c, int cb, int kb, 
     pin();
     vm_wait_tail<REM, 8, 2, SLACK>();
     bar();
-    mfma_quadrant<T16, 0, 0, ZERO, NBW>(acc, fa, fb0);
+    mfma_quadrant<T16, 0, 0, ZERO, NBW, MF>(acc, fa, fb0);
     bar();
     // ---- phase 1: B-second fragments; refill A-second of t+1
 #pragma unroll
@@ -163,7 +188,7 @@ __device__ __forceinline__ void ktile(char* smem, const Ctx& c, int cb, int kb, 
     pin();
     vm_wait_tail<REM, 8, 0, SLACK>();
     bar();
-    mfma_quadrant<T16, 0, 1, ZERO, NBW>(acc, fa, fb1);
+    mfma_quadrant<T16, 0, 1, ZERO, NBW, MF>(acc, fa, fb1);
     bar();
     // ---- phase 2: A-second fragments; refill A-first of t+2 (this buffer)
 #pragma unroll
@@ -175,7 +200,7 @@ __device__ __forceinline__ void ktile(char* smem, const Ctx& c, int cb, int kb, 
     pin();
     vm_wait_tail<REM, 6, 0, SLACK>();
     bar();
-    mfma_quadrant<T16, 2, 1, ZERO, NBW>(acc, fa, fb1);
+    mfma_quadrant<T16, 2, 1, ZERO, NBW, MF>(acc, fa, fb1);
     bar();
     // ---- phase 3: nothing to read (B-first is still in registers); refill B-first of t+2
     if constexpr (REM >= 2) dma2z<BAUX>(c.rb, c.b1[0], c.b1[1], c.pz, m2, kb + 2 * KB, cur + OP_BYTES + c.dB1);
@@ -183,13 +208,14 @@ __device__ __forceinline__ void ktile(char* smem, const Ctx& c, int cb, int kb, 
     pin();
     vm_wait_tail<REM, 4, 0, SLACK>();
     bar();
-    mfma_quadrant<T16, 2, 0, ZERO, NBW>(acc, fa, fb0);
+    mfma_quadrant<T16, 2, 0, ZERO, NBW, MF>(acc, fa, fb0);
     bar();
 }
 
 // ---- DMA / fragment context of one tile.  At, Bt = first row of the tile's A / B panel; rows_a, rows_b = rows that exist from
 // there on (M - m0, N - n0; rows past them are clamped to the last valid one).  `tid` is an opaque copy of threadIdx.x: the
 // context is recomputed per tile (a few dozen integer ops) instead of being kept alive across the epilogue.
+template <int MF = 32>
 __device__ __forceinline__ void make_ctx(Ctx& c, int tid, const bf16* At, const bf16* Bt, int rows_a, int rows_b, int lda, int ldb, int krem) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -214,9 +240,15 @@ __device__ __forceinline__ void make_ctx(Ctx& c, int tid, const bf16* At, const 
     c.dA1 = ra * KB; c.dA2 = (ra + 64) * KB; c.dB1 = rb * KB; c.dB2 = (rb + 32) * KB;
     c.aoff = wr * 128 * KB;
     c.boff = wc * 64 * KB;
-    const int r5 = lane & 31, fr = (r5 >> 1) & 7;
+    if constexpr (MF == 16) {      // 16 rows x one logical slot: (row >> 1) & 7 spreads them over 8 physical slots x 2 row parities = all 64 banks
+        const int r4 = lane & 15, fr = (r4 >> 1) & 7;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) c.loff[ks] = r5 * KB + (((2 * ks + (lane >> 5)) ^ fr) << 4);
+        for (int e = 0; e < 4; ++e) c.loff[e] = ((e >> 1) * 16 + r4) * KB + (((4 * (e & 1) + (lane >> 4)) ^ fr) << 4);
+    } else {
+        const int r5 = lane & 31, fr = (r5 >> 1) & 7;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) c.loff[ks] = r5 * KB + (((2 * ks + (lane >> 5)) ^ fr) << 4);
+    }
 }
 
 // Prologue of a tile: K-tile 0 entirely, the first halves of K-tile 1 (12 LDS-DMA instructions per lane).  LDS must be free
@@ -242,7 +274,7 @@ __device__ __forceinline__ void issue_prologue(const Ctx& c, char* smem, int nk)
     do {                                                                                \
         if (st && threadIdx.x == 0) st[(i)] = __builtin_readcyclecounter();              \
     } while (0)
-template <typename T16, int SLACK, int BAUX = 0, int NBW = 4>
+template <typename T16, int SLACK, int BAUX = 0, int NBW = 4, int MF = 32>
 __device__ __forceinline__ void mainloop8p_s(const Ctx& c, int wr, int nk, char* smem, f32x16_t (&acc)[4][2], unsigned long long* st) {
     G8_MSTAMP(8);
     vm_wait<8 + SLACK>();    // A-first, B-first of K-tile 0 (this wave's pieces)
@@ -258,7 +290,7 @@ __device__ __forceinline__ void mainloop8p_s(const Ctx& c, int wr, int nk, char*
     int cb = 0;
     int t = 0;
     if (nk >= 3) {     // first K-tile: accumulators start from zero; the previous epilogue's stores drain under it
-        ktile<T16, 2, SLACK, true, BAUX, NBW>(smem, c, cb, 0, acc, nk == 3 G8_GS_ARG);
+        ktile<T16, 2, SLACK, true, BAUX, NBW, MF>(smem, c, cb, 0, acc, nk == 3 G8_GS_ARG);
         cb ^= BUF_BYTES;
         t = 1;
     } else {
@@ -271,13 +303,13 @@ __device__ __forceinline__ void mainloop8p_s(const Ctx& c, int wr, int nk, char*
     }
     G8_MSTAMP(11);
     for (; t < nk - 2; ++t) {
-        ktile<T16, 2, 0, false, BAUX, NBW>(smem, c, cb, t * KB, acc, t + 3 == nk G8_GS_ARG);
+        ktile<T16, 2, 0, false, BAUX, NBW, MF>(smem, c, cb, t * KB, acc, t + 3 == nk G8_GS_ARG);
         cb ^= BUF_BYTES;
         if (t == 1) G8_MSTAMP(12);
     }
     G8_MSTAMP(13);
-    ktile<T16, 1, 0, false, BAUX, NBW>(smem, c, cb, t * KB, acc, false G8_GS_ARG);
-    ktile<T16, 0, 0, false, BAUX, NBW>(smem, c, cb ^ BUF_BYTES, (t + 1) * KB, acc, false G8_GS_ARG);
+    ktile<T16, 1, 0, false, BAUX, NBW, MF>(smem, c, cb, t * KB, acc, false G8_GS_ARG);
+    ktile<T16, 0, 0, false, BAUX, NBW, MF>(smem, c, cb ^ BUF_BYTES, (t + 1) * KB, acc, false G8_GS_ARG);
 #ifdef G8_EXP_SHADOW
     asm volatile("" ::"v"(gs[0]), "v"(gs[1]), "v"(gs[2]), "v"(gs[3]));
 #endif
@@ -286,11 +318,11 @@ __device__ __forceinline__ void mainloop8p_s(const Ctx& c, int wr, int nk, char*
     G8_MSTAMP(15);
 }
 // `younger`: VMEM operations this wave has issued since the tile's prologue (only a LOWER bound matters: see vm_wait_tail)
-template <typename T16, int BAUX = 0>
+template <typename T16, int BAUX = 0, int MF = 32>
 __device__ __forceinline__ void mainloop8p(const Ctx& c, int wr, int nk, int younger, char* smem, f32x16_t (&acc)[4][2],
                                            unsigned long long* st) {
-    if (younger >= 32) mainloop8p_s<T16, 32, BAUX>(c, wr, nk, smem, acc, st);
-    else if (younger >= 16) mainloop8p_s<T16, 16, BAUX>(c, wr, nk, smem, acc, st);
-    else mainloop8p_s<T16, 0, BAUX>(c, wr, nk, smem, acc, st);
+    if (younger >= 32) mainloop8p_s<T16, 32, BAUX, 4, MF>(c, wr, nk, smem, acc, st);
+    else if (younger >= 16) mainloop8p_s<T16, 16, BAUX, 4, MF>(c, wr, nk, smem, acc, st);
+    else mainloop8p_s<T16, 0, BAUX, 4, MF>(c, wr, nk, smem, acc, st);
 }
 }  // namespace g8

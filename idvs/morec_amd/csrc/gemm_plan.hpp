@@ -51,6 +51,7 @@ struct GemmPlan {
     int ngroup;             // eight_p, two_w: N-tiles per column group of the tile order (0: row-major)
     int tail_split;         // eight_p: the tail round is split along K (needs its workspace)
     int n_cu;               // eight_p: workgroups of the persistent grid (the n_cu the plan was made for)
+    int mfma;               // eight_p: MFMA shape of the main loop, 16 (16x16x32) or 32 (32x32x16).  Internal: not in morec_gemm_plan_info
     int nbh, ksteps;        // skinny: 16-column blocks per wave half, 32-element k-steps
     int generic_tile;       // generic: GemmGenericTile
     int split_k;            // generic
@@ -169,6 +170,11 @@ inline GemmPlan gemm_plan(const morec_gemm_desc& d, const GemmOperands& o, const
             if (d.out_dtype == d.in_dtype && ((p.mode == 0 && !o.colsum) || (p.mode == 1 && !o.colsum) || (p.mode == 5 && o.colsum)))
                 p.tile_rows = pick_tmr(t.gemm8p_tmr, d.M, tiles_n, (d.K + P8_KE - 1) / P8_KE, n_cu);
             p.tile_cols = P8_TN;
+            // MFMA shape of the main loop.  Automatic = 16x16x32 everywhere: at the six products of the encoder step (M = 54 919; K = 768, 2304, 3072;
+            // plain, GELU + act', x act' + column sums) it measured 1.033 - 1.070 x the 32x32x16 launch on fp16 and on bf16, at a run-to-run spread
+            // of at most 0.9 % of a cell (profiles/mfma_shape_launches.txt) -- same tiles, LDS and HBM traffic; the chip holds a higher clock under its power limit
+            // on the 16-row shape.  No dtype, mode or K measured the other way, so the rule has no condition.  "gemm8p_mfma" = 32: the former loop.
+            p.mfma = t.gemm8p_mfma ? t.gemm8p_mfma : 16;
             // column groups of the tile order: automatic = groups of about 6 N-tiles (a 32-CU XCD then works on a ~5 x 6 block)
             const int ng = (tiles_n + 5) / 6;
             p.ngroup = t.gemm8p_ngroup < 0 ? (tiles_n + ng - 1) / ng : t.gemm8p_ngroup;

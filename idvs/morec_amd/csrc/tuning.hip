@@ -11,6 +11,7 @@ enum Handling {
     TMR,         // 0 | 1 | 224 | 192, anything else = 1
     RESERVE,     // 0..128
     TAIL_BIAS,   // 0..16
+    MFMA,        // 0 | 16 | 32; morec_tuning_set refuses anything else, the environment falls back to 0
     AT_LEAST_1,
     // environment-only spellings
     NOT_CHAR_0,  // 0 if the variable starts with '0', else 1
@@ -36,6 +37,7 @@ const Row ROWS[] = {
     {"gemm8p_reserve_cus", "MOREC_GEMM8P_RESERVE_CUS", &Tuning::gemm8p_reserve_cus, 0, RESERVE},
     {"gemm8p_tail_split", "MOREC_GEMM8P_TAIL_SPLIT", &Tuning::gemm8p_tail_split, 0, FLAG},
     {"gemm8p_tail_bias", nullptr, &Tuning::gemm8p_tail_bias, 2, TAIL_BIAS},
+    {"gemm8p_mfma", "MOREC_GEMM8P_MFMA", &Tuning::gemm8p_mfma, 0, MFMA},
     {"gemm8p_debug", "MOREC_GEMM8P_DEBUG", &Tuning::gemm8p_debug, 0, RAW},
     {"gemm8p_stamps_lo", nullptr, &Tuning::gemm8p_stamps_lo, 0, RAW},
     {"gemm8p_stamps_hi", nullptr, &Tuning::gemm8p_stamps_hi, 0, RAW},
@@ -58,6 +60,7 @@ int handled(Handling how, int v) {
         case TMR: return (v == 0 || v == 1 || v == 224 || v == 192) ? v : 1;
         case RESERVE: return v < 0 ? 0 : v > 128 ? 128 : v;
         case TAIL_BIAS: return v < 0 ? 0 : v > 16 ? 16 : v;
+        case MFMA: return (v == 16 || v == 32) ? v : 0;
         case AT_LEAST_1: return v < 1 ? 1 : v;
         default: return v;
     }
@@ -86,6 +89,7 @@ extern "C" int morec_tuning_set(const char* key, int value) {
     if (!key) return MOREC_E_ARG;
     for (const Row& r : ROWS)
         if (r.key && !strcmp(key, r.key)) {
+            if (r.how == MFMA && value != 0 && value != 16 && value != 32) return MOREC_E_UNSUPPORTED;
             table().*r.field = handled(r.how, value);
             return MOREC_OK;
         }

@@ -12,6 +12,7 @@ struct Tuning {
     int gemm8p_ngroup;         // tile order: -1 = automatic column groups, 0 = row-major, n = groups of n N-tiles
     int gemm8p_reserve_cus;    // 0..128 CUs left out of the persistent grid
     int gemm8p_tail_split, gemm8p_tail_bias;
+    int gemm8p_mfma;           // MFMA shape of the main loop: 0 = automatic (gemm_plan), 16 = 16x16x32, 32 = 32x32x16
     int gemm8p_debug;          // ablation bits
     int gemm8p_stamps_lo, gemm8p_stamps_hi;      // device address of the cycle-stamp buffer, in halves
     int deterministic;

@@ -29,9 +29,11 @@
  *      environment is read once, thread-safely, the first time the table is touched -- by a launch or by morec_tuning_set --
  *      and supplies the defaults; a morec_tuning_set call wins over it from then on, whichever came first.  (Before, each
  *      variable was read lazily at some first use, so whether a set key or its variable won depended on the order of calls.)
- *      Every selectable kernel computes the same function to the same accuracy; "gemm8p_tail_split" = 1 is the only knob that
- *      changes the fp32 SUMMATION ORDER (and with it the last-bit rounding pattern of bf16 outputs), which is why it is off
- *      unless asked for.  Set knobs before the first launch or between steps, not concurrently with launches;
+ *      Every selectable kernel computes the same function to the same accuracy; "gemm8p_tail_split" = 1 changes the
+ *      fp32 SUMMATION ORDER (and with it the last-bit rounding pattern of 16-bit outputs), which is why it is off unless asked
+ *      for.  "gemm8p_mfma" regroups the sum inside the instruction (a K-tile as two MFMAs over 32 products or four over 16):
+ *      nothing promises equal rounding there, but on MI355X the two shapes measured bit-identical (profiles/mfma_shape_step.txt).
+ *      Set knobs before the first launch or between steps, not concurrently with launches;
  *   2. with "gemm8p_tail_split" = 1 only: one device scratch allocation per stream (the only memory the library ever allocates);
  *   3. morec_comm handles (below): created and destroyed by the caller;
  *   4. the dropout seed source (morec_dropout_seed_source): one device pointer, NULL by default;
@@ -96,6 +98,8 @@ int morec_version(void);
  *   "gemm8p_reserve_cus" 0..128 CUs (multiple of 8) left out of the persistent grid for a concurrent RCCL kernel   MOREC_GEMM8P_RESERVE_CUS   0
  *   "gemm8p_tail_split"  1 = split the last, partly filled round of tiles along K between two workgroups (K >= 1536)   MOREC_GEMM8P_TAIL_SPLIT   0
  *   "gemm8p_tail_bias"   0..16: share of K the first part takes in that split                          -                         2
+ *   "gemm8p_mfma"        MFMA shape of gemm8p's main loop: 0 automatic | 16 (16x16x32) | 32 (32x32x16); other values are     MOREC_GEMM8P_MFMA         0
+ *                        refused with MOREC_E_UNSUPPORTED (from the environment: 0).  Tiles, schedule and memory traffic do not depend on it;
  *   "gemm8p_debug"       ablation bits (diagnostics)                                                   MOREC_GEMM8P_DEBUG        0
  *   "gemm8p_stamps_lo", "gemm8p_stamps_hi"  device address of a cycle-stamp buffer, in halves          -                         0
  *   "deterministic"      1 = fixed summation order everywhere (state item 6) | 0 off                   MOREC_DETERMINISTIC       0
@@ -109,7 +113,8 @@ int morec_version(void);
  *   MOREC_SWIN_WPW_MIN   fewest windows per workgroup of the window-attention backward (>= 1)                                8
  *   MOREC_SWIN_BWD_WIDE  0 = the narrow window-attention backward                                                            1
  *   MOREC_QUIET          1 = no once-per-process notes on stderr                                                             0
- * Returns MOREC_E_UNSUPPORTED for an unknown key.  No reference counterpart (the reference has no kernels). */
+ * Returns MOREC_E_UNSUPPORTED for an unknown key or a value "gemm8p_mfma" does not take.  No reference counterpart (the reference has no kernels,
+ * SURVEY.md §2). */
 int morec_tuning_set(const char* key, int value);
 /* Deterministic mode: make the partial-sum scratch of `stream` hold at least n_floats (call outside graph capture; under capture the
  * scratch cannot grow and a launch that needs more returns hipErrorOutOfMemory).  The largest user of the encoder step is the LayerNorm
