@@ -44,19 +44,11 @@ def load_det(module, prefix=""):
 
 
 # ------------------------------------------------------------------------------------------------ kernels
-@pytest.mark.parametrize("dt", ["fp32", "bf16", "fp16"])
-@pytest.mark.parametrize("shift", [0, 3])
-@pytest.mark.parametrize("H,W,heads,n_img", [(14, 14, 2, 3), (7, 7, 4, 5), (28, 14, 1, 2)])
-def test_window_attention(dt, shift, H, W, heads, n_img):
-    if min(H, W) <= 7 and shift:
-        pytest.skip("window == map: HF forces shift 0")
-    dtype = DT[dt]
+def _window_attention_oracle(qkv, table, dctx, n_img, H, W, heads, shift):
+    """fp32 torch window attention (7 x 7 windows, head width 32) on the storage-rounded inputs and its autograd backward on
+    (ref * dctx).sum(): (ctx [R, C], dqkv [R, 3 C], dtable [169, heads], bias [1, heads, 49, 49])."""
     C = heads * 32
     R = n_img * H * W
-    qkv = torch.from_numpy(det_normal(f"swa.qkv{H}{W}{heads}", (R, 3 * C), std=0.7)).to(dtype)
-    table = torch.from_numpy(det_normal(f"swa.tab{heads}", (169, heads), std=0.5))
-    dctx = torch.from_numpy(det_normal(f"swa.dctx{H}{W}{heads}", (R, C), std=1.0)).to(dtype)
-    # oracle on the same (storage-rounded) inputs
     q32 = qkv.float().requires_grad_(True)
     t32 = table.clone().requires_grad_(True)
     x = q32.view(n_img, H, W, 3 * C)
@@ -75,21 +67,28 @@ def test_window_attention(dt, shift, H, W, heads, n_img):
         o = torch.roll(o, (shift, shift), (1, 2))
     ref = o.reshape(R, C)
     (ref * dctx.float()).sum().backward()
+    return ref.detach(), q32.grad, t32.grad, bias.detach()
 
+
+def _check_window_attention(dt, n_img, H, W, heads, shift, qkv, table, dctx, oracle):
+    """The window-attention kernels (forward, backward, backward with the fused q|k|v bias gradient) against ``_window_attention_oracle``."""
+    ref, dqkv_ref, dtab_ref, bias = oracle
+    dtype = DT[dt]
+    C = heads * 32
     desc = ops.swin_attn_desc(n_img, H, W, 7, shift, heads, 32, dtype)
     bias_t = ops.swin_bias_expand(table.to(DEV), 7)
-    np.testing.assert_array_equal(bias_t.cpu().numpy(), bias[0].detach().permute(0, 2, 1).numpy())
+    np.testing.assert_array_equal(bias_t.cpu().numpy(), bias[0].permute(0, 2, 1).numpy())
     qd = qkv.to(DEV)
     ctx = ops.swin_attn_fwd(desc, qd, bias_t)
     tol = 2e-5 if dt == "fp32" else 1.5e-2 * T16[dt]
-    assert relerr(ctx.float().cpu().numpy(), ref.detach().numpy()) < tol
+    assert relerr(ctx.float().cpu().numpy(), ref.numpy()) < tol
     dbias_t = torch.zeros_like(bias_t)
     dqkv = ops.swin_attn_bwd(desc, qd, bias_t, ctx, dctx.to(DEV), dbias_t)
     dtab = torch.zeros((169, heads), device=DEV)
     ops.swin_bias_reduce_(dbias_t, dtab, 7)
     tolg = 5e-5 if dt == "fp32" else 3e-2 * T16[dt]
-    assert froerr(dqkv.float().cpu().numpy(), q32.grad.numpy()) < tolg
-    assert froerr(dtab.cpu().numpy(), t32.grad.numpy()) < tolg
+    assert froerr(dqkv.float().cpu().numpy(), dqkv_ref.numpy()) < tolg
+    assert froerr(dtab.cpu().numpy(), dtab_ref.numpy()) < tolg
     # the same backward with the fused q|k|v bias gradient: same dqkv, same dbias_t, dbqkv += column sums of dqkv (the MFMA path
     # sums the rows before their bf16 rounding: agreement with the sums of the STORED rows to rounding noise, not bit for bit)
     dbias2, dbq = torch.zeros_like(bias_t), torch.full((3 * C,), 0.5, device=DEV)
@@ -98,7 +97,63 @@ def test_window_attention(dt, shift, H, W, heads, n_img):
     assert froerr(dbias2.cpu().numpy(), dbias_t.cpu().numpy()) < 1e-5
     want = 0.5 + dqkv.double().sum(0).cpu().numpy()
     assert froerr(dbq.cpu().numpy(), want) < (1e-5 if dt == "fp32" else 3e-3 * T16[dt])
-    assert froerr(dbq.cpu().numpy() - 0.5, q32.grad.double().sum(0).numpy()) < tolg
+    assert froerr(dbq.cpu().numpy() - 0.5, dqkv_ref.double().sum(0).numpy()) < tolg
+
+
+@pytest.mark.parametrize("dt", ["fp32", "bf16", "fp16"])
+@pytest.mark.parametrize("shift", [0, 3])
+@pytest.mark.parametrize("H,W,heads,n_img", [(14, 14, 2, 3), (7, 7, 4, 5), (28, 14, 1, 2)])
+def test_window_attention(dt, shift, H, W, heads, n_img):
+    if min(H, W) <= 7 and shift:
+        pytest.skip("window == map: HF forces shift 0")
+    dtype = DT[dt]
+    C = heads * 32
+    R = n_img * H * W
+    qkv = torch.from_numpy(det_normal(f"swa.qkv{H}{W}{heads}", (R, 3 * C), std=0.7)).to(dtype)
+    table = torch.from_numpy(det_normal(f"swa.tab{heads}", (169, heads), std=0.5))
+    dctx = torch.from_numpy(det_normal(f"swa.dctx{H}{W}{heads}", (R, C), std=1.0)).to(dtype)
+    oracle = _window_attention_oracle(qkv, table, dctx, n_img, H, W, heads, shift)      # on the same (storage-rounded) inputs
+    _check_window_attention(dt, n_img, H, W, heads, shift, qkv, table, dctx, oracle)
+
+
+# Several windows per wavefront.  morec_swin_attn_mfma_launch (swin_attn_mfma.hip): tiles = n_windows * heads, the forward runs
+# wpw = max(1, min(32, tiles / 8192)) windows per wavefront, four wavefronts per workgroup, gx = ceil(n_windows / (4 wpw)) workgroups
+# per head, and a wavefront walks the windows [w0, min(n_windows, w0 + wpw)).  Every case above has <= 16 windows: wpw = 1, the loop runs
+# once and its tail never cuts.  The smallest geometry with wpw = 2 AND a partly filled last workgroup: a 21 x 21 map is 9 windows, 457
+# images are 4113 windows, times 4 heads 16452 tiles -> wpw = 16452 / 8192 = 2 (456 images: 16416 tiles, still 2, but 4104 = 8 * 513
+# fills every wavefront); 4113 = 8 * 514 + 1: the last workgroup's first wavefront owns ONE window, its other three none.  The backward
+# (wpw = max(8, 2) there) and its dbias_t / dbqkv outputs are checked on the same tensors.  If the rule changes, move the case.
+WPW2 = dict(H=21, W=21, shift=3, heads=4, n_img=457)
+
+
+@pytest.fixture(scope="module")
+def wpw2_case():
+    """Inputs and the fp32 oracle of the wpw = 2 case, evaluated ONCE for both 16-bit types (the CPU oracle over ~77 M elements is the
+    cost of this case): the inputs lie on a grid of 1 / 64 inside (-4, 4) -- eight significant bits, exact in bf16 AND in fp16 -- so the
+    storage-rounded inputs of the two types are the same numbers."""
+    import time
+    g = WPW2
+    assert (g["n_img"] * (g["H"] // 7) * (g["W"] // 7) * g["heads"]) // 8192 == 2 and (g["n_img"] * 9) % 8 == 1
+    C, R = g["heads"] * 32, g["n_img"] * g["H"] * g["W"]
+    gen = torch.Generator().manual_seed(21)
+
+    def grid(shape, std):
+        return (torch.round(torch.randn(shape, generator=gen) * (std * 64)) / 64).clamp_(-4 + 1 / 64, 4 - 1 / 64)
+    qkv, dctx = grid((R, 3 * C), 0.7), grid((R, C), 1.0)
+    table = torch.from_numpy(det_normal(f"swa.tab{g['heads']}", (169, g["heads"]), std=0.5))
+    for d in (torch.bfloat16, torch.float16):
+        assert torch.equal(qkv.to(d).float(), qkv) and torch.equal(dctx.to(d).float(), dctx)
+    t0 = time.perf_counter()
+    oracle = _window_attention_oracle(qkv, table, dctx, g["n_img"], g["H"], g["W"], g["heads"], g["shift"])
+    print(f"window attention, wpw = 2: fp32 CPU oracle over {qkv.numel() / 1e6:.0f} M elements took {time.perf_counter() - t0:.1f} s")
+    return qkv, table, dctx, oracle
+
+
+@pytest.mark.parametrize("dt", ["bf16", "fp16"])
+def test_window_attention_several_windows_per_wavefront(dt, wpw2_case):
+    qkv, table, dctx, oracle = wpw2_case
+    g = WPW2
+    _check_window_attention(dt, g["n_img"], g["H"], g["W"], g["heads"], g["shift"], qkv.to(DT[dt]), table, dctx.to(DT[dt]), oracle)
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16", "fp16"])
