@@ -38,23 +38,37 @@ struct CeArgs {
     int tiles_m, tiles_n;
 };
 
+// Where masked_logits keeps its tables in the LDS that the main loop leaves behind, for a tile overlapping `nu` users: ONE definition
+// for the kernel's pointers and for the host (ce_fill refuses a shape whose tables would not fit the ring).
+struct MaskedLogitsLds {
+    int cid, mem, lp, cv, bytes;      // byte offsets of s_cid, s_mem, s_lp, s_cv (s_uid is at 0) and the total
+    __host__ __device__ MaskedLogitsLds(int nu, int S) {
+        cid = ((nu * (S + 1) + 3) & ~3) * (int)sizeof(int32_t);      // s_uid int32 [nu][S+1], padded to 16 bytes
+        mem = cid + 128 * (int)sizeof(int32_t);                      // s_cid int32 [128]
+        lp = mem + ((nu * 128 + 15) & ~15);                          // s_mem uint8 [nu][128]
+        cv = lp + 128 * (int)sizeof(float);                          // s_lp float [128]
+        bytes = cv + 128;                                            // s_cv uint8 [128]
+    }
+};
+
 // Turns the accumulator tile into masked logits in place.  Uses LDS (free after the main loop) for the
 // tile's user id lists, column ids and the [user][column] membership bytes.
 // Returns through `lab[mi]` the label column of each of the lane's 4 rows (or -1 when the row is out of range).
 template <typename T>
 __device__ __forceinline__ void masked_logits(const CeArgs& p, int m0, int n0, char* smem, f32x4_t (&acc)[4][4],
                                               int (&lab)[4]) {
-    int32_t* s_uid = reinterpret_cast<int32_t*>(smem);                       // [nu][S+1]
     const int S1 = p.S + 1;
     const int u_lo = m0 / p.S;
     const int u_hi = min(p.B - 1, (min(m0 + 127, p.Nr - 1)) / p.S);
     const int nu = u_hi - u_lo + 1;
-    int32_t* s_cid = s_uid + ((nu * S1 + 3) & ~3);                           // [128]
-    uint8_t* s_mem = reinterpret_cast<uint8_t*>(s_cid + 128);               // [nu][128]
+    const MaskedLogitsLds L(nu, p.S);
+    int32_t* s_uid = reinterpret_cast<int32_t*>(smem);                       // [nu][S+1]
+    int32_t* s_cid = reinterpret_cast<int32_t*>(smem + L.cid);               // [128]
+    uint8_t* s_mem = reinterpret_cast<uint8_t*>(smem + L.mem);               // [nu][128]
     // the tile's 128 columns' log-popularity and validity, staged once (coalesced) instead of two guarded global loads
     // per logit element -- 128 dependent L2 round trips per lane, most of this kernel's time at these sizes
-    float* s_lp = reinterpret_cast<float*>(s_mem + ((nu * 128 + 15) & ~15));   // [128]
-    uint8_t* s_cv = reinterpret_cast<uint8_t*>(s_lp + 128);                   // [128]
+    float* s_lp = reinterpret_cast<float*>(smem + L.lp);                     // [128]
+    uint8_t* s_cv = reinterpret_cast<uint8_t*>(smem + L.cv);                 // [128]
     const int tid = threadIdx.x;
     for (int i = tid; i < nu * S1; i += 256) s_uid[i] = p.row_ids[u_lo * S1 + i];
     if (tid < 128) {
@@ -283,6 +297,10 @@ static int ce_fill(const morec_ce_desc* d, CeArgs& a) {
     if ((d->D * elt_size(d->dtype)) % 16) return MOREC_E_ALIGN;
     if (d->dtype != MOREC_F32 && !is_h16(d->dtype)) return MOREC_E_DTYPE;
     if (d->col_offset < 0 || d->col_offset + d->B * (d->S + 1) > d->Nc) return MOREC_E_ARG;
+    // a 128-row tile overlaps at most 126 / S + 2 users; their tables live in the 64 KiB that the main loop leaves behind
+    const long nu = d->B < 126 / d->S + 2 ? d->B : 126 / d->S + 2;
+    if (nu * (d->S + 1) > GemmTile<float, 2>::LDS_BYTES / 4) return MOREC_E_UNSUPPORTED;      // (also keeps the int arithmetic below exact)
+    if (MaskedLogitsLds((int)nu, d->S).bytes > GemmTile<float, 2>::LDS_BYTES) return MOREC_E_UNSUPPORTED;
     a.B = d->B; a.S = d->S; a.D = d->D; a.Nr = d->B * d->S; a.Nc = d->Nc; a.col_offset = d->col_offset;
     a.tiles_m = (a.Nr + 127) / 128; a.tiles_n = (a.Nc + 127) / 128; a.K2 = 2 * a.tiles_n;
     a.ldp = d->D; a.lde = d->D;

@@ -461,6 +461,8 @@ int morec_strided_rows_copy(const void* in, void* out, int R, int D, int in_row_
  *      dlogit = gscale * (*gscale_dev if given) * (softmax - onehot) on unmasked cells of valid rows,
  *      0 elsewhere; dP = dlogit . E, dE = dlogit^T . P.
  * workspace (both): morec_inbatch_ce_workspace_bytes().
+ * MOREC_E_UNSUPPORTED: S so long that the id lists of the users under one 128-row tile do not fit the tile kernel's 64 KiB of LDS
+ * (two users of S > 8015 positions; the reference's launchers use S <= 50).
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
     int B, S, D;

@@ -247,6 +247,41 @@ def test_transpose_cast_colsum(dt):
     assert not ops.TransposeBatch.eligible(rnd(10, 6, dt=dt), torch.zeros(6, 16, device=DEV, dtype=dt))     # C % 4 != 0: single-matrix path
 
 
+# one vector of four, and 77 vectors more than the 4096 x 256 threads of the largest grid: a second grid-stride pass with a ragged end
+ELEMENTWISE_N = [4, 4 * (4096 * 256 + 77)]
+
+
+@pytest.mark.parametrize("dt", DT)
+@pytest.mark.parametrize("n", ELEMENTWISE_N)
+def test_act_bwd(dt, n):
+    """``morec_act_bwd``, the backward of the GELU that follows the last projection of ``Text_Encoder`` (T/model/encoders.py:70):
+    out = dy * act'(pre) against fp64 autograd; the ReLU form is a select and exact."""
+    dy, pre = rnd(n, dt=dt, seed=1), rnd(n, dt=dt, scale=2.0, seed=2)
+    out = ops.act_bwd(dy, pre, ACT_GELU)
+    u = pre.double().requires_grad_(True)
+    torch.nn.functional.gelu(u).sum().backward()
+    assert out.dtype == dt and rel(out, dy.double() * u.grad) < tol(dt)
+    out = ops.act_bwd(dy, pre, ACT_RELU)
+    assert torch.equal(out, torch.where(pre > 0, dy, torch.zeros_like(dy)))
+
+
+@pytest.mark.parametrize("dt", DT)
+@pytest.mark.parametrize("n", ELEMENTWISE_N)
+@pytest.mark.parametrize("k", [1, 2, 3])
+def test_scaled_sum(dt, n, k):
+    """``morec_scaled_sum`` with one, two and three inputs against fp64 ``scale * (x0 + x1 + x2)`` rounded to the storage type.  Inputs on
+    a grid of 1 / 16 with a power-of-two scale: sums and product are exact in every type, so is the result; random inputs with
+    scale = 1 / 3: within the type's tolerance."""
+    g = torch.Generator(device="cpu").manual_seed(n + k)
+    xs = [(torch.randint(-8, 9, (n,), generator=g).float() / 16).to(DEV).to(dt) for _ in range(k)]
+    out = ops.scaled_sum(xs, 0.5)
+    assert out.dtype == dt and torch.equal(out, (0.5 * sum(x.double() for x in xs)).to(dt))
+    xs = [rnd(n, dt=dt, seed=10 + i) for i in range(k)]
+    third = float(np.float32(1.0 / 3.0))
+    out = ops.scaled_sum(xs, third)
+    assert rel(out, (third * sum(x.double() for x in xs)).to(dt)) < tol(dt)
+
+
 @pytest.mark.parametrize("dt", DT)
 @pytest.mark.parametrize("N", [64, 512, 768, 2048])
 def test_layernorm(dt, N):
