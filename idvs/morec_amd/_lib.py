@@ -128,6 +128,9 @@ _SIGS = {
     "morec_adamw_sp": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P]),
     "morec_eval_rank": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "morec_eval_rank_cand": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "morec_eval_topk": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, _P]),
+    "morec_eval_topk_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "morec_eval_topk_max_k": (C.c_int, []),
     "morec_dropout_keep_mask": (C.c_int, [_P, C.c_size_t, C.c_float, C.c_uint64, _P]),
     "morec_probe": (C.c_int, [_P, _P]),
     "morec_swin_attn_fwd": (C.c_int, [C.POINTER(SwinAttnDesc), _P, _P, _P, _P]),

@@ -112,6 +112,39 @@ class PackedEvalUsers:
             self.hist[hrows, hcols] = hflat.astype(np.int32)
         self.U, self.S = U, S
 
+    @classmethod
+    def for_recommendation(cls, user_history, seqs, users, S):
+        """The recommendation form: there is no target.  ``idx`` / ``lm`` = the last ``S`` items of the user's WHOLE sequence ``seqs[u]``,
+        right-aligned; ``hist`` = every item the user has interacted with, ``user_history[u]`` (``None``: the items of ``seqs[u]``) --
+        none of them is recommended again; ``target`` = -1."""
+        self = cls.__new__(cls)
+        U = len(users)
+        seq_len = np.fromiter((len(seqs[u]) for u in users), dtype=np.int64, count=U)
+        flat = np.concatenate([np.asarray(seqs[u], dtype=np.int64).reshape(-1) for u in users]) if U and int(seq_len.sum()) else \
+            np.zeros(0, np.int64)
+        ends = np.cumsum(seq_len)
+        n_in = np.minimum(seq_len, S)
+        rows = np.repeat(np.arange(U), n_in)
+        k = np.arange(int(n_in.sum())) - np.repeat(np.cumsum(n_in) - n_in, n_in)
+        self.idx = np.zeros((U, S), dtype=np.int64)
+        self.lm = np.zeros((U, S), dtype=np.float32)
+        self.idx[rows, np.repeat(S - n_in, n_in) + k] = flat[np.repeat(ends - n_in, n_in) + k]
+        self.lm[rows, np.repeat(S - n_in, n_in) + k] = 1.0
+        self.target = np.full(U, -1, dtype=np.int32)
+        if user_history is None:
+            h_len, hflat = seq_len, flat
+        else:
+            h_len = np.fromiter((len(user_history[u]) for u in users), dtype=np.int64, count=U)
+            hflat = np.concatenate([np.asarray(user_history[u], dtype=np.int64).reshape(-1) for u in users]) if U and int(h_len.sum()) \
+                else np.zeros(0, np.int64)
+        hmax = max(1, int(h_len.max()) if U else 1)
+        self.hist = np.full((U, hmax), -1, dtype=np.int32)
+        hrows = np.repeat(np.arange(U), h_len)
+        hcols = np.arange(int(h_len.sum())) - np.repeat(np.cumsum(h_len) - h_len, h_len)
+        self.hist[hrows, hcols] = hflat.astype(np.int32)
+        self.U, self.S = U, S
+        return self
+
     def slice(self, a, b):
         hist = self.hist[a:b]
         used = max(1, int((hist >= 0).sum(1).max()) if b > a else 1)     # the chunk's own widest history: what the kernel walks per tile
@@ -164,6 +197,54 @@ def eval_users(model, user_history, eval_seq, item_embeddings, test_batch_size, 
         dist.all_gather(parts_n, ndcg)
         hit, ndcg = torch.cat(parts_h), torch.cat(parts_n)
     return hit[:n_users], ndcg[:n_users]       # drop the sampler's padding (metrics.py:33-37 ``[:num_total_examples]``)
+
+
+def metrics_from_topk(ids: torch.Tensor, target: torch.Tensor, topK: int = 10):
+    """Hit@K and nDCG@K per user from top-K lists ``ids`` [U, >= topK] (best first, -1 = empty slot) and the target item of each user:
+    the target at 0-based column c < topK is rank c + 1.  Equals ``metrics_from_ranks`` of the target's rank when scores are tie-free."""
+    where = ids[:, :topK].long() == target.long().view(-1, 1)
+    hit = where.any(1).float()
+    rank = where.float().argmax(1) + 1
+    ndcg = torch.where(where.any(1), 1.0 / torch.log2(rank.float() + 1.0), torch.zeros_like(hit))
+    return hit, ndcg
+
+
+def recommend_packed(model, packed: PackedEvalUsers, a, b, item_embeddings, local_rank, k):
+    """Top-``k`` lists of users [a, b) of a ``PackedEvalUsers`` (either form: the mask is its ``hist``): user states exactly as
+    ``eval_ranks_packed`` computes them, selection by the HIP kernel (``ops.eval_topk``) -> ``(ids int32 [b - a, k], scores float32)``."""
+    m = _module(model)
+    idx, lm, hist, _ = packed.slice(a, b)
+    dev = item_embeddings.device
+    with torch.no_grad(), ops.fp32_gemm_mode(getattr(m, "fp32_gemm", ops.FP32_GEMM)):
+        embs = item_embeddings[torch.from_numpy(idx).to(dev)]
+        prec = m.user_encoder(embs, torch.from_numpy(lm).to(dev), local_rank)[:, -1].float().contiguous()
+        return ops.eval_topk(prec, item_embeddings.contiguous(), torch.from_numpy(hist).to(dev), k)
+
+
+def recommend_users(model, user_history, seqs, item_embeddings, test_batch_size, args, local_rank, k):
+    """Top-``k`` lists of every user of ``seqs`` in order (sharded over ranks and gathered like ``eval_users``, the sampler's padding
+    dropped): the recommendation form of ``PackedEvalUsers`` -- the input is the last ``max_seq_len`` items of ``seqs[u]``, the mask is
+    ``user_history[u]`` (``None``: the items of ``seqs[u]``)."""
+    world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
+    rank = dist.get_rank() if world > 1 else 0
+    n_users = len(seqs)
+    sampler = SequentialDistributedSampler(list(range(n_users)), test_batch_size, rank=rank, num_replicas=world)
+    mine = list(iter(sampler))
+    item_embeddings = item_embeddings.to(local_rank)
+    packed = PackedEvalUsers.for_recommendation(user_history, seqs, mine, args.max_seq_len)
+    ids, scores = [], []
+    for s in range(0, len(mine), test_batch_size):
+        i, sc = recommend_packed(model, packed, s, min(len(mine), s + test_batch_size), item_embeddings, local_rank, k)
+        ids.append(i)
+        scores.append(sc)
+    ids, scores = torch.cat(ids), torch.cat(scores)
+    if world > 1:
+        parts_i = [torch.empty_like(ids) for _ in range(world)]
+        parts_s = [torch.empty_like(scores) for _ in range(world)]
+        dist.all_gather(parts_i, ids)
+        dist.all_gather(parts_s, scores)
+        ids, scores = torch.cat(parts_i), torch.cat(parts_s)
+    return ids[:n_users], scores[:n_users]
 
 
 def eval_model(model, user_history, eval_seq, item_embeddings, test_batch_size, args, item_num, Log_file, v_or_t, local_rank):

@@ -695,6 +695,34 @@ def eval_rank_cand(prec, item_emb, hist32, cand_emb, cand_idx32):
     return rank
 
 
+def eval_topk_max_k() -> int:
+    """Largest ``k`` of ``eval_topk`` (``morec_eval_topk_max_k``; host code, no device needed)."""
+    return int(_lib.lib().morec_eval_topk_max_k())
+
+
+def eval_topk(prec, item_emb, hist32, k, strips=0):
+    """``morec_eval_topk``: for every user the ``k`` best catalogue items 1 .. item_num outside the user's history ``hist32`` (int32
+    [U, Hmax] padded with -1, or ``None``: nothing masked), score descending, item id ascending among equal scores -> ``(ids int32
+    [U, k], scores float32 [U, k])``; slots past the eligible items hold -1 / -inf.  ``strips`` cuts the catalogue into column strips
+    (0 = automatic) and does not change the result.  The workspace comes from torch's caching allocator: a second call of the same
+    shape allocates nothing on the device."""
+    U, D = prec.shape
+    k, strips = int(k), int(strips)
+    if k > eval_topk_max_k():
+        raise _lib.MorecError(f"eval_topk: k = {k} is above the kernel's cap of {eval_topk_max_k()}")
+    h = _lib.lib()
+    hmax = 0 if hist32 is None else hist32.shape[1]
+    if hist32 is not None and hist32.dtype != torch.int32:
+        raise _lib.MorecError("eval_topk: the history must be int32")
+    ws_bytes = int(h.morec_eval_topk_ws_bytes(U, item_emb.shape[0], k, strips))
+    ids = torch.empty((U, max(k, 0)), device=prec.device, dtype=torch.int32)
+    scores = torch.empty((U, max(k, 0)), device=prec.device, dtype=torch.float32)
+    ws = torch.empty(max(ws_bytes, 8), device=prec.device, dtype=torch.uint8)
+    check(h.morec_eval_topk(_p(_dev(prec)), _p(_dev(item_emb)), _p(None if hist32 is None else _dev(hist32)), hmax, k, strips, _p(ids),
+                            _p(scores), _p(ws), ws_bytes, U, item_emb.shape[0], D, _stream()), "morec_eval_topk")
+    return ids, scores
+
+
 # ---------------------------------------------------------------------------------------------------------
 # Swin vision tower
 # ---------------------------------------------------------------------------------------------------------

@@ -60,6 +60,10 @@ def build_parser():
     p.add_argument("--new_images_npy", type=str, default="None",
                    help="vision: uint8 [n_new + 1, R, R, 3] images of the new items (row 0 unused); stands in for --new_lmdb_data as "
                         "--images_npy does for the catalogue")
+    # ============== recommendation lists (data_utils/metrics.py: recommend_users) ==============
+    p.add_argument("--topk", type=int, default=10, help="--mode recommend: items per user (at most the top-K kernel's cap)")
+    p.add_argument("--recommend_out", type=str, default="None", help="--mode recommend: output file, one line per test user "
+                   "(<user>\\t<item>:<score> ...); default: recommend_top<K>.tsv in the run's checkpoint directory")
     # ============== MI355X path ==============
     p.add_argument("--compute_dtype", type=str, default="fp16", choices=["bf16", "fp16", "fp32", "fp32x3", "fp16_res32", "bf16_res32"],
                    help="fp16 (default) = IEEE half operands on the MFMA, fp32 accumulate, with the reference's GradScaler loss scaling -- the arithmetic of "

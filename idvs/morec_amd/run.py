@@ -247,6 +247,36 @@ def run_eval(model, item_content, user_history, users_eval, batch_size, item_num
     return hit10
 
 
+def check_topk(k):
+    """``--topk`` against the selection kernel's cap (host code: judged before any data is read)."""
+    from . import ops
+    cap = ops.eval_topk_max_k()
+    if k < 1 or k > cap:
+        raise SystemExit(f"--topk {k}: the top-K kernel returns between 1 and {cap} items per user")
+
+
+def run_recommend(model, item_content, users_test, catalogue, batch_size, use_modal, args, out_path, local_rank):
+    """``--mode recommend``: the catalogue is encoded once; every user of the test split gets the ``--topk`` best items that are not
+    in the user's sequence (input: its last ``max_seq_len`` items), written best first as ``<user>\\t<item name>:<score> ...``.
+    Rank 0 writes the file.  Returns the number of users."""
+    from .data_utils import recommend_users
+    t0 = time.time()
+    model.eval()
+    item_embeddings = get_item_embeddings(model, item_content, batch_size, args, use_modal, local_rank)
+    keys = list(users_test.keys())
+    seqs = [users_test[u] for u in keys]
+    ids, scores = recommend_users(model, None, seqs, item_embeddings, batch_size, args, local_rank, args.topk)
+    ids, scores = ids.cpu().numpy(), scores.cpu().numpy()
+    if not dist.is_initialized() or dist.get_rank() == 0:
+        names = {i: n for n, i in catalogue["item_name_to_id"].items()}
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            for u, row_i, row_s in zip(keys, ids, scores):
+                f.write("%s\t%s\n" % (u, " ".join("%s:%.6g" % (names[int(i)], s) for i, s in zip(row_i, row_s) if i >= 0)))
+    Log.info("recommend: top-%d lists of %d users in %.1f s -> %s" % (args.topk, len(keys), time.time() - t0, out_path))
+    return len(keys)
+
+
 def synthetic_item_name(i, vision):
     """Item names of a ``--synthetic`` catalogue (id i): ``v<i>`` for the vision tower (the form its LMDB keys are derived from),
     ``N<i>`` otherwise."""
@@ -420,6 +450,8 @@ def _load_pretrained_text_tower(bert, args):
 def train(args, use_modal, local_rank):
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
+    if args.mode == "recommend":
+        check_topk(args.topk)
     S, T = args.max_seq_len, args.num_words_title
     vision = use_modal and args.CV_model_load != "None"
     if not vision and hasattr(args, "CV_model_load"):
@@ -512,6 +544,12 @@ def train(args, use_modal, local_rank):
         if getattr(args, "cold_seqs", "None") != "None":
             run_eval_special(model, item_content, catalogue, 512, item_num, use_modal, vision, args, local_rank)
         return hit10
+    if args.mode == "recommend":
+        if ckpt is None:
+            raise SystemExit("--mode recommend needs --load_ckpt_name epoch-N.pt")
+        out_path = args.recommend_out if args.recommend_out != "None" else os.path.join(model_dir, "recommend_top%d.tsv" % args.topk)
+        run_recommend(model, item_content, users_test, catalogue, 512, use_modal, args, out_path, local_rank)
+        return 0.0
     stepper, optimizer = None, None
     if args.fused_step:
         stepper = TrainStep(model, lr=args.lr, fine_tune_lr=args.fine_tune_lr, l2_weight=args.l2_weight,

@@ -563,6 +563,25 @@ int morec_eval_rank(const float* prec, const float* item_emb, const int32_t* his
 int morec_eval_rank_cand(const float* prec, const float* item_emb, const int32_t* hist, int Hmax, const float* cand_emb,
                          int n_cand_rows, const int32_t* cand_idx, int32_t* rank, float* tscore_ws /* float[U] scratch */, int U,
                          int n_items_plus1, int D, void* stream);
+/* Top-K recommendation lists (T/data_utils/metrics.py:96-102 -- score every item, set the history to -inf, argsort -- read for the
+ * first K positions instead of the target's): row u of out_ids / out_scores holds the K best ELIGIBLE items of user u, where item i
+ * is eligible when 1 <= i < n_items_plus1 and i does not occur in hist[u, :], in a strict total order: score descending, item id
+ * ascending among equal scores.  score = prec[u] . item_emb[i] on the exact-fp32 MFMA main loop of morec_eval_rank.  Fewer than K
+ * eligible items: the remaining slots hold id -1 and score -inf.  A NaN score is never returned (ordered comparisons only).
+ * hist: int32 [U, Hmax] as for morec_eval_rank; NULL or Hmax == 0: nobody masks anything.
+ * strips: column strips the catalogue is cut into (0 = automatic, values above the number of 128-column tiles are clamped); the
+ * result does not depend on it, on the grid or on the device.  ws: scratch of at least morec_eval_topk_ws_bytes(...) bytes for the
+ * same (U, n_items_plus1, K, strips), 8-byte aligned.  K < 1, null outputs or a short workspace: MOREC_E_ARG;
+ * K > morec_eval_topk_max_k(): MOREC_E_UNSUPPORTED; D % 4 or misaligned operands: MOREC_E_ALIGN -- all before anything is launched. */
+int morec_eval_topk(const float* prec, const float* item_emb, const int32_t* hist, int Hmax, int K, int strips,
+                    int32_t* out_ids /* [U, K] */, float* out_scores /* [U, K] */, void* ws, size_t ws_bytes, int U,
+                    int n_items_plus1, int D, void* stream);
+/* Host-only queries for morec_eval_topk (no device needed; T/data_utils/metrics.py:96-102 has no counterpart: torch allocates the
+ * score matrix).  ws_bytes: 0 for arguments morec_eval_topk rejects, else positive and monotone in U, K and strips. */
+size_t morec_eval_topk_ws_bytes(int U, int n_items_plus1, int K, int strips);
+/* Largest K of morec_eval_topk (T/data_utils/metrics.py:49-57 uses 10): one list entry per lane of a wave, and 128 rows x K x 8 B of
+ * lists beside the 64 KiB score tile in one CU's 160 KiB of LDS -- 64. */
+int morec_eval_topk_max_k(void);
 
 /* test hook: out[i] = 1 iff the dropout hash keeps element index i for (p, seed) */
 int morec_dropout_keep_mask(uint8_t* out, size_t n, float p, uint64_t seed, void* stream);
