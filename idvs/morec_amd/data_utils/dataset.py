@@ -48,10 +48,11 @@ def collate_train_batch(u2seq, users, item_content, max_seq_len, use_modal):
     return torch.from_numpy(ids), items, torch.from_numpy(log_mask)
 
 
-def collate_bce_batch(u2seq, users, item_content, max_seq_len, item_num, use_modal, rng):
+def collate_bce_batch(u2seq, users, item_content, max_seq_len, item_num, use_modal, rng, with_ids=False):
     """Batch of the BCE variant (``bce_text/main-end2end/data_utils/dataset.py:25-49``): per user the left-padded sequence and,
     for every input position, one negative drawn uniformly from the items the user has not interacted with (rejection
-    sampling, as the reference does); returns (sample_items [B, S+1, 2(, 2T)], log_mask [B, S])."""
+    sampling, as the reference does); returns (sample_items [B, S+1, 2(, 2T)], log_mask [B, S]).  ``with_ids`` (the fusion towers,
+    ``bce_text/id_plus_mo-end2end/data_utils/dataset.py``): (sample_items_id [B, S+1, 2], sample_items, log_mask)."""
     B, L = len(users), max_seq_len + 1
     items = np.zeros((B, L, 2), dtype=np.int64)
     log_mask = np.zeros((B, max_seq_len), dtype=np.float32)
@@ -67,6 +68,8 @@ def collate_bce_batch(u2seq, users, item_content, max_seq_len, item_num, use_mod
                 neg = int(rng.integers(1, item_num + 1))
             items[r, L - n + j, 1] = neg
     out = np.asarray(item_content)[items] if use_modal else items
+    if with_ids:
+        return torch.from_numpy(items), torch.from_numpy(np.ascontiguousarray(out)).long(), torch.from_numpy(log_mask)
     return torch.from_numpy(np.ascontiguousarray(out)).long(), torch.from_numpy(log_mask)
 
 

@@ -32,6 +32,7 @@ def get_item_embeddings(model, item_content, test_batch_size, args, use_modal, l
 def _get_item_embeddings(model, item_content, test_batch_size, args, use_modal, local_rank):
     m = _module(model)
     vision = bool(use_modal and getattr(m, "vision", False))
+    fusion = getattr(m, "fusion", None) if use_modal else None      # ID (+) modality fusion: every catalogue row is fc(id row, content vector)
     # vision (``get_itemLMDB_embeddings``, V/data_utils/metrics.py:63-76): ``item_content`` is the decoded image tensor
     # f32[item_num+1, 3, R, R] (the LMDB / PIL decode of V/data_utils/dataset.py is host-side I/O outside this library)
     if hasattr(item_content, "device_batch"):       # LmdbItemImages: records decoded per chunk, resized on the device
@@ -39,7 +40,11 @@ def _get_item_embeddings(model, item_content, test_batch_size, args, use_modal, 
         with torch.no_grad():
             for s in range(0, len(item_content), test_batch_size):
                 ids = np.arange(s, min(len(item_content), s + test_batch_size))
-                outs.append(m.cv_encoder(item_content.device_batch(ids, local_rank).contiguous()))
+                px = item_content.device_batch(ids, local_rank).contiguous()
+                if fusion:
+                    outs.append(m.fc.encode(torch.from_numpy(ids).to(px.device), m.cv_encoder.encode(px), m.id_embedding.weight))
+                else:
+                    outs.append(m.cv_encoder(px))
         return torch.cat(outs, 0).float().detach()
     content = torch.as_tensor(np.asarray(item_content))
     if not vision:
@@ -61,7 +66,11 @@ def _get_item_embeddings(model, item_content, test_batch_size, args, use_modal, 
     with torch.no_grad():
         for s in starts:
             chunk = content[s:s + test_batch_size].to(local_rank)
-            if vision:
+            if fusion:      # fc(id_embedding(ids of the chunk), encoder(content of the chunk)): bce_text/id_plus_mo-end2end/data_utils/metrics.py:84-97
+                enc = m.cv_encoder if vision else m.bert_encoder
+                ids = torch.arange(s, s + chunk.shape[0], device=chunk.device, dtype=torch.int32)
+                o = m.fc.encode(ids, enc.encode(chunk.contiguous()), m.id_embedding.weight).float()
+            elif vision:
                 o = m.cv_encoder(chunk.contiguous())
             else:
                 o = m.bert_encoder(chunk) if use_modal else m.id_embedding(chunk)

@@ -131,6 +131,79 @@ class IdEmbeddingFn(torch.autograd.Function):
         return None, dw, None
 
 
+class FusionFn(torch.autograd.Function):
+    """ID (+) modality fusion ``fc(id_embedding(ids), content)`` (``bce_text/id_plus_mo-end2end/model/model.py:43-47``): ``ADD`` or ``CAT``
+    (``model/encoders.py:8-39``).  ``cfg = (kind, dtype, drop, pad_id)``: kind "add" | "cat", the compute dtype, a ``DropCfg`` whose
+    ``p_hidden`` is the MLP's drop rate (site 0: the concatenation, site l: the input of layer l), and the table row that receives no
+    gradient (0 = ``padding_idx``; -1: none).  ``fc_params`` = (W1, b1[, W2, b2, W3, b3]).  Gradients: content, the id table (dense fp32,
+    like ``IdEmbeddingFn``), the fc weights and biases.  Outside the residual stream: the ``*_res32`` modes are plain 16-bit here."""
+
+    @staticmethod
+    def forward(ctx, ids, content, table, cfg, *fc_params):
+        kind, dtype, drop, pad_id = cfg
+        need = any(ctx.needs_input_grad)
+        idx = ids.reshape(-1).to(torch.int32).contiguous()
+        y = content.contiguous().view(idx.numel(), -1)
+        if y.dtype != dtype:
+            y = ops.cast(y, dtype)
+        tab = table.contiguous()
+        if tab.dtype != torch.float32 or tab.shape[1] != y.shape[1]:
+            raise ValueError(f"fusion: the id table must be fp32 [n, {y.shape[1]}] (content width), got {tab.dtype} {tuple(tab.shape)}")
+        if kind == "cat" and fc_params[0].shape[1] != 2 * y.shape[1]:
+            raise ValueError(f"fusion: the first Linear takes {fc_params[0].shape[1]} inputs, the concatenation has {2 * y.shape[1]}")
+        ctx.fp32_gemm = ops.FP32_GEMM
+        ctx.meta = (kind, pad_id, content.dtype, tuple(content.shape), tuple(table.shape))
+        if kind == "add":
+            ctx.stuff = (idx,)
+            return ops.fuse_add_fwd(tab, idx, y)
+        p = float(drop.p_hidden)
+        n_layers = len(fc_params) // 2
+        lin = [engine.prepare_linear(fc_params[2 * l], dtype) for l in range(n_layers)]
+        a = ops.fuse_cat_fwd(tab, idx, y, p, drop.site(0))
+        acts, pres = [], []
+        for l in range(n_layers):
+            pre = torch.empty((a.shape[0], lin[l].w.shape[0]), device=a.device, dtype=dtype) if need else None
+            h = ops.gemm_nt(a, lin[l].w, bias=fc_params[2 * l + 1], act=ops.ACT_GELU, aux_out=pre)
+            acts.append(a)
+            pres.append(pre)
+            if l + 1 < n_layers and p > 0:
+                ops.dropout_apply_(h, p, drop.site(l + 1))
+            a = h
+        ctx.stuff = (idx, lin, acts, pres, p, drop) if need else None
+        return a
+
+    @staticmethod
+    def backward(ctx, dout):
+        kind, pad_id, in_dtype, in_shape, tshape = ctx.meta
+        stuff, ctx.stuff = ctx.stuff, None
+        idx = stuff[0]
+        d_table = torch.zeros(tshape, device=dout.device, dtype=torch.float32)
+        d = dout.contiguous().view(idx.numel(), -1)
+        if kind == "add":
+            ops.scatter_add_rows_(d, idx, d_table, pad_id)
+            dc = d if d.dtype == in_dtype else ops.cast(d, in_dtype)
+            return None, dc.view(in_shape), d_table, None
+        _, lin, acts, pres, p, drop = stuff
+        n_layers = len(lin)
+        grads = []
+        with ops.fp32_gemm_mode(ctx.fp32_gemm):
+            for l in reversed(range(n_layers)):
+                if l + 1 < n_layers and p > 0:      # the mask the forward put on this layer's output
+                    d = ops.dropout_apply_(d.clone() if d.data_ptr() == dout.data_ptr() else d, p, drop.site(l + 1))
+                dv = ops.act_bwd(d, pres[l], ops.ACT_GELU)
+                db = torch.zeros(dv.shape[1], device=dv.device, dtype=torch.float32)
+                dw = torch.zeros(lin[l].w.shape, device=dv.device, dtype=torch.float32)
+                ops.colsum_(dv, db)
+                engine.linear_wgrad_(dv, acts[l], dw)
+                grads = [dw, db] + grads
+                d = ops.gemm_nt(dv, lin[l].wt, K=dv.shape[1], N=acts[l].shape[1])
+            dc = ops.fuse_cat_bwd(d, idx, d_table, pad_id, p, drop.site(0))
+            engine.WgradStream.join(dout.device)
+        if dc.dtype != in_dtype:
+            dc = ops.cast(dc, in_dtype)
+        return (None, dc.view(in_shape), d_table, None) + tuple(grads)
+
+
 def _all_gather_cat(t: torch.Tensor, world: int, comm=None) -> torch.Tensor:
     if comm is not None:       # morec_comm_all_gather: RCCL on the compute stream (comm.MorecComm)
         return comm.all_gather(t)

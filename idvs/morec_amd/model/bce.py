@@ -1,13 +1,16 @@
 """``BceModel``: drop-in for ``bce_text/main-end2end/model/model.py`` -- the same encoders as the in-batch
 ``Model`` with the one-sampled-negative BCE loss of ``model.py:30-51``: constructor ``(args, item_num, use_modal,
 bert_model)``, ``forward(sample_items, log_mask, local_rank)``, attributes ``user_encoder`` / ``bert_encoder`` /
-``id_embedding``, identical ``state_dict`` keys.  Scoring, loss and their backward are ``morec_bce_fwd/bwd``."""
+``id_embedding``, identical ``state_dict`` keys.  Scoring, loss and their backward are ``morec_bce_fwd/bwd``.
+With ``args.item_tower`` 'modal_add' / 'modal_cat' / 'modal_cat_3' it is the drop-in for ``bce_text/id_plus_mo-end2end/model/model.py``:
+``forward(sample_items_id, sample_items_content, log_mask, local_rank)``, attributes ``bert_encoder`` AND ``fc`` AND ``id_embedding``, item
+vectors ``fc(id_embedding(id), bert_encoder(content))`` (``encoders.ADD`` / ``CAT``)."""
 import torch
 from torch import nn
 from torch.nn.init import xavier_normal_
 
-from .. import ops
-from .encoders import Bert_Encoder, IdEmbedding, User_Encoder, resolve_dtype, resolve_fp32_gemm, resolve_res32
+from .. import engine, ops
+from .encoders import Bert_Encoder, IdEmbedding, User_Encoder, fusion_tower, make_fusion, resolve_dtype, resolve_fp32_gemm, resolve_res32
 
 
 class BceLossFn(torch.autograd.Function):
@@ -45,19 +48,44 @@ class BceModel(nn.Module):
                                          n_layers=args.transformer_block, compute_dtype=self.compute_dtype, res32=resolve_res32(args))
         if self.use_modal:
             self.bert_encoder = Bert_Encoder(args=args, bert_model=bert_model)
-        else:
+        # ID (+) modality fusion (bce_text/id_plus_mo-end2end/model/model.py:23-39): encoder AND fc AND id_embedding
+        self.fusion = fusion_tower(args)[0] if self.use_modal else None
+        if self.fusion:
+            self.fc = make_fusion(args, self.compute_dtype)
+        if self.fusion or not self.use_modal:
             self.id_embedding = IdEmbedding(item_num + 1, args.embedding_dim, padding_idx=0, compute_dtype=self.compute_dtype)
             xavier_normal_(self.id_embedding.weight.data)
         self.criterion = nn.BCEWithLogitsLoss()          # attribute compatibility; unused
+        self._drop_calls = 0
 
-    def forward(self, sample_items, log_mask, local_rank=None):
+    def dropout_cfgs(self):
+        """(item, user, fusion) dropout streams.  The encoders of this model run without dropout, as before the fusion towers; the
+        fusion MLP draws ``args.drop_rate`` in training mode, from ``torch.initial_seed()`` and a per-call counter."""
+        p = float(self.args.drop_rate)
+        if not self.training or not self.fusion or p <= 0:
+            return engine.NO_DROP, engine.NO_DROP, engine.NO_DROP
+        self._drop_calls += 1
+        base = (torch.initial_seed() * 0x9E3779B97F4A7C15 + self._drop_calls * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
+        return engine.NO_DROP, engine.NO_DROP, engine.DropCfg(p, 0.0, base ^ 0x3C6EF372FE94F82B)
+
+    def forward(self, *inputs, local_rank=None):
+        """``(sample_items, log_mask, local_rank)`` (bce_text/main-end2end), or with a fusion tower the four-argument form of
+        bce_text/id_plus_mo-end2end: ``(sample_items_id, sample_items_content, log_mask, local_rank)``."""
+        n = 3 if self.fusion else 2
+        if not n <= len(inputs) <= n + 1:
+            raise TypeError(f"BceModel.forward takes {'(sample_items_id, sample_items_content' if self.fusion else '(sample_items'}, log_mask, "
+                            f"local_rank) with item_tower={getattr(self.args, 'item_tower', None)!r}; got {len(inputs)} arguments")
         with ops.fp32_gemm_mode(self.fp32_gemm):      # the autograd shells carry the mode into their backward
-            return self._forward(sample_items, log_mask, local_rank)
+            if self.fusion:
+                return self._forward(inputs[1], inputs[2], None, inputs[0])
+            return self._forward(inputs[0], inputs[1], None)
 
-    def _forward(self, sample_items, log_mask, local_rank=None):
+    def _forward(self, sample_items, log_mask, local_rank=None, sample_items_id=None):
         D = self.args.embedding_dim
         if self.use_modal:
             E = self.bert_encoder.encode(sample_items.reshape(-1, sample_items.shape[-1]))
+            if self.fusion:
+                E = self.fc.encode(sample_items_id.reshape(-1), E, self.id_embedding.weight, self.dropout_cfgs()[2])
         else:
             E = self.id_embedding.encode(sample_items.reshape(-1))
         E = E.reshape(-1, D)

@@ -1,5 +1,6 @@
 """Item / user encoders with the reference's class names, constructor arguments, attribute names and
-``forward`` signatures (``T/model/encoders.py:7-117``); arithmetic in ``libmorec_hip.so``."""
+``forward`` signatures (``T/model/encoders.py:7-117``; ``ADD`` / ``CAT``: ``bce_text/id_plus_mo-end2end/model/encoders.py:8-39``);
+arithmetic in ``libmorec_hip.so``."""
 import os
 
 import torch
@@ -35,6 +36,90 @@ def resolve_fp32_gemm(args=None) -> str:
     """How products of fp32 operands run for this model: ``ops.FP32_GEMM`` value ("exact" | "bf16x3")."""
     name = getattr(args, "compute_dtype", None) or os.environ.get("MOREC_DTYPE", "bf16")
     return "bf16x3" if str(name) == "fp32x3" else "exact"
+
+
+def fusion_tower(args=None):
+    """The fusion tower ``args.item_tower`` names (``bce_text/id_plus_mo-end2end/model/model.py:26-36``): ("add", 0), ("cat", 1),
+    ("cat", 3) for a name containing 'cat_3', or (None, 0)."""
+    name = str(getattr(args, "item_tower", "") or "")
+    if "add" in name:
+        return "add", 0
+    if "cat" in name:
+        return "cat", 3 if "cat_3" in name else 1
+    return None, 0
+
+
+def make_fusion(args, compute_dtype):
+    kind, n = fusion_tower(args)
+    if kind == "add":
+        return ADD(compute_dtype=compute_dtype)
+    if kind == "cat":
+        return CAT(layers=[args.embedding_dim * 2] + [args.embedding_dim] * n, drop_rate=args.drop_rate, compute_dtype=compute_dtype)
+    return None
+
+
+class _Fusion(nn.Module):
+    """Shared plumbing of ``ADD`` / ``CAT``: ``encode`` is the models' path (ids + the id table, so the gather is part of the fused
+    kernel); ``forward(x, y)`` keeps the reference's signature on already-gathered id vectors (row r of ``x`` is its own table row)."""
+    kind = None
+
+    def _params(self):
+        return ()
+
+    def encode(self, ids, content, table, drop: DropCfg = NO_DROP, pad_id: int = 0):
+        cfg = (self.kind, self.compute_dtype, drop, pad_id)
+        return F_.FusionFn.apply(ids, content, table, cfg, *self._params())
+
+    def _own_drop(self):
+        p = float(getattr(self, "drop_rate", 0.0))
+        if not self.training or p <= 0:
+            return NO_DROP
+        self._drop_calls += 1
+        return DropCfg(p, 0.0, (torch.initial_seed() * 0x9E3779B97F4A7C15 + self._drop_calls * 0xA0761D6478BD642F) & 0xFFFFFFFFFFFFFFFF)
+
+    def forward(self, x, y):
+        R = x.shape[0]
+        ids = torch.arange(R, device=x.device, dtype=torch.int32)
+        out = self.encode(ids, y, x if x.dtype == torch.float32 else x.float(), self._own_drop(), pad_id=-1)
+        return out if out.dtype == x.dtype else out.to(x.dtype)
+
+
+class ADD(_Fusion):
+    """``x + y`` (``model/encoders.py:8-13`` of the fusion package): ``morec_fuse_add_fwd``."""
+    kind = "add"
+
+    def __init__(self, compute_dtype=None):
+        super().__init__()
+        self.compute_dtype = compute_dtype or resolve_dtype()
+        self._drop_calls = 0
+
+
+class CAT(_Fusion):
+    """``cat([x, y], 1)`` through ``len(layers) - 1`` triples of Dropout -> Linear -> GELU (``model/encoders.py:17-39`` of the fusion
+    package; keys ``mlp_layers.{1,4,7}.{weight,bias}``).  The nn modules hold the parameters; the arithmetic is ``functional.FusionFn``."""
+    kind = "cat"
+
+    def __init__(self, layers, drop_rate, compute_dtype=None):
+        super().__init__()
+        self.layers = layers
+        self.drop_rate = drop_rate
+        mods = []
+        for n_in, n_out in zip(layers[:-1], layers[1:]):
+            mods += [nn.Dropout(p=drop_rate), nn.Linear(n_in, n_out), nn.GELU()]
+        self.mlp_layers = nn.Sequential(*mods)
+        self.compute_dtype = compute_dtype or resolve_dtype()
+        self._drop_calls = 0
+        for m in self.mlp_layers:
+            if isinstance(m, nn.Linear):
+                xavier_normal_(m.weight.data)
+                constant_(m.bias.data, 0)
+
+    def _params(self):
+        out = []
+        for m in self.mlp_layers:
+            if isinstance(m, nn.Linear):
+                out += [m.weight, m.bias]
+        return tuple(out)
 
 
 class User_Encoder(nn.Module):

@@ -2,7 +2,9 @@
 sub-module attribute names (``bert_encoder`` | ``cv_encoder`` / ``id_embedding`` / ``user_encoder``) and ``state_dict``
 keys; every FLOP of the forward AND backward runs in hand-written gfx950 kernels behind ``libmorec_hip.so``.  The
 vision variant is selected the way the reference's two packages differ: ``args.CV_model_load`` is present
-(``V/model/model.py:24-29``) and the fourth constructor argument is the image network."""
+(``V/model/model.py:24-29``) and the fourth constructor argument is the image network.  ``args.item_tower`` 'modal_add' / 'modal_cat' /
+'modal_cat_3' adds the ID (+) modality fusion of ``bce_text/id_plus_mo-end2end/model/model.py:23-47``: the model then owns the encoder, ``fc``
+AND ``id_embedding``, and every item vector is ``fc(id_embedding(id), encoder(content))`` (``encoders.ADD`` / ``CAT``, ``csrc/fuse.hip``)."""
 import torch
 import torch.distributed as dist
 from torch import nn
@@ -10,7 +12,8 @@ from torch.nn.init import xavier_normal_
 
 from .. import engine, ops
 from .. import functional as F_
-from .encoders import Bert_Encoder, IdEmbedding, User_Encoder, Vit_Encoder, resolve_dtype, resolve_fp32_gemm, resolve_res32
+from .encoders import (Bert_Encoder, IdEmbedding, User_Encoder, Vit_Encoder, fusion_tower, make_fusion, resolve_dtype, resolve_fp32_gemm,
+                       resolve_res32)
 
 
 class Model(nn.Module):
@@ -43,7 +46,12 @@ class Model(nn.Module):
             self.cv_encoder = Vit_Encoder(image_net=bert_model, compute_dtype=self.compute_dtype)
         elif self.use_modal:
             self.bert_encoder = Bert_Encoder(args=args, bert_model=bert_model)
-        else:
+        # ID (+) modality fusion (bce_text/id_plus_mo-end2end/model/model.py:23-39, here under the in-batch loss too): the model then owns
+        # the encoder AND fc AND id_embedding, and every item vector is fc(id_embedding(id), encoder(content))
+        self.fusion = fusion_tower(args)[0] if self.use_modal else None
+        if self.fusion:
+            self.fc = make_fusion(args, self.compute_dtype)
+        if self.fusion or not self.use_modal:
             self.id_embedding = IdEmbedding(item_num + 1, args.embedding_dim, padding_idx=0,
                                             compute_dtype=self.compute_dtype)
             xavier_normal_(self.id_embedding.weight.data)            # T/model/model.py:28 (overwrites the pad row too)
@@ -52,9 +60,10 @@ class Model(nn.Module):
 
     def dropout_cfgs(self):
         """Per-call dropout streams (training mode only).  SASRec uses ``args.drop_rate`` on hidden states and attention
-        probabilities (``T/model/modules.py:9,24,48``); BERT uses its own config's probabilities (HF)."""
+        probabilities (``T/model/modules.py:9,24,48``); BERT uses its own config's probabilities (HF).  With a fusion tower a third
+        stream follows: the fusion MLP's Dropouts (``args.drop_rate``), from the same base seed with a constant of its own."""
         if not self.training:
-            return engine.NO_DROP, engine.NO_DROP
+            return (engine.NO_DROP,) * (3 if self.fusion else 2)
         self._drop_calls += 1
         base = (torch.initial_seed() * 0x9E3779B97F4A7C15 + self._drop_calls * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
         if dist.is_available() and dist.is_initialized():
@@ -69,6 +78,8 @@ class Model(nn.Module):
             ph, pa = float(getattr(c, "hidden_dropout_prob", 0.0)), float(getattr(c, "attention_probs_dropout_prob", 0.0))
             if ph > 0 or pa > 0:
                 d_item = engine.DropCfg(ph, pa, base)
+        if self.fusion:
+            return d_item, d_user, (engine.DropCfg(p, 0.0, base ^ 0x3C6EF372FE94F82B) if p > 0 else engine.NO_DROP)
         return d_item, d_user
 
     def _log_pop_table(self, device):
@@ -83,13 +94,15 @@ class Model(nn.Module):
     def _forward(self, sample_items_id, sample_items, log_mask, local_rank=None):
         D = self.args.embedding_dim
         ids = sample_items_id.view(-1)
-        d_item, d_user = self.dropout_cfgs()
+        d_item, d_user, *d_fuse = self.dropout_cfgs()
         if self.use_modal and self.vision:
             score_embs = self.cv_encoder.encode(sample_items, d_item)
         elif self.use_modal:
             score_embs = self.bert_encoder.encode(sample_items, d_item)
         else:
             score_embs = self.id_embedding.encode(sample_items.view(-1))
+        if self.fusion:      # the fused vectors are the SASRec inputs and the scoring candidates
+            score_embs = self.fc.encode(ids, score_embs, self.id_embedding.weight, d_fuse[0])
         input_embs = score_embs.view(-1, self.max_seq_len + 1, D)
         prec_vec = self.user_encoder.encode(input_embs[:, :-1, :], log_mask, d_user).reshape(-1, D)
         ci = engine.ce_inputs_local(ids, log_mask, self._log_pop_table(ids.device))

@@ -548,6 +548,44 @@ def scatter_add_rows_(d, idx32, dtable, pad_id):
           "morec_scatter_add_rows")
 
 
+def fuse_add_fwd(table, idx32, content):
+    """``table[idx] + content`` in content's dtype: one fp32 add, one rounding (``morec_fuse_add_fwd``; the ADD fusion tower)."""
+    _dev(table), _dev(content)
+    R, D = content.shape
+    out = torch.empty_like(content)
+    check(_lib.lib().morec_fuse_add_fwd(_p(table), _p(idx32), _p(content), _p(out), R, D, code(content.dtype), _stream()), "morec_fuse_add_fwd")
+    return out
+
+
+def fuse_cat_fwd(table, idx32, content, p=0.0, seed=0):
+    """``drop(cat([table[idx], content], 1))`` [R, 2D] in content's dtype, one dropout stream over the result (``morec_fuse_cat_fwd``)."""
+    _dev(table), _dev(content)
+    R, D = content.shape
+    a = torch.empty((R, 2 * D), device=content.device, dtype=content.dtype)
+    check(_lib.lib().morec_fuse_cat_fwd(_p(table), _p(idx32), _p(content), _p(a), R, D, code(content.dtype), float(p), int(seed), _stream()),
+          "morec_fuse_cat_fwd")
+    return a
+
+
+def fuse_cat_bwd(dA, idx32, d_table, pad_id=0, p=0.0, seed=0):
+    """Backward of ``fuse_cat_fwd`` with the forward's (p, seed): returns the content gradient [R, D]; the id half of ``dA`` [R, 2D] is
+    scatter-ADDED into the fp32 ``d_table`` (rows ``pad_id`` skipped) (``morec_fuse_cat_bwd``)."""
+    _dev(dA), _dev(d_table)
+    R, D = dA.shape[0], dA.shape[1] // 2
+    assert d_table.dtype == torch.float32 and d_table.shape[1] == D
+    d_content = torch.empty((R, D), device=dA.device, dtype=dA.dtype)
+    check(_lib.lib().morec_fuse_cat_bwd(_p(dA), _p(idx32), _p(d_content), _p(d_table), R, D, pad_id, code(dA.dtype), float(p), int(seed),
+                                        _stream()), "morec_fuse_cat_bwd")
+    return d_content
+
+
+def dropout_apply_(x, p, seed):
+    """In place: ``x = keep ? x * inv_keep : 0`` with the counter-based stream of (p, seed) over x's elements (``morec_dropout_apply``)."""
+    _dev(x)
+    check(_lib.lib().morec_dropout_apply(_p(x), _p(x), x.numel(), float(p), int(seed), code(x.dtype), _stream()), "morec_dropout_apply")
+    return x
+
+
 def indexed_rows_copy(src, out, in_idx=None, out_idx=None, R=None):
     """out[out_idx[r]] = src[in_idx[r]] (int32 device index vectors; None = identity)."""
     _dev(src), _dev(out)

@@ -5,11 +5,16 @@ import argparse
 import os
 
 
+ITEM_TOWERS = ("id", "modal", "modal_add", "modal_cat", "modal_cat_3")
+
+
 def build_parser():
     p = argparse.ArgumentParser()
     # ============== data_dir ==============
     p.add_argument("--mode", type=str, default="train")
-    p.add_argument("--item_tower", type=str, default="id")
+    p.add_argument("--item_tower", type=str, default="id", choices=ITEM_TOWERS,
+                   help="id | modal, or ID (+) modality fusion (bce_text/id_plus_mo-end2end): modal_add = id vector + content vector, "
+                        "modal_cat / modal_cat_3 = their concatenation through one / three Dropout-Linear-GELU layers")
     p.add_argument("--root_data_dir", type=str, default="../")
     p.add_argument("--dataset", type=str, default="MIND-small")
     p.add_argument("--behaviors", type=str, default="behaviors_l5_tr_v.tsv")
@@ -95,6 +100,21 @@ def build_parser():
     p.add_argument("--pretrained_dir", type=str, default="../pretrained_models",
                    help="directory holding <bert_model_load>/pytorch_model.bin (T/run.py:29-53 reads ../../pretrained_models/)")
     return p
+
+
+def check_fusion_args(args):
+    """What an ID (+) modality fusion tower does not run with: exits with the reason (before anything touches a device)."""
+    from .model.encoders import fusion_tower
+    kind = fusion_tower(args)[0] if "modal" in str(args.item_tower) else None
+    if kind is None:
+        return None
+    if getattr(args, "fused_step", False) or getattr(args, "graph", False):
+        raise SystemExit(f"--item_tower {args.item_tower}: the fusion towers run on the drop-in autograd path (Model / BceModel with "
+                         "torch.optim.AdamW); --fused_step / --graph (train_step.TrainStep) do not cover them")
+    if getattr(args, "new_seqs", "None") != "None":
+        raise SystemExit(f"--item_tower {args.item_tower}: a new item has no row in the id table, so the fused vector fc(id, content) "
+                         "does not exist for it; --new_seqs is not available with a fusion tower (--cold_seqs alone is)")
+    return kind
 
 
 def parse_args(argv=None):

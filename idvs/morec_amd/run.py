@@ -30,7 +30,7 @@ from .data_utils import (collate_bce_batch, collate_train_batch, epoch_batches, 
 from .model import BceModel, BertShape, HipBertModel, Model
 from .model.swin import HipSwinForImageClassification
 from .swin_engine import SwinShape
-from .parameters import parse_args
+from .parameters import check_fusion_args, parse_args
 from . import engine
 from .train_step import TrainStep
 
@@ -106,9 +106,10 @@ class BatchMaker:
     for a single attribute, one per attribute otherwise.  ``pin``: False inside worker processes (they must not touch the HIP runtime;
     the loader's pin thread page-locks), None = page-lock when a GPU is present."""
 
-    def __init__(self, users, users_train, item_content, S, use_modal, *, bce=False, item_num=0, neg_seed=0, text_attrs=None, pad_to=0, pin=None):
+    def __init__(self, users, users_train, item_content, S, use_modal, *, bce=False, item_num=0, neg_seed=0, text_attrs=None, pad_to=0, pin=None,
+                 bce_ids=False):
         self.users, self.users_train, self.item_content, self.S, self.use_modal = users, users_train, item_content, S, use_modal
-        self.bce, self.item_num, self.neg_seed = bce, item_num, neg_seed
+        self.bce, self.item_num, self.neg_seed, self.bce_ids = bce, item_num, neg_seed, bce_ids
         self.text_attrs, self.pad_to, self.pin = list(text_attrs or []), pad_to, pin
         self._neg_rng = None
 
@@ -117,8 +118,9 @@ class BatchMaker:
         if self.bce:      # bce_text/main-end2end/run.py:224-237
             if self._neg_rng is None:
                 self._neg_rng = np.random.default_rng(self.neg_seed)
-            items, log_mask = collate_bce_batch(self.users_train, batch_users, self.item_content, self.S, self.item_num, self.use_modal, self._neg_rng)
-            return None, items, log_mask, None
+            out = collate_bce_batch(self.users_train, batch_users, self.item_content, self.S, self.item_num, self.use_modal, self._neg_rng,
+                                    with_ids=self.bce_ids)      # fusion towers: the ids travel with the content
+            return (out[0], out[1], out[2], None) if self.bce_ids else (None, out[0], out[1], None)
         ids, items, log_mask = collate_train_batch(self.users_train, batch_users, self.item_content, self.S, self.use_modal)
         pack = None
         if self.text_attrs:      # the collate's share of the unpadded token layout (no host sync in the step)
@@ -325,12 +327,18 @@ def synthetic_new_item_docs(args, item_num, n_new=12, seed=1357):
     return docs
 
 
+def _unwrap(model):
+    return model.module if hasattr(model, "module") else model
+
+
 def run_eval_special(model, item_content, catalogue, batch_size, item_num, use_modal, vision, args, local_rank):
     """``--mode test --cold_seqs ...``: the cold-start / new-item protocol of ``data_utils/special.py`` on the loaded checkpoint.  The
     new items' vectors come from the item tower over their content (text: ``get_doc_input_bert`` tables, vision: ``--new_lmdb_data``
     or ``--new_images_npy``); the ID tower has no vector for an unseen item and is evaluated on the cold users only (as the reference)."""
     from .data_utils import eval_model_special, get_doc_input_bert, read_behaviors_special
     t0 = time.time()
+    fusion = getattr(_unwrap(model), "fusion", None)
+    use_modal = use_modal and not fusion      # a fused vector needs an id row: a fusion tower is evaluated on the cold users only, like the ID tower
     new_seqs = args.new_seqs if use_modal else "None"
     if args.synthetic > 0:
         write_synthetic_special(args, item_num, vision)
@@ -348,7 +356,7 @@ def run_eval_special(model, item_content, catalogue, batch_size, item_num, use_m
         out = read_behaviors_special(args.cold_seqs, new_seqs, catalogue["item_name_to_id"], catalogue.get("before_item_id_to_dic"),
                                      catalogue.get("before_item_name_to_id"), Log, use_modal)
     seqs_cold, hist_cold, seqs_new, hist_new, new_content = out
-    item_embeddings = get_item_embeddings(model, item_content, batch_size, args, use_modal, local_rank)
+    item_embeddings = get_item_embeddings(model, item_content, batch_size, args, use_modal or bool(fusion), local_rank)
     new_embeddings = None
     if use_modal:
         n_new = len(new_content)
@@ -513,6 +521,7 @@ def train(args, use_modal, local_rank):
     if use_modal and not vision:
         _load_pretrained_text_tower(bert, args)
     bce = args.loss == "bce"
+    fusion = check_fusion_args(args) if use_modal else None
     if bce and (args.fused_step or vision):
         raise SystemExit("--loss bce runs on the drop-in autograd path with the text / ID towers (bce_text/main-end2end)")
     model = (BceModel(args, item_num, use_modal, bert) if bce else Model(args, item_num, use_modal, bert, pop)).to(local_rank)
@@ -587,7 +596,8 @@ def train(args, use_modal, local_rank):
     # host side of a batch: a picklable object over numpy tables and flags (no closure over the model / stepper)
     make_batch = BatchMaker(users, users_train, item_content, S, use_modal, bce=bce, item_num=item_num, neg_seed=777 + rank,
                             text_attrs=(stepper.text_attrs if (stepper is not None and use_modal and not vision) else None),
-                            pad_to=512 if (stepper is not None and stepper.graph) else 0, pin=False if n_workers > 0 else None)
+                            pad_to=512 if (stepper is not None and stepper.graph) else 0, pin=False if n_workers > 0 else None,
+                            bce_ids=bool(bce and fusion))
     loader, sampler = None, None
     if n_workers > 0:
         # T/run.py:111-124: DataLoader worker processes + its pin-memory thread; one "sample" = one whole collated batch.  ONE loader for
@@ -629,7 +639,10 @@ def train(args, use_modal, local_rank):
                 items, log_mask = items.to(local_rank, non_blocking=True), log_mask.to(local_rank, non_blocking=True)
                 items = items.view(-1, items.size(-1)) if use_modal else items.view(-1)
                 optimizer.zero_grad()
-                loss = wrapped(items, log_mask, local_rank)
+                if fusion:      # bce_text/id_plus_mo-end2end/run.py: ids and content
+                    loss = wrapped(ids.to(local_rank, non_blocking=True).view(-1), items, log_mask, local_rank)
+                else:
+                    loss = wrapped(items, log_mask, local_rank)
                 if scaler is not None:
                     scaler.scale(loss).backward()
                     scaler.step(optimizer)
@@ -722,6 +735,7 @@ def train(args, use_modal, local_rank):
 
 def main(argv=None):
     args = parse_args(argv)
+    check_fusion_args(args)
     logging.basicConfig(level=logging.INFO, format="[%(levelname)s %(asctime)s] %(message)s")
     local_rank = args.local_rank if args.local_rank >= 0 else int(os.environ.get("LOCAL_RANK", 0))
     if os.environ.get("MOREC_DEVICE_INDEX") is not None:      # several ranks on ONE device (functional tests of the N > 1 driver over gloo)

@@ -446,6 +446,30 @@ int morec_strided_rows_copy(const void* in, void* out, int R, int D, int in_row_
                             int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * ID (+) modality fusion of item vectors (bce_text/id_plus_mo-end2end: model/model.py:26-47, model/encoders.py:8-39): each item vector is
+ * fc(id_embedding(id), encoder(content)) with fc = ADD (x + y) or CAT (cat([x, y], 1) -> one or three Dropout -> Linear -> GELU layers).
+ * table: fp32 [n_rows, D]; idx: int32 [R]; content / out / a / dA / d_content: dtype.  D % 8 (16-bit) or D % 4 (fp32), else
+ * MOREC_E_ALIGN; p outside [0, 1): MOREC_E_ARG -- all before anything is launched.  Dropout is the counter-based stream of the LayerNorm
+ * kernels (element index = position in the matrix named below; morec_dropout_keep_mask exports it); masks are regenerated, never stored.
+ *   morec_fuse_add_fwd:  out[r] = T(table[idx[r]] + float(content[r])): one fp32 add, one rounding.  Row idx == 0 is gathered like any
+ *       other.  No backward kernel: d(content) = d(out), d(table) by morec_scatter_add_rows with pad_id = 0.
+ *   morec_fuse_cat_fwd:  a[r, 0:D] = drop(table[idx[r]]), a[r, D:2D] = drop(content[r]), one stream over the [R, 2D] matrix, kept values
+ *       times 1 / (1 - floor(p 2^16) / 2^16), rounded once; p = 0: gather + concatenation.  a feeds morec_gemm_nt (bias, GELU, aux).
+ *   morec_fuse_cat_bwd:  from dA [R, 2D] (that GEMM's input gradient) and the forward's (p, seed):
+ *       d_content[r] = mask . inv_keep . dA[r, D:2D] (dtype, overwritten);  d_table[idx[r]] += mask . inv_keep . dA[r, 0:D] (fp32, ADDED,
+ *       unrounded) unless idx[r] == pad_id.  fp32 atomics, or in the deterministic mode one writer wave per table row summing its source
+ *       rows in row order.
+ *   morec_dropout_apply: out[e] = keep(e) ? x[e] . inv_keep : 0 for e < n (out may alias x): the Dropouts between the layers of the
+ *       three-layer MLP, forward and (same p, seed) backward.
+ * ------------------------------------------------------------------------------------------ */
+int morec_fuse_add_fwd(const float* table, const int32_t* idx, const void* content, void* out, int R, int D, int dtype, void* stream);
+int morec_fuse_cat_fwd(const float* table, const int32_t* idx, const void* content, void* a_out, int R, int D, int dtype, float p,
+                       uint64_t seed, void* stream);
+int morec_fuse_cat_bwd(const void* dA, const int32_t* idx, void* d_content, float* d_table, int R, int D, int pad_id, int dtype,
+                       float p, uint64_t seed, void* stream);
+int morec_dropout_apply(const void* x, void* out, size_t n, float p, uint64_t seed, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-batch debiased sampled-softmax cross-entropy (T/model/model.py:32-33,45-67), fused:
  * logits never reach HBM.  P [Nr, D] user states (Nr = B*S rows), E [Nc, D] item vectors of the
  * column pool (local: Nc = B*(S+1); pooled over ranks: SURVEY.md §8e), both `dtype`.
