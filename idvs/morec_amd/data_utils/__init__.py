@@ -5,3 +5,5 @@ from .metrics import PackedEvalUsers, metrics_from_topk, recommend_packed, recom
 from .special import read_behaviors_special, eval_model_special  # noqa: F401
 from .utils import get_checkpoint, load_model, save_model  # noqa: F401
 from .images import DeviceImageFeed, LMDB_Image, LmdbImageStore, LmdbItemImages, PatchRows, decode_record, pack_images, resize_table  # noqa: F401
+from .dssm import read_behaviors as read_behaviors_dssm, BuildTrainDataset as DssmTrainDataset, eval_model as eval_model_dssm  # noqa: F401
+from .dssm import collate_dssm_batch, get_user_embeddings  # noqa: F401

@@ -204,6 +204,84 @@ class FusionFn(torch.autograd.Function):
         return (None, dc.view(in_shape), d_table, None) + tuple(grads)
 
 
+class MlpFn(torch.autograd.Function):
+    """``MLP_Encoder.forward`` of the DSSM package (``bce_text/main-end2end(DSSM)/model/encoders.py:6-41``): ``len(params) / 2`` triples of
+    Dropout -> Linear(D, D) -> GELU over the rows of ``x``.  ``cfg = (dtype, drop)``: the compute dtype and a ``DropCfg`` whose ``p_hidden``
+    is the drop rate (site l: the input of layer l); masks are regenerated from the seed in the backward.  ``params`` = (W1, b1, W2, b2, ...).
+    Built from the same ops as ``FusionFn``'s CAT branch."""
+
+    @staticmethod
+    def forward(ctx, x, cfg, *params):
+        dtype, drop = cfg
+        need = any(ctx.needs_input_grad)
+        a = x.contiguous().view(-1, x.shape[-1])
+        if a.dtype != dtype:
+            a = ops.cast(a, dtype)
+        p = float(drop.p_hidden)
+        n_layers = len(params) // 2
+        if params[0].shape[1] != a.shape[1]:
+            raise ValueError(f"mlp: the first Linear takes {params[0].shape[1]} inputs, the rows have {a.shape[1]}")
+        ctx.fp32_gemm = ops.FP32_GEMM
+        ctx.meta = (x.dtype, tuple(x.shape))
+        lin = [engine.prepare_linear(params[2 * l], dtype) for l in range(n_layers)]
+        acts, pres = [], []
+        for l in range(n_layers):
+            if p > 0:       # the layer's own Dropout, on its input (never on the caller's tensor)
+                a = ops.dropout_apply_(a.clone() if l == 0 and a.data_ptr() == x.data_ptr() else a, p, drop.site(l))
+            pre = torch.empty((a.shape[0], lin[l].w.shape[0]), device=a.device, dtype=dtype) if need else None
+            h = ops.gemm_nt(a, lin[l].w, bias=params[2 * l + 1], act=ops.ACT_GELU, aux_out=pre)
+            acts.append(a)
+            pres.append(pre)
+            a = h
+        ctx.stuff = (lin, acts, pres, p, drop) if need else None
+        return a.view(tuple(x.shape[:-1]) + (a.shape[1],))
+
+    @staticmethod
+    def backward(ctx, dout):
+        in_dtype, in_shape = ctx.meta
+        (lin, acts, pres, p, drop), ctx.stuff = ctx.stuff, None
+        d = dout.contiguous().view(-1, dout.shape[-1])
+        grads = []
+        with ops.fp32_gemm_mode(ctx.fp32_gemm):
+            for l in reversed(range(len(lin))):
+                dv = ops.act_bwd(d, pres[l], ops.ACT_GELU)
+                db = torch.zeros(dv.shape[1], device=dv.device, dtype=torch.float32)
+                dw = torch.zeros(lin[l].w.shape, device=dv.device, dtype=torch.float32)
+                ops.colsum_(dv, db)
+                engine.linear_wgrad_(dv, acts[l], dw)
+                grads = [dw, db] + grads
+                d = ops.gemm_nt(dv, lin[l].wt, K=dv.shape[1], N=acts[l].shape[1])
+                if p > 0:       # the mask the forward put on this layer's input
+                    ops.dropout_apply_(d, p, drop.site(l))
+            engine.WgradStream.join(dout.device)
+        if d.dtype != in_dtype:
+            d = ops.cast(d, in_dtype)
+        return (d.view(in_shape), None) + tuple(grads)
+
+
+class DssmBceFn(torch.autograd.Function):
+    """The DSSM scoring loss (``bce_text/main-end2end(DSSM)/model/model.py:40-42``): U [B, D] user vectors, E [B * n1, D] item vectors,
+    ``labels`` fp32 [B * n1] (or None: [1, 0, ..., 0] per user) -> the mean of BCEWithLogits over all B * n1 scores.
+    ``morec_dssm_bce_fwd`` / ``morec_dssm_bce_bwd``."""
+
+    @staticmethod
+    def forward(ctx, U, E, labels, B, n1):
+        U, E = U.contiguous(), E.contiguous()
+        if labels is not None:
+            labels = labels.reshape(-1).to(torch.float32).contiguous()
+        scores, _, loss_sum = ops.dssm_bce_fwd(U, E, labels, B, n1)
+        ctx.stuff = (U, E, labels, scores, B, n1)
+        return (loss_sum[0] / (B * n1)).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        U, E, labels, scores, B, n1 = ctx.stuff
+        ctx.stuff = None
+        g = (dloss.to(torch.float32) / (B * n1)).reshape(1).contiguous()
+        dU, dE = ops.dssm_bce_bwd(U, E, labels, scores, g, B, n1)
+        return dU, dE, None, None, None
+
+
 def _all_gather_cat(t: torch.Tensor, world: int, comm=None) -> torch.Tensor:
     if comm is not None:       # morec_comm_all_gather: RCCL on the compute stream (comm.MorecComm)
         return comm.all_gather(t)

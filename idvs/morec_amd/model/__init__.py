@@ -3,3 +3,4 @@ from .encoders import ADD, CAT, Bert_Encoder, IdEmbedding, Text_Encoder, User_En
 from .bert import HipBertModel  # noqa: F401
 from .spec import BertShape  # noqa: F401
 from .bce import BceModel  # noqa: F401  (drop-in for bce_text/main-end2end/model/model.py)
+from .dssm import DssmModel, MLP_Encoder  # noqa: F401  (drop-in for bce_text/main-end2end(DSSM)/model/model.py)

@@ -650,6 +650,48 @@ def bce_bwd(P, E, row_valid, scores, gscale_dev, B, S):
     return dP, dE
 
 
+def dssm_bce_fwd(U, E, labels, B, n1, *, out=None):
+    """DSSM scoring loss (``morec_dssm_bce_fwd``): U [B, D], E [B * n1, D], ``labels`` fp32 [B * n1] or None for [1, 0, ..., 0] per user.
+    Returns fp32 ``(scores [B * n1], terms [B * n1], loss_sum [1])``; ``out`` = caller-provided tensors in that order (every element is
+    written, so ``torch.empty`` is enough)."""
+    _dev(U), _dev(E)
+    R, D = B * n1, U.shape[-1]
+    if tuple(U.shape) != (B, D) or tuple(E.shape) != (R, D) or E.dtype != U.dtype:
+        raise _lib.MorecError(f"dssm_bce_fwd: U {tuple(U.shape)} {U.dtype} / E {tuple(E.shape)} {E.dtype} do not fit B = {B}, n1 = {n1}")
+    if labels is not None and (_dev(labels).dtype != torch.float32 or labels.numel() != R):
+        raise _lib.MorecError(f"dssm_bce_fwd: labels must be fp32 with {R} elements")
+    if out is None:
+        out = (torch.empty(R, device=U.device, dtype=torch.float32), torch.empty(R, device=U.device, dtype=torch.float32),
+               torch.empty(1, device=U.device, dtype=torch.float32))
+    scores, terms, loss_sum = out
+    for t, n in ((scores, R), (terms, R), (loss_sum, 1)):
+        if _dev(t).dtype != torch.float32 or t.numel() != n:
+            raise _lib.MorecError("dssm_bce_fwd: out = (scores [R], terms [R], loss_sum [1]) in fp32")
+    check(_lib.lib().morec_dssm_bce_fwd(_p(U), _p(E), _p(labels), _p(scores), _p(terms), _p(loss_sum), B, n1, D, code(U.dtype), _stream()),
+          "morec_dssm_bce_fwd")
+    return scores, terms, loss_sum
+
+
+def dssm_bce_bwd(U, E, labels, scores, gscale_dev, B, n1, *, out=None):
+    """``morec_dssm_bce_bwd``: returns ``(dU, dE)`` in the dtype of U / E; ``gscale_dev`` fp32 [1] on the device (dloss / R); ``out`` =
+    caller-provided ``(dU, dE)``."""
+    _dev(U), _dev(E), _dev(scores), _dev(gscale_dev)
+    if labels is not None and (_dev(labels).dtype != torch.float32 or labels.numel() != B * n1):
+        raise _lib.MorecError(f"dssm_bce_bwd: labels must be fp32 with {B * n1} elements")
+    if gscale_dev.dtype != torch.float32 or gscale_dev.numel() < 1:
+        raise _lib.MorecError("dssm_bce_bwd: gscale_dev must be an fp32 device tensor")
+    if out is None:
+        out = (torch.empty_like(U), torch.empty_like(E))
+    dU, dE = out
+    if _dev(dU).shape != U.shape or _dev(dE).shape != E.shape or dU.dtype != U.dtype or dE.dtype != E.dtype or E.dtype != U.dtype:
+        raise _lib.MorecError("dssm_bce_bwd: out = (dU like U, dE like E)")
+    if tuple(U.shape) != (B, U.shape[-1]) or E.shape[0] != B * n1 or scores.numel() != B * n1 or scores.dtype != torch.float32:
+        raise _lib.MorecError(f"dssm_bce_bwd: shapes do not fit B = {B}, n1 = {n1}")
+    check(_lib.lib().morec_dssm_bce_bwd(_p(U), _p(E), _p(labels), _p(scores), _p(gscale_dev), _p(dU), _p(dE), B, n1, U.shape[-1],
+                                        code(U.dtype), _stream()), "morec_dssm_bce_bwd")
+    return dU, dE
+
+
 def adamw_(param, grad, exp_avg, exp_avg_sq, shadow, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):
     check(_lib.lib().morec_adamw(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), _p(shadow), param.numel(), lr, beta1,
                                  beta2, eps, wd, step, grad_scale, _stream()), "morec_adamw")

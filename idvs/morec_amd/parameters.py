@@ -15,6 +15,12 @@ def build_parser():
     p.add_argument("--item_tower", type=str, default="id", choices=ITEM_TOWERS,
                    help="id | modal, or ID (+) modality fusion (bce_text/id_plus_mo-end2end): modal_add = id vector + content vector, "
                         "modal_cat / modal_cat_3 = their concatenation through one / three Dropout-Linear-GELU layers")
+    p.add_argument("--arch", type=str, default="sasrec", choices=["sasrec", "dssm"],
+                   help="sasrec = the sequential user encoder (everything as before); dssm = the two-tower model of "
+                        "bce_text/main-end2end(DSSM): user-id embedding + MLP against 1 + neg_num sampled items per (user, item) pair, "
+                        "BCE loss; --item_tower id | modal (text), autograd path; --loss is not consulted")
+    p.add_argument("--neg_num", type=int, default=1, help="--arch dssm: sampled negatives per (user, item) pair")
+    p.add_argument("--dnn_layers", type=int, default=0, help="--arch dssm: Dropout-Linear-GELU layers of the user MLP and of the ID tower's item MLP")
     p.add_argument("--root_data_dir", type=str, default="../")
     p.add_argument("--dataset", type=str, default="MIND-small")
     p.add_argument("--behaviors", type=str, default="behaviors_l5_tr_v.tsv")
@@ -115,6 +121,30 @@ def check_fusion_args(args):
         raise SystemExit(f"--item_tower {args.item_tower}: a new item has no row in the id table, so the fused vector fc(id, content) "
                          "does not exist for it; --new_seqs is not available with a fusion tower (--cold_seqs alone is)")
     return kind
+
+
+def check_dssm_args(args):
+    """What ``--arch dssm`` does not run with: exits with the reason (before anything touches a device).  True for a DSSM run."""
+    if getattr(args, "arch", "sasrec") != "dssm":
+        return False
+    why = None
+    if getattr(args, "fused_step", False) or getattr(args, "graph", False):
+        why = "--fused_step / --graph (train_step.TrainStep) cover the SASRec models only; DSSM trains on the autograd path"
+    elif getattr(args, "pool_negatives", False):
+        why = "--pool_negatives pools in-batch negatives; DSSM samples its negatives per pair (--neg_num)"
+    elif getattr(args, "mode", "train") == "recommend":
+        why = "--mode recommend builds its lists from the sequential user encoder; there is no DSSM form of it"
+    elif getattr(args, "cold_seqs", "None") != "None" or getattr(args, "new_seqs", "None") != "None":
+        why = "--cold_seqs / --new_seqs evaluate users through their item sequence; a DSSM user is a row of the user table"
+    elif args.item_tower not in ("id", "modal"):
+        why = f"--item_tower {args.item_tower}: the ID (+) modality fusion towers belong to the SASRec models; DSSM takes id | modal"
+    elif getattr(args, "CV_model_load", "None") != "None":
+        why = "--CV_model_load: a vision item tower is not built for DSSM (text tower: --item_tower modal with --bert_model_load)"
+    elif args.neg_num < 0 or args.dnn_layers < 0:
+        why = "--neg_num and --dnn_layers must be >= 0"
+    if why:
+        raise SystemExit("--arch dssm (DSSM two-tower model): " + why)
+    return True
 
 
 def parse_args(argv=None):

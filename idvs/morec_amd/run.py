@@ -27,10 +27,10 @@ from torch.nn.parallel import DistributedDataParallel as DDP
 
 from .data_utils import (collate_bce_batch, collate_train_batch, epoch_batches, eval_model, get_checkpoint, get_item_embeddings,
                          load_model, read_behaviors, read_news, save_model)
-from .model import BceModel, BertShape, HipBertModel, Model
+from .model import BceModel, BertShape, DssmModel, HipBertModel, Model
 from .model.swin import HipSwinForImageClassification
 from .swin_engine import SwinShape
-from .parameters import check_fusion_args, parse_args
+from .parameters import check_dssm_args, check_fusion_args, parse_args
 from . import engine
 from .train_step import TrainStep
 
@@ -733,8 +733,192 @@ def train(args, use_modal, local_rank):
     return best
 
 
+def dssm_model_dir(args):
+    """The checkpoint directory of the reference's DSSM driver (``bce_text/main-end2end(DSSM)/run.py:307-319``), under ``--checkpoint_root``."""
+    modal = "modal" in args.item_tower
+    load = args.bert_model_load if modal else "id"
+    dir_label = f"{args.item_tower}_{load}_freeze_{args.freeze_paras_before}" if modal else str(args.item_tower)
+    label = (f"{load}_dnn_{args.dnn_layers}_bs_{args.batch_size}_ed_{args.embedding_dim}_lr_{args.lr}_L2_{args.l2_weight}"
+             f"_dp_{args.drop_rate}_Flr_{args.fine_tune_lr}")
+    return os.path.join(args.checkpoint_root, "checkpoint_" + dir_label, "cpt_" + label)
+
+
+def run_eval_dssm(model, item_content, user_history, eval_pairs, batch_size, user_num, item_num, use_modal, args, mode, local_rank):
+    """``run_eval`` of the DSSM driver (``run.py:262-270`` there): both tables, then the ranking kernel over the eval pairs."""
+    from .data_utils import dssm as dd
+    t0 = time.time()
+    user_embeddings = dd.get_user_embeddings(model, user_num, batch_size, args, local_rank)
+    item_embeddings = dd.get_item_embeddings(model, item_content, batch_size, args, use_modal, local_rank)
+    hit10 = dd.eval_model(model, user_history, eval_pairs, user_embeddings, item_embeddings, batch_size, args, item_num, Log, mode, local_rank)
+    Log.info("eval %.1f s, Hit10 %.5f" % (time.time() - t0, hit10 * 100))
+    return hit10
+
+
+def train_dssm(args, use_modal, local_rank):
+    """``--arch dssm``: the driver of ``bce_text/main-end2end(DSSM)/run.py`` around ``DssmModel`` -- (user, item) training pairs with
+    ``--neg_num`` sampled negatives, AdamW (two parameter groups with a text tower), GradScaler for fp16, validation every
+    ``steps_for_test`` steps with early stopping, a checkpoint ``epoch-<N>-<label>.pt`` (the reference's keys) whenever the validation
+    Hit@10 improves and at the end, then the test split.  ``--mode test --load_ckpt_name ...`` evaluates a checkpoint on the test split.
+    As in the reference, the save at the end carries the label of the last improvement, so it REPLACES that file with the final weights
+    (``run.py:251-253`` there).  Evaluation runs in chunks of 512 rows, the constant ``train()`` and the reference use.  The negatives come
+    from a numpy generator seeded from the run's seed (``torch.initial_seed()``), the rank and the epoch -- a resumed run draws the
+    epoch's negatives it would have drawn.  This is a loop of its own beside ``train()``: that one iterates users and steps once per
+    sequence batch, this one iterates pairs, validates inside the epoch and names its files differently; they share the loaders of
+    pretrained weights, ``epoch_batches``, ``BatchPrefetcher`` and ``load_model``."""
+    from .data_utils import dssm as dd
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    S, T = args.max_seq_len, args.num_words_title
+    if hasattr(args, "CV_model_load"):
+        del args.CV_model_load
+    if args.synthetic > 0:
+        extra_T = [w for n, w in (("abstract", args.num_words_abstract), ("body", args.num_words_body)) if use_modal and n in args.news_attributes]
+        item_num, content, tr, _, te, _, _, _ = synthetic_dataset(args.synthetic, args.synthetic_items, S, T,
+                                                                 full_len=bool(getattr(args, "synthetic_full_len", False)), extra_T=extra_T)
+        seqs = [list(tr[u]) + list(te[u][-2:]) for u in range(args.synthetic)]      # the raw sequences (at most S + 3 items), split by the DSSM rule
+        users_train, _, train_pairs, valid_pairs, test_pairs, hist_valid, hist_test = dd.pairs_from_sequences(seqs)
+        user_num = len(seqs)
+        item_content = content if use_modal else np.arange(item_num + 1)
+    elif use_modal:
+        from transformers import BertTokenizer
+        from .data_utils import get_doc_input_bert, read_news_bert
+        tok_dir = os.path.join(args.pretrained_dir, args.bert_model_load)
+        if not os.path.exists(os.path.join(tok_dir, "vocab.txt")):
+            raise SystemExit(f"modal run on real data: no tokenizer vocabulary under {tok_dir} (--pretrained_dir / --bert_model_load)")
+        a, b, _ = read_news_bert(os.path.join(args.root_data_dir, args.dataset, args.news), args, BertTokenizer.from_pretrained(tok_dir))
+        user_num, item_num, id2content, users_train, _, train_pairs, valid_pairs, test_pairs, hist_valid, hist_test = dd.read_behaviors(
+            os.path.join(args.root_data_dir, args.dataset, args.behaviors), a, b, args.min_seq_len, S, Log)
+        item_content = np.concatenate([x for x in get_doc_input_bert(id2content, args) if x is not None], axis=1)
+    else:
+        a, b, _ = read_news(os.path.join(args.root_data_dir, args.dataset, args.news))
+        user_num, item_num, _, users_train, _, train_pairs, valid_pairs, test_pairs, hist_valid, hist_test = dd.read_behaviors(
+            os.path.join(args.root_data_dir, args.dataset, args.behaviors), a, b, args.min_seq_len, S, Log)
+        item_content = np.arange(item_num + 1)
+    bert = None
+    if use_modal:
+        shape = BertShape.named(args.bert_model_load)
+        args.word_embedding_dim = shape.hidden_size
+        bert = HipBertModel(shape)
+        for index, (name, param) in enumerate(bert.named_parameters()):
+            if index < args.freeze_paras_before or name in ("pooler.dense.weight", "pooler.dense.bias"):
+                param.requires_grad = False
+        _load_pretrained_text_tower(bert, args)
+    model = DssmModel(args, user_num, item_num, use_modal, bert).to(local_rank)
+    model_dir = dssm_model_dir(args)
+    ckpt, start_epoch, is_early_stop = None, 0, True
+    if "None" not in args.load_ckpt_name:
+        ckpt_path = get_checkpoint(model_dir, args.load_ckpt_name)
+        if ckpt_path is None:
+            raise SystemExit(f"--load_ckpt_name {args.load_ckpt_name}: not found under {model_dir}")
+        start_epoch = load_model(model, ckpt_path)
+        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=False)
+        if ckpt.get("rng_state") is not None:
+            torch.set_rng_state(ckpt["rng_state"])
+        if ckpt.get("cuda_rng_state") is not None and torch.cuda.is_available():
+            torch.cuda.set_rng_state(ckpt["cuda_rng_state"])
+        if ckpt.get("morec_drop_calls") is not None:
+            model._drop_calls = int(ckpt["morec_drop_calls"])
+        is_early_stop = False
+        Log.info("model loaded from %s (epoch %d)" % (ckpt_path, start_epoch))
+    if args.mode == "test":
+        if ckpt is None:
+            raise SystemExit("--mode test needs --load_ckpt_name epoch-N-<label>.pt")
+        return run_eval_dssm(model, item_content, hist_test, test_pairs, 512, user_num, item_num, use_modal, args, "test", local_rank)
+    wrapped = DDP(model, device_ids=[local_rank], output_device=local_rank, find_unused_parameters=True) if world > 1 else model
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    # run.py:139-180 of the DSSM package: the text tower's own learning rate, one weight decay for both groups
+    groups = [{"params": [p for n, p in named if "bert_model" in n], "lr": args.fine_tune_lr, "weight_decay": args.l2_weight},
+              {"params": [p for n, p in named if "bert_model" not in n], "lr": args.lr, "weight_decay": args.l2_weight}]
+    optimizer = optim.AdamW([g for g in groups if g["params"]])
+    if ckpt is not None and ckpt.get("optimizer") is not None:
+        optimizer.load_state_dict(ckpt["optimizer"])
+    scaler = torch.amp.GradScaler("cuda", enabled=True) if args.compute_dtype in ("fp16", "fp16_res32") else None
+    if scaler is not None and ckpt is not None and ckpt.get("scaler_state"):
+        scaler.load_state_dict(ckpt["scaler_state"])
+    step_num = int(np.ceil(len(train_pairs) / world / args.batch_size))
+    steps_for_log = max(1, int(step_num / max(1, args.logging_num)))
+    steps_for_test = max(1, int(step_num / max(1, args.testing_num)))
+    Log.info("dssm: %d users, %d items, %d train pairs; %d steps/epoch, a log every %d steps, a validation every %d" %
+             (user_num, item_num, len(train_pairs), step_num, steps_for_log, steps_for_test))
+    keys = dd.history_keys(users_train, item_num)
+    neg = {"rng": None}      # re-seeded per epoch (below); read by the one thread that builds the batches
+    make_batch = lambda idx: dd.collate_dssm_batch(users_train, train_pairs[idx], item_content, item_num, args.neg_num, use_modal, neg["rng"], keys=keys)
+    depth = int(getattr(args, "prefetch", 2))
+
+    def save(now_epoch, label):
+        if rank != 0:
+            return
+        os.makedirs(model_dir, exist_ok=True)
+        path = os.path.join(model_dir, f"epoch-{now_epoch}-{label}.pt")
+        torch.save({"model_state_dict": model.state_dict(), "optimizer": optimizer.state_dict(), "rng_state": torch.get_rng_state(),
+                    "cuda_rng_state": torch.cuda.get_rng_state() if torch.cuda.is_available() else None,
+                    "scaler_state": scaler.state_dict() if scaler is not None else {}, "morec_drop_calls": int(model._drop_calls)}, path)
+        Log.info(f"Model saved to {path}")
+
+    best, max_epoch, early_stop_epoch, early_stop_count, step, need_break = 0.0, 0, args.epoch, 0, 0, False
+    now_epoch, save_label = start_epoch, "0"
+    for ep in range(1, args.epoch + 1):
+        now_epoch = start_epoch + ep
+        model.train()
+        batches = epoch_batches(len(train_pairs), args.batch_size, world, rank, now_epoch)
+        neg["rng"] = np.random.default_rng([torch.initial_seed() % (1 << 63), rank, now_epoch])
+        feeder = BatchPrefetcher(make_batch, batches, depth) if depth > 0 else None
+        source = feeder if feeder is not None else ((b_, make_batch(idx_)) for b_, idx_ in enumerate(batches))
+        t0, loss_acc, n_done = time.time(), None, 0
+        for b, (input_user, sample_items, bce_label) in source:
+            input_user, sample_items, bce_label = (input_user.to(local_rank, non_blocking=True), sample_items.to(local_rank, non_blocking=True),
+                                                   bce_label.to(local_rank, non_blocking=True))
+            optimizer.zero_grad()
+            loss = wrapped(input_user, sample_items, bce_label)
+            if scaler is not None:
+                scaler.scale(loss).backward()
+                scaler.step(optimizer)
+                scaler.update()
+            else:
+                loss.backward()
+                optimizer.step()
+            loss_acc = loss.detach() if loss_acc is None else loss_acc + loss.detach()
+            step += 1
+            n_done = b + 1
+            if n_done % steps_for_log == 0:
+                bl = float(loss.detach())
+                if bl != bl:
+                    Log.info("NaN loss, stopping")
+                    need_break = True
+                    break
+                Log.info("step %d (%d pairs): batch loss %.5f, mean loss %.5f" % (n_done, n_done * args.batch_size, bl, float(loss_acc) / n_done))
+            if n_done % steps_for_test == 0:
+                hit10 = run_eval_dssm(wrapped, item_content, hist_valid, valid_pairs, 512, user_num, item_num, use_modal, args, "valid", local_rank)
+                if hit10 > best:
+                    best, max_epoch, early_stop_count = hit10, now_epoch, 0
+                    save_label = str(n_done // steps_for_test)
+                    save(now_epoch, save_label)
+                else:
+                    early_stop_count += 1
+                    if early_stop_count > 10:
+                        need_break = is_early_stop
+                        early_stop_epoch = now_epoch
+                model.train()
+            if need_break or (args.max_steps and step >= args.max_steps):
+                break
+        if feeder is not None:
+            feeder.close()
+        torch.cuda.synchronize()
+        Log.info("epoch %d: %d steps, mean loss %.5f, %.1f pairs/s" % (now_epoch, n_done, float(loss_acc) / max(1, n_done) if loss_acc is not None else 0.0,
+                                                                    sum(len(x) for x in batches[:n_done]) * world / max(time.time() - t0, 1e-9)))
+        if need_break or (args.max_steps and step >= args.max_steps):
+            break
+    if args.max_steps and step >= args.max_steps and step % steps_for_test != 0:      # a run cut short still reports a validation
+        best = max(best, run_eval_dssm(wrapped, item_content, hist_valid, valid_pairs, 512, user_num, item_num, use_modal, args, "valid", local_rank))
+    save(now_epoch, save_label)
+    run_eval_dssm(wrapped, item_content, hist_test, test_pairs, 512, user_num, item_num, use_modal, args, "test", local_rank)
+    Log.info("max eval Hit10 %.5f in epoch %d; early stop in epoch %d" % (best * 100, max_epoch, early_stop_epoch))
+    return best
+
+
 def main(argv=None):
     args = parse_args(argv)
+    dssm = check_dssm_args(args)
     check_fusion_args(args)
     logging.basicConfig(level=logging.INFO, format="[%(levelname)s %(asctime)s] %(message)s")
     local_rank = args.local_rank if args.local_rank >= 0 else int(os.environ.get("LOCAL_RANK", 0))
@@ -749,7 +933,7 @@ def main(argv=None):
     use_modal = "modal" in args.item_tower
     if dist.is_initialized() and dist.get_rank() != 0:
         Log.setLevel(logging.WARNING)
-    best = train(args, use_modal, local_rank)
+    best = (train_dssm if dssm else train)(args, use_modal, local_rank)
     Log.info("max eval Hit10 %.5f" % (best * 100))
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -418,6 +418,23 @@ int morec_bce_bwd(const void* P, const void* E, const uint8_t* row_valid, const 
                   void* dE, int B, int S, int D, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DSSM two-tower scoring loss (bce_text/main-end2end(DSSM)/model/model.py): every user vector against its own 1 + neg_num sampled items.
+ * n1 = 1 + neg_num, R = B * n1.  U [B, D] and E [R, D] in dtype (user b owns the rows b*n1 .. b*n1 + n1 - 1); labels fp32 [R], any
+ * values in [0, 1], or NULL for [1, 0, ..., 0] per user.  fp32 outputs: scores[r] = U[r / n1] . E[r], terms[r] = softplus(s) - y s,
+ * loss_sum[0] = sum_r terms[r] (overwritten, not accumulated; the caller divides by R for the BCEWithLogitsLoss mean).
+ * Backward: gscale[0] = dloss / R on the device; c_r = g (sigmoid(s_r) - y_r), dE[r] = c_r U[r / n1], dU[b] = sum_j c_{b,j} E[b, j].
+ * Few users with many rows each: the backward cuts a user's rows into segments, keeps their fp32 partial dU in library-owned scratch and
+ * adds them in segment order in a second launch.
+ * No atomics: every element of scores, terms, loss_sum, dU and dE is written exactly once and every sum has a fixed order -- the same
+ * bits on every run, in either setting of the deterministic mode.  D % 4 != 0 or a row base off 16 bytes: MOREC_E_ALIGN; null pointers
+ * (labels excepted), B, n1 or D < 1: MOREC_E_ARG; all before anything is launched.
+ * ------------------------------------------------------------------------------------------ */
+int morec_dssm_bce_fwd(const void* U, const void* E, const float* labels, float* scores, float* terms, float* loss_sum, int B, int n1,
+                       int D, int dtype, void* stream);
+int morec_dssm_bce_bwd(const void* U, const void* E, const float* labels, const float* scores, const float* gscale, void* dU, void* dE,
+                       int B, int n1, int D, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Embeddings
  * ------------------------------------------------------------------------------------------ */
 /* BERT embeddings: z = word[ids[m]] + pos[m % T] + type0;  y = LN(z)  (HF BertEmbeddings). */
