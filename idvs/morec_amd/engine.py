@@ -530,8 +530,10 @@ def bert_needs_grad_buffer(name: str, grad_from: int, prefix: str = TE) -> bool:
 
 def bert_forward(p: dict, prep, text: torch.Tensor, heads: int, dtype, need_grad: bool, eps: float = 1e-12,
                  mask_value: float = ops.FLT_MIN_MASK, prefix: str = TE, drop: DropCfg = NO_DROP, unpad: bool | None = None,
-                 grad_from: int = -1, packing=None, on_use=None, res32: bool = False):
+                 grad_from: int = -1, packing=None, on_use=None, res32: bool = False, features_only: bool = False):
     """text int64 [Nc, 2T] = [input_ids | attention_mask] (T/model/encoders.py:63-67) -> item vectors [Nc, D].
+    ``features_only``: return ``(cls [Nc, H], None)``, the [CLS] rows in front of ``fc`` -- what the two-stage packages' ``Text_Encoder``
+    returns (stage 1 of two-stage training, ``data_utils.two_stage``).
 
     ``unpad``: run the encoder layers on the REAL tokens only (packed rows + ``cu_seqlens``) instead of all T positions of
     every title.  Exact for what the path consumes (``hidden[:, 0]``, encoders.py:69): [PAD] keys carry the additive
@@ -603,6 +605,8 @@ def bert_forward(p: dict, prep, text: torch.Tensor, heads: int, dtype, need_grad
     if n_layers == 0:
         x16 = x[0] if res32 else x
         cls = ops.strided_rows_copy(x16, torch.empty((Nc, H), device=x16.device, dtype=dtype), Nc, H, T, 1)
+    if features_only:
+        return cls, None
     if on_use is not None:
         on_use("head")
     D = prep["fc"].w.shape[0]

@@ -259,6 +259,54 @@ class MlpFn(torch.autograd.Function):
         return (d.view(in_shape), None) + tuple(grads)
 
 
+class FeatProjFn(torch.autograd.Function):
+    """The first layer of the two-stage item tower over a FROZEN feature table (``bce_text/main-2stage(SASRec)/model/encoders.py:29-30``:
+    ``activate(fc(item_content[ids]))``, with the reference's host-side lookup ``data_utils/dataset.py:39`` folded in):
+    ``GELU(table[ids] @ W^T + b)``.  ``table`` [n_rows, Kw] in the compute dtype ``dtype``, ``ids`` any integer tensor.  Forward:
+    ``ops.featproj_fwd`` (one launch) where ``ops.featproj_supported`` says so, else ``ops.featproj_composed`` (fp32 modes, odd widths,
+    ``MOREC_FEATPROJ=1``).  Backward: act', column sums, the looked-up rows materialised on the weight-gradient stream, the weight-gradient
+    GEMM -- and NO input-gradient GEMM: the table receives no gradient."""
+
+    @staticmethod
+    def forward(ctx, ids, table, dtype, weight, bias):
+        need = any(ctx.needs_input_grad)
+        idx = ids.reshape(-1).to(torch.int32).contiguous()
+        if table.dtype != dtype or table.dim() != 2 or not table.is_contiguous():
+            raise ValueError(f"featproj: the feature table must be a contiguous {dtype} matrix, got {table.dtype} {tuple(table.shape)}")
+        if weight.shape[1] != table.shape[1]:
+            raise ValueError(f"featproj: fc takes {weight.shape[1]} inputs, the feature table has {table.shape[1]} columns")
+        w = weight.contiguous() if weight.dtype == dtype else ops.cast(weight.contiguous(), dtype)
+        ctx.fp32_gemm = ops.FP32_GEMM
+        if ops.featproj_supported(idx.numel(), table.shape[1], w.shape[0], dtype):
+            out, pre = ops.featproj_fwd(table, idx, w, bias, need_pre=need)
+        else:
+            out, pre, _ = ops.featproj_composed(table, idx, w, bias, need_pre=need)
+        ctx.stuff = (idx, table, pre, tuple(weight.shape)) if need else None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (idx, table, pre, wshape), ctx.stuff = ctx.stuff, None
+        d = dout.contiguous().view(idx.numel(), -1)
+        dev = d.device
+        with ops.fp32_gemm_mode(ctx.fp32_gemm):
+            dv = ops.act_bwd(d, pre, ops.ACT_GELU)
+            db = torch.zeros(dv.shape[1], device=dev, dtype=torch.float32)
+            dw = torch.zeros(wshape, device=dev, dtype=torch.float32)
+            ops.colsum_(dv, db)
+            # (the side stream exactly where linear_wgrad_ launches on it: 16-bit operands with whole 16-byte rows)
+            side = engine.WgradStream.get(dev) if (ops.is16(dv.dtype) and dv.shape[1] % 8 == 0 and table.shape[1] % 8 == 0) else None
+            if side is None:
+                x = ops.indexed_rows_copy(table, torch.empty((idx.numel(), table.shape[1]), device=dev, dtype=table.dtype), in_idx=idx)
+            else:       # X[idx] is read by the weight gradient alone: gathered on ITS stream (which waits for the main one first)
+                ops.stream_wait_stream(side.cuda_stream)
+                with torch.cuda.stream(side):
+                    x = ops.indexed_rows_copy(table, torch.empty((idx.numel(), table.shape[1]), device=dev, dtype=table.dtype), in_idx=idx)
+            engine.linear_wgrad_(dv, x, dw)
+            engine.WgradStream.join(dev)
+        return None, None, None, dw, db
+
+
 class DssmBceFn(torch.autograd.Function):
     """The DSSM scoring loss (``bce_text/main-end2end(DSSM)/model/model.py:40-42``): U [B, D] user vectors, E [B * n1, D] item vectors,
     ``labels`` fp32 [B * n1] (or None: [1, 0, ..., 0] per user) -> the mean of BCEWithLogits over all B * n1 scores.

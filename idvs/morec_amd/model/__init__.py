@@ -4,3 +4,4 @@ from .bert import HipBertModel  # noqa: F401
 from .spec import BertShape  # noqa: F401
 from .bce import BceModel  # noqa: F401  (drop-in for bce_text/main-end2end/model/model.py)
 from .dssm import DssmModel, MLP_Encoder  # noqa: F401  (drop-in for bce_text/main-end2end(DSSM)/model/model.py)
+from .two_stage import MLP_Layers, TwoStageModel  # noqa: F401  (drop-in for bce_text|bce_vision/main-2stage(SASRec)/model/model.py)

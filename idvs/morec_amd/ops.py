@@ -595,6 +595,47 @@ def indexed_rows_copy(src, out, in_idx=None, out_idx=None, R=None):
     return out
 
 
+def featproj_supported(R, Kw, D, dtype) -> bool:
+    """Does the first layer of the two-stage tower run as ``featproj_fwd`` for this shape (``morec_featproj_supported``: 16-bit,
+    ``Kw % 8 == D % 8 == 0``, the knob ``MOREC_FEATPROJ`` / ``set_featproj`` and, when that is automatic, ``R Kw D <= 2^29``: the sizes at
+    which one launch measured faster than two, ``profiles/two_stage_step.txt``)?  Otherwise it is ``featproj_composed``."""
+    return is16(dtype) and bool(_lib.lib().morec_featproj_supported(int(R), int(Kw), int(D), code(dtype)))
+
+
+def set_featproj(mode: int):
+    """The knob of ``featproj_supported``: 0 automatic | 1 never | 2 wherever the rules allow (``morec_tuning_set("featproj", mode)``)."""
+    check(_lib.lib().morec_tuning_set(b"featproj", int(mode)), "morec_tuning_set(featproj)")
+
+
+def featproj_fwd(table, idx32, w, bias=None, *, need_pre=False, out=None, pre=None, R=None):
+    """``GELU(table[idx] @ w^T + bias)`` in ONE launch (``morec_featproj_fwd``): ``table`` [n_rows, Kw] and ``w`` [D, Kw] in the same 16-bit
+    dtype, ``idx32`` int32 [R] (clamped into the table by the kernel), ``bias`` fp32 [D] or None.  Returns ``(out, pre)``; ``pre`` (the
+    pre-activation, for the backward) is None unless ``need_pre`` or a buffer is given.  Rows past ``R`` of a given buffer stay untouched."""
+    _dev(table), _dev(w)
+    R = idx32.numel() if R is None else R
+    n_rows, Kw = table.shape
+    D = w.shape[0]
+    assert table.is_contiguous() and w.is_contiguous() and idx32.is_contiguous() and idx32.dtype == torch.int32
+    assert w.dtype == table.dtype and w.shape[1] == Kw, "featproj: table and weight must share the 16-bit dtype and the feature width"
+    if out is None:
+        out = torch.empty((R, D), device=table.device, dtype=table.dtype)
+    if pre is None and need_pre:
+        pre = torch.empty((R, D), device=table.device, dtype=table.dtype)
+    check(_lib.lib().morec_featproj_fwd(_p(table), _p(idx32), _p(w), _p(bias), _p(out), _p(pre), R, n_rows, Kw, D, code(table.dtype),
+                                        _stream()), "morec_featproj_fwd")
+    return out, pre
+
+
+def featproj_composed(table, idx32, w, bias=None, *, need_pre=False):
+    """The same layer as two launches, in any dtype: ``indexed_rows_copy`` of the looked-up rows, then ``gemm_nt`` with the bias + GELU
+    epilogue.  Returns ``(out, pre, x)`` with ``x`` the gathered rows [R, Kw] (the weight gradient's operand)."""
+    R = idx32.numel()
+    x = indexed_rows_copy(table, torch.empty((R, table.shape[1]), device=table.device, dtype=table.dtype), in_idx=idx32)
+    pre = torch.empty((R, w.shape[0]), device=table.device, dtype=table.dtype) if need_pre else None
+    out = gemm_nt(x, w, bias=bias, act=ACT_GELU, aux_out=pre)
+    return out, pre, x
+
+
 def strided_rows_copy(src, out, R, D, in_stride, out_stride):
     check(_lib.lib().morec_strided_rows_copy(_p(src), _p(out), R, D, in_stride, out_stride, code(src.dtype), _stream()),
           "morec_strided_rows_copy")

@@ -3,6 +3,7 @@ what ROCm / torchrun need: ``--news`` (read by ``T/run.py:79,100`` but never dec
 launcher spelling), and the MI355X-path switches."""
 import argparse
 import os
+import sys
 
 
 ITEM_TOWERS = ("id", "modal", "modal_add", "modal_cat", "modal_cat_3")
@@ -15,12 +16,18 @@ def build_parser():
     p.add_argument("--item_tower", type=str, default="id", choices=ITEM_TOWERS,
                    help="id | modal, or ID (+) modality fusion (bce_text/id_plus_mo-end2end): modal_add = id vector + content vector, "
                         "modal_cat / modal_cat_3 = their concatenation through one / three Dropout-Linear-GELU layers")
-    p.add_argument("--arch", type=str, default="sasrec", choices=["sasrec", "dssm"],
+    p.add_argument("--arch", type=str, default="sasrec", choices=["sasrec", "dssm", "two_stage"],
                    help="sasrec = the sequential user encoder (everything as before); dssm = the two-tower model of "
                         "bce_text/main-end2end(DSSM): user-id embedding + MLP against 1 + neg_num sampled items per (user, item) pair, "
-                        "BCE loss; --item_tower id | modal (text), autograd path; --loss is not consulted")
+                        "BCE loss; --item_tower id | modal (text), autograd path; --loss is not consulted; two_stage = "
+                        "bce_text|bce_vision/main-2stage(SASRec): the item tower runs once over the catalogue (or --features_npy supplies its "
+                        "features), an MLP over the frozen feature rows + SASRec + BCE are trained; --item_tower modal, autograd path")
     p.add_argument("--neg_num", type=int, default=1, help="--arch dssm: sampled negatives per (user, item) pair")
     p.add_argument("--dnn_layers", type=int, default=0, help="--arch dssm: Dropout-Linear-GELU layers of the user MLP and of the ID tower's item MLP")
+    p.add_argument("--dnn_layer", type=int, default=0, help="--arch two_stage: Dropout-Linear-GELU layers behind fc (the reference's spelling)")
+    p.add_argument("--features_npy", type=str, default="None", help="--arch two_stage: fp16 / fp32 [item_num + 1, W] item features from any "
+                   "encoder (row 0 = padding item); skips stage 1")
+    p.add_argument("--save_features", type=str, default="None", help="--arch two_stage: write the feature table stage 1 extracted to this .npy file")
     p.add_argument("--root_data_dir", type=str, default="../")
     p.add_argument("--dataset", type=str, default="MIND-small")
     p.add_argument("--behaviors", type=str, default="behaviors_l5_tr_v.tsv")
@@ -147,7 +154,34 @@ def check_dssm_args(args):
     return True
 
 
+def check_two_stage_args(args):
+    """What ``--arch two_stage`` does not run with: exits with the reason (before anything touches a device).  True for a two-stage run."""
+    if getattr(args, "arch", "sasrec") != "two_stage":
+        return False
+    why = None
+    if getattr(args, "fused_step", False):
+        why = "--fused_step (train_step.TrainStep) covers the end-to-end SASRec models only; two-stage trains on the autograd path"
+    elif getattr(args, "graph", False):
+        why = "--graph replays the fused step (train_step.TrainStep), which two-stage does not use"
+    elif getattr(args, "pool_negatives", False):
+        why = "--pool_negatives pools in-batch negatives; two-stage samples one negative per position (BCE)"
+    elif getattr(args, "new_seqs", "None") != "None":
+        why = "--new_seqs needs the item tower over the new items' content; after stage 1 only the feature table exists (--cold_seqs alone is available)"
+    elif args.item_tower != "modal":
+        why = (f"--item_tower {args.item_tower}: two-stage trains on frozen MODALITY features (--item_tower modal); the ID (+) modality fusion "
+               "towers over frozen features (id_plus_mo-2stage) are not built")
+    elif getattr(args, "loss", "bce") == "inbatch" and getattr(args, "loss_given", False):
+        why = "--loss inbatch: the two-stage packages train with the one-sampled-negative BCE loss only"
+    elif args.dnn_layer < 0:
+        why = "--dnn_layer must be >= 0"
+    if why:
+        raise SystemExit("--arch two_stage (two-stage training on frozen item features): " + why)
+    return True
+
+
 def parse_args(argv=None):
     args = build_parser().parse_args(argv)
     args.news_attributes = args.news_attributes.split(",")
+    # --loss defaults to inbatch; --arch two_stage (BCE only) has to tell the default from a request
+    args.loss_given = any(a == "--loss" or a.startswith("--loss=") for a in (sys.argv[1:] if argv is None else argv))
     return args

@@ -30,7 +30,7 @@ from .data_utils import (collate_bce_batch, collate_train_batch, epoch_batches, 
 from .model import BceModel, BertShape, DssmModel, HipBertModel, Model
 from .model.swin import HipSwinForImageClassification
 from .swin_engine import SwinShape
-from .parameters import check_dssm_args, check_fusion_args, parse_args
+from .parameters import check_dssm_args, check_fusion_args, check_two_stage_args, parse_args
 from . import engine
 from .train_step import TrainStep
 
@@ -455,15 +455,10 @@ def _load_pretrained_text_tower(bert, args):
     return False
 
 
-def train(args, use_modal, local_rank):
-    world = dist.get_world_size() if dist.is_initialized() else 1
-    rank = dist.get_rank() if dist.is_initialized() else 0
-    if args.mode == "recommend":
-        check_topk(args.topk)
+def load_dataset(args, use_modal, vision):
+    """The data of a SASRec-family run -- ``--synthetic N``, the text tables (tokenizer), the vision catalogue (LMDB) or the bare ids -- as
+    ``(item_num, item_content, users_train, users_valid, users_test, hist_valid, hist_test, pop, catalogue)``."""
     S, T = args.max_seq_len, args.num_words_title
-    vision = use_modal and args.CV_model_load != "None"
-    if not vision and hasattr(args, "CV_model_load"):
-        del args.CV_model_load                # `Model` picks the vision tower by the presence of this attribute (V/model/model.py:24-29)
     if args.synthetic > 0:
         extra_T = [w for n, w in (("abstract", args.num_words_abstract), ("body", args.num_words_body))
                    if use_modal and not vision and n in args.news_attributes]
@@ -504,6 +499,19 @@ def train(args, use_modal, local_rank):
             os.path.join(args.root_data_dir, args.dataset, args.behaviors), a, b, c, S, args.min_seq_len, Log)
         item_content = np.arange(item_num + 1)
         catalogue = dict(item_name_to_id=name_to_id)
+    return item_num, item_content, users_train, users_valid, users_test, hist_valid, hist_test, pop, catalogue
+
+
+def train(args, use_modal, local_rank):
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    if args.mode == "recommend":
+        check_topk(args.topk)
+    S, T = args.max_seq_len, args.num_words_title
+    vision = use_modal and args.CV_model_load != "None"
+    if not vision and hasattr(args, "CV_model_load"):
+        del args.CV_model_load                # `Model` picks the vision tower by the presence of this attribute (V/model/model.py:24-29)
+    item_num, item_content, users_train, users_valid, users_test, hist_valid, hist_test, pop, catalogue = load_dataset(args, use_modal, vision)
     bert = None
     if vision:
         bert = HipSwinForImageClassification(SwinShape.named(args.CV_model_load), args.embedding_dim)   # V/run.py:47-54
@@ -916,8 +924,177 @@ def train_dssm(args, use_modal, local_rank):
     return best
 
 
+def two_stage_model_dir(args):
+    """The checkpoint directory of the two-stage drivers (``bce_text/main-2stage(SASRec)/run.py:242-252``, the vision package alike), under
+    ``--checkpoint_root``: ``checkpoint_<item_tower>_<model>/cpt_<item_tower>_<model>[_mlp_<dnn_layer>]_bs_..._Flr_...``."""
+    cv = getattr(args, "CV_model_load", "None")
+    load = args.bert_model_load if cv == "None" else cv
+    mlp = f"_mlp_{args.dnn_layer}" if args.dnn_layer != 0 else ""
+    label = (f"{args.item_tower}_{load}{mlp}_bs_{args.batch_size}_ed_{args.embedding_dim}_lr_{args.lr}_L2_{args.l2_weight}"
+             f"_dp_{args.drop_rate}_Flr_{args.fine_tune_lr}")
+    return os.path.join(args.checkpoint_root, f"checkpoint_{args.item_tower}_{load}", "cpt_" + label)
+
+
+def two_stage_features(args, item_content, item_num, vision, local_rank, rank):
+    """Stage 1 of ``--arch two_stage``: the frozen item tower once over the catalogue (``data_utils.extract_item_features``) -> fp32
+    [item_num + 1, W] on the device; ``--save_features`` writes it (rank 0).  The tower is dropped afterwards."""
+    from .data_utils import extract_item_features
+    from .model.encoders import Bert_Encoder, Vit_Encoder, resolve_dtype
+    t0 = time.time()
+    if vision:
+        tower = Vit_Encoder(image_net=HipSwinForImageClassification(SwinShape.named(args.CV_model_load), args.embedding_dim),
+                            compute_dtype=resolve_dtype(args))
+    else:
+        shape = BertShape.named(args.bert_model_load)
+        args.word_embedding_dim = shape.hidden_size
+        bert = HipBertModel(shape)
+        _load_pretrained_text_tower(bert, args)
+        tower = Bert_Encoder(args=args, bert_model=bert)
+    table = extract_item_features(tower.to(local_rank), item_content, 512, local_rank)
+    del tower
+    Log.info("two-stage: stage 1 -- %d x %d item features in %.1f s" % (table.shape[0], table.shape[1], time.time() - t0))
+    if args.save_features != "None" and rank == 0:
+        np.save(args.save_features, table.cpu().numpy())
+        Log.info(f"two-stage: features written to {args.save_features}")
+    assert table.shape[0] == item_num + 1
+    return table
+
+
+def train_two_stage(args, use_modal, local_rank):
+    """``--arch two_stage``: the driver of ``bce_text/main-2stage(SASRec)/run.py`` (and its vision twin) around ``TwoStageModel``.  Stage 1
+    runs the frozen tower once (or ``--features_npy`` supplies the table); a step is then ids -> ``fc`` over looked-up feature rows ->
+    SASRec -> BCE.  One AdamW over ALL parameters (``lr``, ``l2_weight``: ``run.py:124`` there), GradScaler for fp16, a validation per
+    epoch with early stopping, ``epoch-N.pt`` (the reference's keys) whenever the validation Hit@10 improves and once more at the end
+    (``run.py:182-190``).  ``--mode test`` (with ``--cold_seqs``) and ``--mode recommend`` evaluate a checkpoint through the same catalogue
+    paths as ``train()``: the catalogue is ``fc`` over the feature table.  Multi-GPU goes through DDP and is unmeasured."""
+    from .data_utils import collate_two_stage_batch, load_feature_table
+    from .model import TwoStageModel
+    from .model.encoders import resolve_dtype
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    if args.mode == "recommend":
+        check_topk(args.topk)
+    S = args.max_seq_len
+    have = args.features_npy != "None"
+    vision = args.CV_model_load != "None"
+    model_dir = two_stage_model_dir(args)
+    if not vision:
+        del args.CV_model_load
+    # with a feature file no content is read at all (bare ids, like the ID tower)
+    item_num, item_content, users_train, users_valid, users_test, hist_valid, hist_test, _, catalogue = load_dataset(
+        args, not have, vision and not have)
+    if have:
+        table = load_feature_table(args.features_npy, item_num, resolve_dtype(args), local_rank)
+    else:
+        table = two_stage_features(args, item_content, item_num, vision, local_rank, rank)
+    del item_content
+    model = TwoStageModel(args, item_num, num_fc_ftr=int(table.shape[1])).to(local_rank)
+    model.set_feature_table(table)
+    table = model.feature_table
+    users = list(users_train.keys())
+    ckpt, start_epoch, is_early_stop = None, 0, True
+    if "None" not in args.load_ckpt_name:
+        ckpt_path = get_checkpoint(model_dir, args.load_ckpt_name)
+        if ckpt_path is None:
+            raise SystemExit(f"--load_ckpt_name {args.load_ckpt_name}: not found under {model_dir}")
+        start_epoch = load_model(model, ckpt_path)
+        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=False)
+        if ckpt.get("rng_state") is not None:
+            torch.set_rng_state(ckpt["rng_state"])
+        if ckpt.get("cuda_rng_state") is not None and torch.cuda.is_available():
+            torch.cuda.set_rng_state(ckpt["cuda_rng_state"])
+        if ckpt.get("morec_drop_calls") is not None:
+            model._drop_calls = int(ckpt["morec_drop_calls"])
+        is_early_stop = False
+        Log.info("model loaded from %s (epoch %d)" % (ckpt_path, start_epoch))
+    if args.mode == "test":
+        if ckpt is None:
+            raise SystemExit("--mode test needs --load_ckpt_name epoch-N.pt")
+        hit10 = run_eval(model, table, hist_test, users_test, 512, item_num, True, args, "test", local_rank)
+        if getattr(args, "cold_seqs", "None") != "None":      # cold users only: a new item has no row in the feature table
+            if args.synthetic > 0:
+                catalogue = dict(item_name_to_id={synthetic_item_name(i, False): i for i in range(1, item_num + 1)})
+            run_eval_special(model, table, catalogue, 512, item_num, False, False, args, local_rank)
+        return hit10
+    if args.mode == "recommend":
+        if ckpt is None:
+            raise SystemExit("--mode recommend needs --load_ckpt_name epoch-N.pt")
+        out_path = args.recommend_out if args.recommend_out != "None" else os.path.join(model_dir, "recommend_top%d.tsv" % args.topk)
+        run_recommend(model, table, users_test, catalogue, 512, True, args, out_path, local_rank)
+        return 0.0
+    wrapped = DDP(model, device_ids=[local_rank], output_device=local_rank) if world > 1 else model
+    optimizer = optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.l2_weight)
+    if ckpt is not None and ckpt.get("optimizer") is not None:
+        optimizer.load_state_dict(ckpt["optimizer"])
+    scaler = torch.amp.GradScaler("cuda", enabled=True) if args.compute_dtype in ("fp16", "fp16_res32") else None
+    if scaler is not None and ckpt is not None and ckpt.get("scaler_state"):
+        scaler.load_state_dict(ckpt["scaler_state"])
+    neg = {"rng": None}      # re-seeded per epoch; read by the one thread that builds the batches
+    make_batch = lambda idx: collate_two_stage_batch(users_train, [users[i] for i in idx], S, item_num, neg["rng"])
+    depth = int(getattr(args, "prefetch", 2))
+    Log.info("two-stage: %d users, %d items, features %d wide in %s, dnn_layer %d" %
+             (len(users), item_num, table.shape[1], str(table.dtype).replace("torch.", ""), args.dnn_layer))
+
+    def save(now_epoch):
+        if rank == 0:
+            save_model(now_epoch, model, model_dir, optimizer, torch.get_rng_state(),
+                       torch.cuda.get_rng_state() if torch.cuda.is_available() else None, scaler, Log,
+                       extra={"morec_drop_calls": int(model._drop_calls)})
+
+    best, step, max_epoch, early_stop_epoch, early_stop_count, now_epoch = 0.0, 0, 0, args.epoch, 0, start_epoch
+    for ep in range(1, args.epoch + 1):
+        now_epoch = start_epoch + ep
+        model.train()
+        batches = epoch_batches(len(users), args.batch_size, world, rank, now_epoch)
+        neg["rng"] = np.random.default_rng([torch.initial_seed() % (1 << 63), rank, now_epoch])
+        feeder = BatchPrefetcher(make_batch, batches, depth) if depth > 0 else None
+        source = feeder if feeder is not None else ((b_, make_batch(idx_)) for b_, idx_ in enumerate(batches))
+        t0, loss_acc, n_done = time.time(), None, 0
+        for b, (ids, log_mask) in source:
+            ids, log_mask = ids.to(local_rank, non_blocking=True), log_mask.to(local_rank, non_blocking=True)
+            optimizer.zero_grad()
+            loss = wrapped(ids, log_mask, local_rank)
+            if scaler is not None:
+                scaler.scale(loss).backward()
+                scaler.step(optimizer)
+                scaler.update()
+            else:
+                loss.backward()
+                optimizer.step()
+            loss_acc = loss.detach() if loss_acc is None else loss_acc + loss.detach()
+            step += 1
+            n_done = b + 1
+            if args.max_steps and step >= args.max_steps:
+                break
+        if feeder is not None:
+            feeder.close()
+        torch.cuda.synchronize()
+        mean_loss = float(loss_acc) / max(1, n_done) if loss_acc is not None else 0.0
+        if mean_loss != mean_loss:
+            Log.info("NaN loss, stopping")
+            break
+        Log.info("epoch %d: %d steps, mean loss %.5f, %.1f user-seq/s" %
+                 (now_epoch, n_done, mean_loss, sum(len(x) for x in batches[:n_done]) * world / max(time.time() - t0, 1e-9)))
+        hit10 = run_eval(wrapped, table, hist_valid, users_valid, 512, item_num, True, args, "valid", local_rank)
+        need_break = False
+        if hit10 > best:
+            best, max_epoch, early_stop_count = hit10, now_epoch, 0
+            save(now_epoch)
+        else:
+            early_stop_count += 1
+            if early_stop_count > 10:
+                need_break = is_early_stop
+                early_stop_epoch = now_epoch
+        if need_break or (args.max_steps and step >= args.max_steps):
+            break
+    save(now_epoch)      # run.py:189-190 of the two-stage packages: the final weights, whatever the validation said
+    Log.info("max eval Hit10 %.5f in epoch %d; early stop in epoch %d" % (best * 100, max_epoch, early_stop_epoch))
+    return best
+
+
 def main(argv=None):
     args = parse_args(argv)
+    two_stage = check_two_stage_args(args)
     dssm = check_dssm_args(args)
     check_fusion_args(args)
     logging.basicConfig(level=logging.INFO, format="[%(levelname)s %(asctime)s] %(message)s")
@@ -933,7 +1110,7 @@ def main(argv=None):
     use_modal = "modal" in args.item_tower
     if dist.is_initialized() and dist.get_rank() != 0:
         Log.setLevel(logging.WARNING)
-    best = (train_dssm if dssm else train)(args, use_modal, local_rank)
+    best = (train_two_stage if two_stage else train_dssm if dssm else train)(args, use_modal, local_rank)
     Log.info("max eval Hit10 %.5f" % (best * 100))
     if dist.is_initialized():
         dist.destroy_process_group()

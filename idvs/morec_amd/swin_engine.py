@@ -131,9 +131,11 @@ def _window_of(H, W, ws, shift):
 
 
 def swin_forward(p: dict, prep, shape: SwinShape, pixels: torch.Tensor, dtype, need_grad: bool, prefix: str = IN,
-                 drop: DropCfg = NO_DROP, training: bool = False):
+                 drop: DropCfg = NO_DROP, training: bool = False, features_only: bool = False):
     """pixels fp32 [n_img, 3, R, R] (normalised, as V/run.py:201-204 uploads) or uint8 [n_img, R, R, 3] (decoded) -> item vectors [n_img, D] (``GELU(classifier(pool(LN(encoder(embed(x))))))``).
-    ``training``: apply DropPath with the rates of ``shape.drop_path_rates()`` and the streams of ``drop``."""
+    ``training``: apply DropPath with the rates of ``shape.drop_path_rates()`` and the streams of ``drop``.
+    ``features_only``: return ``(pooled [n_img, num_features], None)``, the reference's ``image_net(x)[1]`` in front of the classifier (stage 1
+    of two-stage training, ``data_utils.two_stage``)."""
     sw = prefix + "swin."
     n_img = pixels.shape[0]
     eps = shape.layer_norm_eps
@@ -201,6 +203,8 @@ def swin_forward(p: dict, prep, shape: SwinShape, pixels: torch.Tensor, dtype, n
     xf, z_last, mean_f, rstd_f = ops.layernorm_fwd(f, p[sw + "layernorm.weight"], p[sw + "layernorm.bias"], eps, bias=b2, res=h,
                                                    z_inplace=True)
     pooled = ops.swin_pool_fwd(xf, n_img, H * W)
+    if features_only:
+        return pooled, None
     D = prep["cls"].w.shape[0]
     pre_c = torch.empty((n_img, D), device=x.device, dtype=dtype) if need_grad else None
     item = ops.gemm_nt(pooled, prep["cls"].w, bias=p[prefix + "classifier.bias"], act=ACT_GELU, aux_out=pre_c)

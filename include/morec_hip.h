@@ -93,6 +93,9 @@ int morec_version(void);
  *                        output, 288 < N <= 768, 32 <= K <= 192.  With 1 or 2 morec_mlp_dact_recompute_supported() answers 0;
  *   "ce8p"               0 automatic | 1 always the 128 x 128 kernels | 2 wherever the shapes allow    MOREC_CE8P                0
  *                        scoring kernels on 256 x 256 eight-phase tiles (16-bit, D > 64, D % 8 == Nc % 8 == (B S) % 8 == 0);
+ *   "featproj"           0 automatic | 1 never | 2 wherever the rules allow                            MOREC_FEATPROJ            0
+ *                        the fused gather + first projection of the two-stage tower (morec_featproj_fwd; 16-bit, Kw % 8 == D % 8 == 0).
+ *                        Automatic: R Kw D <= 2^29 (morec_featproj_supported);
  *   "gemm8p_tmr"         0 always 256-row tiles | 1 automatic | 224 | 192 (other values: 1)            MOREC_GEMM8P_TMR          1
  *   "gemm8p_ngroup"      tile order: -1 automatic column groups | 0 row-major | n groups of n N-tiles  MOREC_GEMM8P_NGROUP       -1
  *   "gemm8p_reserve_cus" 0..128 CUs (multiple of 8) left out of the persistent grid for a concurrent RCCL kernel   MOREC_GEMM8P_RESERVE_CUS   0
@@ -485,6 +488,28 @@ int morec_fuse_cat_fwd(const float* table, const int32_t* idx, const void* conte
 int morec_fuse_cat_bwd(const void* dA, const int32_t* idx, void* d_content, float* d_table, int R, int D, int pad_id, int dtype,
                        float p, uint64_t seed, void* stream);
 int morec_dropout_apply(const void* x, void* out, size_t n, float p, uint64_t seed, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Two-stage training on frozen item features (bce_text/main-2stage(SASRec), bce_vision/main-2stage(SASRec): model/encoders.py MLP_Layers.fc
+ * over rows of a precomputed feature table, which the reference gathers on the host, data_utils/dataset.py BuildTrainDataset).  The first
+ * layer with the gather folded in, one launch (csrc/featproj.hip):
+ *     out[r, :] = GELU(table[idx[r], :] . W^T + b),   pre[r, :] = table[idx[r], :] . W^T + b,   r < R
+ * table [n_rows, Kw] and W [D, Kw]: the same 16-bit dtype, contiguous;  idx int32 [R];  b fp32 [D] or NULL;  out, and pre unless NULL,
+ * [R, D] in dtype.  fp32 accumulation on v_mfma_f32_16x16x32_{f16,bf16}, erf GELU (MOREC_ACT_GELU) on the fp32 sum, one rounding per
+ * output.  One writer per element and no atomics: the same bits on every run.  Rows >= R and columns >= D are never written.  idx values
+ * are clamped into [0, n_rows) inside the kernel, so a bad id never reads outside the table (the data layer validates ids on the host).
+ * Checked in this order, before anything touches the device: R, n_rows, Kw or D < 1: MOREC_E_ARG;  fp32 (or an unknown dtype):
+ * MOREC_E_DTYPE -- the fp32, fp32x3 and *_res32 first layers are morec_indexed_rows_copy + morec_gemm_nt;  Kw % 8 or D % 8:
+ * MOREC_E_ALIGN (loads and stores are whole 16- / 8-byte lanes; Kw % 32 != 0 is legal, the K tail is zero-filled in registers);
+ * a null table, idx, W or out: MOREC_E_ARG;  a base pointer off 16 bytes: MOREC_E_ALIGN.
+ * morec_featproj_supported: 1 where the library's callers should take this kernel instead of the two-launch composition.  Knob
+ * "featproj" (MOREC_FEATPROJ): 0 automatic | 1 never | 2 wherever the rules above allow.  Automatic: where the rules allow and
+ * R Kw D <= 2^29 -- measured (profiles/two_stage_step.txt): ahead of the composition up to 1344 x 768 x 512 and at every R with
+ * Kw = 128, D = 64; behind it at 5376 x 768 x 512 (39 us against 21 us), where each wave re-reads its operand rows through L2.
+ * ------------------------------------------------------------------------------------------ */
+int morec_featproj_fwd(const void* table, const int32_t* idx, const void* W, const float* bias, void* out, void* pre, int R, int n_rows,
+                       int Kw, int D, int dtype, void* stream);
+int morec_featproj_supported(int R, int Kw, int D, int dtype);
 
 /* ------------------------------------------------------------------------------------------
  * In-batch debiased sampled-softmax cross-entropy (T/model/model.py:32-33,45-67), fused:
