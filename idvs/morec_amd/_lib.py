@@ -119,6 +119,9 @@ _SIGS = {
     "morec_dropout_apply": (C.c_int, [_P, _P, C.c_size_t, C.c_float, C.c_uint64, C.c_int, _P]),
     "morec_featproj_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "morec_featproj_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "morec_featfuse_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64,
+                                     _P]),
+    "morec_featfuse_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "morec_inbatch_ce_workspace_bytes":(C.c_size_t, [C.POINTER(CeDesc)]),
     "morec_inbatch_ce_fwd": (C.c_int, [C.POINTER(CeDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "morec_inbatch_ce_bwd": (C.c_int, [C.POINTER(CeDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, _P, _P, _P,

@@ -9,85 +9,19 @@
 // k-steps: a lane's two loads of a row are one 128-byte line between the four lanes that share the row); the loads of step s + 1 are issued
 // into a second register set before the MFMAs of step s.  Rows >= R and columns >= D are loaded from a clamped (valid) address and never
 // stored; k >= Kw is zero-filled in registers; idx is clamped into [0, n_rows).  One writer per element, no atomics: the same bits every run.
-#include "common.hpp"
+// The main loop lives in featproj_core.hpp, shared with featfuse.hip.
+#include "featproj_core.hpp"
 
 namespace {
-constexpr int FP_TR = 64, FP_TC = 64;      // rows x columns of a workgroup's tile
-constexpr int FP_KU = 2;                   // MFMA k-steps (32 elements) per K step
-
-struct FpFrags {
-    bf16x8_t w[2][FP_KU], x[2][FP_KU];
-};
-
-struct FpRows {      // this lane's two W rows and two (looked-up) table rows
-    const bf16* w[2];
-    const bf16* x[2];
-};
-// the fragments of K step s: element offset k = 64 s + 32 u + 8 q of this lane's rows.  The address is always a valid one (k clamped to
-// the last whole vector of the row); what lies past Kw is replaced by zeros AFTER the load, so no load is guarded.
-__device__ __forceinline__ void fp_load(FpFrags& f, const FpRows& rows, int s, int q, int Kw) {
-    const bf16x8_t zero = {};
-#pragma unroll
-    for (int u = 0; u < FP_KU; ++u) {
-        const int k = s * (32 * FP_KU) + u * 32 + q * 8;
-        const bool in = k < Kw;
-        const int kc = in ? k : Kw - 8;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const bf16x8_t wv = *reinterpret_cast<const bf16x8_t*>(rows.w[i] + kc);
-            const bf16x8_t xv = *reinterpret_cast<const bf16x8_t*>(rows.x[i] + kc);
-            f.w[i][u] = in ? wv : zero;
-            f.x[i][u] = in ? xv : zero;
-        }
-    }
-}
-
-template <typename T16>
-__device__ __forceinline__ void fp_mma(f32x4_t (&acc)[2][2], const FpFrags& f) {
-#pragma unroll
-    for (int u = 0; u < FP_KU; ++u)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[i][j] = h16<T16>::mma16(f.w[j][u], f.x[i][u], acc[i][j]);
-}
-
 template <typename T16>
 __global__ __launch_bounds__(256) void featproj_fwd_kernel(const T16* __restrict__ table, const int32_t* __restrict__ idx,
                                                            const T16* __restrict__ W, const float* __restrict__ bias, T16* __restrict__ out,
                                                            T16* __restrict__ pre, int R, int n_rows, int Kw, int D) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c16 = lane & 15, q = lane >> 4;
-    const int ctiles = (D + FP_TC - 1) / FP_TC;                // column tiles vary fastest: neighbouring workgroups share their table rows
-    const int r0 = (blockIdx.x / ctiles) * FP_TR + (wave >> 1) * 32;      // this wave's 32 rows
-    const int d0 = (blockIdx.x % ctiles) * FP_TC + (wave & 1) * 32;       // and 32 columns
-    // operand rows of this lane: W rows d0 + 16 j + c16 (first operand), table rows idx[r0 + 16 i + c16] (second operand)
-    FpRows rows;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int d = min(d0 + 16 * i + c16, D - 1);
-        const int r = min(r0 + 16 * i + c16, R - 1);
-        const int id = min(max(idx[r], 0), n_rows - 1);
-        rows.w[i] = reinterpret_cast<const bf16*>(W) + (size_t)d * Kw;
-        rows.x[i] = reinterpret_cast<const bf16*>(table) + (size_t)id * Kw;
-    }
+    const FpTile t = fp_tile(D);
+    const int r0 = t.r0, d0 = t.d0, c16 = t.c16, q = t.q;
     f32x4_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-    const int KS = (Kw + 32 * FP_KU - 1) / (32 * FP_KU);
-    FpFrags fa, fb;
-    fp_load(fa, rows, 0, q, Kw);
-    int s = 0;
-    for (; s + 2 <= KS; s += 2) {      // two K steps per trip: both register sets have compile-time names
-        fp_load(fb, rows, s + 1, q, Kw);
-        fp_mma<T16>(acc, fa);
-        fp_load(fa, rows, min(s + 2, KS - 1), q, Kw);      // the last trip re-reads a step it does not use
-        fp_mma<T16>(acc, fb);
-    }
-    if (s < KS) fp_mma<T16>(acc, fa);
+    int ids[2];
+    fp_accumulate<T16>(acc, ids, t, table, idx, W, R, n_rows, Kw, D);
 
     // accumulator (i, j), register e: output row r0 + 16 i + c16, column d0 + 16 j + 4 q + e (D % 8 == 0: the four columns are in or out together)
 #pragma unroll

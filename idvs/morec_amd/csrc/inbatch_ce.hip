@@ -441,7 +441,8 @@ extern "C" int morec_inbatch_ce_bwd(const morec_ce_desc* d, const void* P, const
 namespace {
 __device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
 
-template <typename T>
+// DET (the deterministic mode): the rows only store their scores; bce_loss_total_kernel adds their loss terms up in a fixed order
+template <typename T, bool DET>
 __global__ __launch_bounds__(256) void bce_fwd_kernel(const T* __restrict__ P, const T* __restrict__ E,
                                                       const uint8_t* __restrict__ row_valid, float* __restrict__ scores,
                                                       float* __restrict__ loss_sum, int B, int S, int D) {
@@ -463,8 +464,25 @@ __global__ __launch_bounds__(256) void bce_fwd_kernel(const T* __restrict__ P, c
     if (lane == 0) {
         scores[row] = sp;
         scores[B * S + row] = sn;
-        if (row_valid[row]) atomicAdd(loss_sum, softplus_f(-sp) + softplus_f(sn));
+        if (!DET && row_valid[row]) atomicAdd(loss_sum, softplus_f(-sp) + softplus_f(sn));
     }
+}
+
+// loss_sum += the loss terms of the valid rows, from the stored scores: one block, fixed summation tree (ce_loss_total_kernel's) ->
+// bit-identical totals from run to run, where the atomics above add the same terms in the order the waves happen to finish
+__global__ __launch_bounds__(256) void bce_loss_total_kernel(const float* __restrict__ scores, const uint8_t* __restrict__ row_valid, int BS,
+                                                             float* __restrict__ loss_sum) {
+    __shared__ float s[256];
+    float a = 0.f;
+    for (int r = threadIdx.x; r < BS; r += 256)
+        if (row_valid[r]) a += softplus_f(-scores[r]) + softplus_f(scores[BS + r]);
+    s[threadIdx.x] = a;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *loss_sum += s[0];
 }
 
 // dpos = -sigmoid(-pos) g, dneg = sigmoid(neg) g on valid rows (g = dloss / n_valid), 0 elsewhere
@@ -518,12 +536,18 @@ extern "C" int morec_bce_fwd(const void* P, const void* E, const uint8_t* row_va
     if (D % 4) return MOREC_E_ALIGN;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     dim3 grid((B * S + 3) / 4);
+    const bool det = morec_deterministic();
     if (!by_dtype(dtype, [&](auto* t) {
             using T = MOREC_TAG_T(t);
-            hipLaunchKernelGGL((bce_fwd_kernel<T>), grid, dim3(256), 0, s, (const T*)P, (const T*)E, row_valid, scores, loss_sum, B, S, D);
+            if (det) hipLaunchKernelGGL((bce_fwd_kernel<T, true>), grid, dim3(256), 0, s, (const T*)P, (const T*)E, row_valid, scores, loss_sum, B, S, D);
+            else hipLaunchKernelGGL((bce_fwd_kernel<T, false>), grid, dim3(256), 0, s, (const T*)P, (const T*)E, row_valid, scores, loss_sum, B, S, D);
         }))
         return MOREC_E_DTYPE;
     MOREC_CHECK_LAUNCH();
+    if (det) {
+        hipLaunchKernelGGL(bce_loss_total_kernel, dim3(1), dim3(256), 0, s, scores, row_valid, B * S, loss_sum);
+        MOREC_CHECK_LAUNCH();
+    }
     return MOREC_OK;
 }
 

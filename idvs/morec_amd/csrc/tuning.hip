@@ -33,6 +33,7 @@ const Row ROWS[] = {
     {"gemm_skinny", "MOREC_GEMM_SKINNY", &Tuning::gemm_skinny, 0, RAW},
     {"ce8p", "MOREC_CE8P", &Tuning::ce8p, 0, RAW},
     {"featproj", "MOREC_FEATPROJ", &Tuning::featproj, 0, RAW},
+    {"featfuse", "MOREC_FEATFUSE", &Tuning::featfuse, 0, RAW},
     {"gemm8p_tmr", "MOREC_GEMM8P_TMR", &Tuning::gemm8p_tmr, 1, TMR},
     {"gemm8p_ngroup", "MOREC_GEMM8P_NGROUP", &Tuning::gemm8p_ngroup, -1, RAW},
     {"gemm8p_reserve_cus", "MOREC_GEMM8P_RESERVE_CUS", &Tuning::gemm8p_reserve_cus, 0, RESERVE},

@@ -7,6 +7,7 @@
 struct Tuning {
     // kernel selection: 0 = automatic, 1 = never, 2 = wherever eligible (gemm_skinny 2: gemm_skinny only, no gemm_skinny_wide / recompute)
     int gemm8p, gemm2w, gemm_small, gemm_skinny, ce8p;
+    int featfuse;              // the fused gather + projection + ID fusion of the id-two-stage tower (featfuse.hip): same values as featproj
     int featproj;              // the fused gather + first projection of the two-stage tower (featproj.hip): 0 automatic | 1 never | 2 wherever the rules allow
     // gemm8p launch parameters
     int gemm8p_tmr;            // tile height: 0 = always 256, 1 = automatic, 224 / 192 = forced where an instantiation exists

@@ -26,7 +26,9 @@ def get_item_embeddings(model, item_content, test_batch_size, args, use_modal, l
     fp32x3: the encoders called on their own would otherwise fall back to the exact-fp32 MFMA)."""
     model.eval()
     if hasattr(_module(model), "feature_table"):      # two-stage model: ``item_content`` is the frozen feature table, the catalogue is fc over it
-        from .two_stage import get_item_embeddings_two_stage
+        from .two_stage import get_item_embeddings_id_two_stage, get_item_embeddings_two_stage
+        if hasattr(_module(model), "id_embedding"):      # IdTwoStageModel: the catalogue is the fused tower over every id
+            return get_item_embeddings_id_two_stage(model, item_content, test_batch_size)
         return get_item_embeddings_two_stage(model, item_content, test_batch_size)
     with ops.fp32_gemm_mode(getattr(_module(model), "fp32_gemm", ops.FP32_GEMM)):
         return _get_item_embeddings(model, item_content, test_batch_size, args, use_modal, local_rank)

@@ -6,7 +6,9 @@
 * ``collate_two_stage_batch``: the ids of a BCE batch, ``[B, L + 1, 2]`` int32 -- the reference's dataset gathers the feature rows on the
   host (``data_utils/dataset.py:39``) and ships ``[B, L + 1, 2, W]`` floats per step; here the table stays on the device;
 * ``get_item_embeddings_two_stage``: ``model.fc`` over the whole table (``data_utils/metrics.py:74-85``) -> the catalogue
-  ``[item_num + 1, D]`` that ``eval_model``, ``recommend_users`` and the cold-start evaluation take unchanged."""
+  ``[item_num + 1, D]`` that ``eval_model``, ``recommend_users`` and the cold-start evaluation take unchanged;
+* ``get_item_embeddings_id_two_stage``: the same catalogue for ``IdTwoStageModel`` (``bce_text/id_plus_mo-2stage``): the fused tower
+  ``mlp_layers(fc(id_embedding(id), turn_dim(features[id])))`` over every id."""
 from __future__ import annotations
 
 import numpy as np
@@ -119,4 +121,26 @@ def get_item_embeddings_two_stage(model, table, batch_size):
         for s in range(0, n, batch_size):
             ids = torch.arange(s, min(n, s + batch_size), device=dev, dtype=torch.int32)
             out[s:s + ids.numel()] = m.fc.encode_ids(ids, tab).float()
+    return out
+
+
+def get_item_embeddings_id_two_stage(model, table, batch_size):
+    """The eval-mode item tower of an ``IdTwoStageModel`` over ``arange`` id chunks of ``batch_size`` -> fp32 ``[item_num + 1, D]`` on the
+    model's device (``get_item_embeddings`` of the id_plus_mo-2stage packages, ``data_utils/metrics.py``).  ``table``: the frozen features;
+    the model's own device table is used when it is the same tensor, else ``table`` is cast to the compute dtype for this call."""
+    m = _module(model)
+    model.eval()
+    dev = m.id_embedding.weight.device
+    n = int(m.id_embedding.weight.shape[0])
+    keep = m.feature_table
+    if table is not None and table is not keep:
+        m.set_feature_table(table)
+    out = torch.empty((n, m.args.embedding_dim), device=dev, dtype=torch.float32)
+    try:
+        with torch.no_grad(), ops.fp32_gemm_mode(getattr(m, "fp32_gemm", ops.FP32_GEMM)):
+            for s in range(0, n, batch_size):
+                ids = torch.arange(s, min(n, s + batch_size), device=dev, dtype=torch.int32)
+                out[s:s + ids.numel()] = m.encode_items(ids).float()
+    finally:
+        m.feature_table = keep
     return out

@@ -131,6 +131,42 @@ class IdEmbeddingFn(torch.autograd.Function):
         return None, dw, None
 
 
+def _cat_layers_forward(a, fc_params, dtype, drop, need):
+    """The Linear + GELU layers behind the CAT fusion's concatenation ``a`` [R, 2D] (dropout already applied, site 0); ``drop.site(l)`` is
+    the Dropout in front of layer l.  Returns (output, prepared weights, layer inputs, pre-activations) for ``_cat_layers_backward``."""
+    p = float(drop.p_hidden)
+    n_layers = len(fc_params) // 2
+    lin = [engine.prepare_linear(fc_params[2 * l], dtype) for l in range(n_layers)]
+    acts, pres = [], []
+    for l in range(n_layers):
+        pre = torch.empty((a.shape[0], lin[l].w.shape[0]), device=a.device, dtype=dtype) if need else None
+        h = ops.gemm_nt(a, lin[l].w, bias=fc_params[2 * l + 1], act=ops.ACT_GELU, aux_out=pre)
+        acts.append(a)
+        pres.append(pre)
+        if l + 1 < n_layers and p > 0:
+            ops.dropout_apply_(h, p, drop.site(l + 1))
+        a = h
+    return a, lin, acts, pres
+
+
+def _cat_layers_backward(d, dout, lin, acts, pres, p, drop):
+    """Backward of ``_cat_layers_forward`` from the output gradient ``d`` (``dout``: the caller's tensor, never written): returns the gradient
+    of the concatenation [R, 2D] and [dW1, db1, ...].  Weight gradients run on the weight-gradient stream: the caller joins it."""
+    n_layers = len(lin)
+    grads = []
+    for l in reversed(range(n_layers)):
+        if l + 1 < n_layers and p > 0:      # the mask the forward put on this layer's output
+            d = ops.dropout_apply_(d.clone() if d.data_ptr() == dout.data_ptr() else d, p, drop.site(l + 1))
+        dv = ops.act_bwd(d, pres[l], ops.ACT_GELU)
+        db = torch.zeros(dv.shape[1], device=dv.device, dtype=torch.float32)
+        dw = torch.zeros(lin[l].w.shape, device=dv.device, dtype=torch.float32)
+        ops.colsum_(dv, db)
+        engine.linear_wgrad_(dv, acts[l], dw)
+        grads = [dw, db] + grads
+        d = ops.gemm_nt(dv, lin[l].wt, K=dv.shape[1], N=acts[l].shape[1])
+    return d, grads
+
+
 class FusionFn(torch.autograd.Function):
     """ID (+) modality fusion ``fc(id_embedding(ids), content)`` (``bce_text/id_plus_mo-end2end/model/model.py:43-47``): ``ADD`` or ``CAT``
     (``model/encoders.py:8-39``).  ``cfg = (kind, dtype, drop, pad_id)``: kind "add" | "cat", the compute dtype, a ``DropCfg`` whose
@@ -157,18 +193,7 @@ class FusionFn(torch.autograd.Function):
             ctx.stuff = (idx,)
             return ops.fuse_add_fwd(tab, idx, y)
         p = float(drop.p_hidden)
-        n_layers = len(fc_params) // 2
-        lin = [engine.prepare_linear(fc_params[2 * l], dtype) for l in range(n_layers)]
-        a = ops.fuse_cat_fwd(tab, idx, y, p, drop.site(0))
-        acts, pres = [], []
-        for l in range(n_layers):
-            pre = torch.empty((a.shape[0], lin[l].w.shape[0]), device=a.device, dtype=dtype) if need else None
-            h = ops.gemm_nt(a, lin[l].w, bias=fc_params[2 * l + 1], act=ops.ACT_GELU, aux_out=pre)
-            acts.append(a)
-            pres.append(pre)
-            if l + 1 < n_layers and p > 0:
-                ops.dropout_apply_(h, p, drop.site(l + 1))
-            a = h
+        a, lin, acts, pres = _cat_layers_forward(ops.fuse_cat_fwd(tab, idx, y, p, drop.site(0)), fc_params, dtype, drop, need)
         ctx.stuff = (idx, lin, acts, pres, p, drop) if need else None
         return a
 
@@ -184,19 +209,8 @@ class FusionFn(torch.autograd.Function):
             dc = d if d.dtype == in_dtype else ops.cast(d, in_dtype)
             return None, dc.view(in_shape), d_table, None
         _, lin, acts, pres, p, drop = stuff
-        n_layers = len(lin)
-        grads = []
         with ops.fp32_gemm_mode(ctx.fp32_gemm):
-            for l in reversed(range(n_layers)):
-                if l + 1 < n_layers and p > 0:      # the mask the forward put on this layer's output
-                    d = ops.dropout_apply_(d.clone() if d.data_ptr() == dout.data_ptr() else d, p, drop.site(l + 1))
-                dv = ops.act_bwd(d, pres[l], ops.ACT_GELU)
-                db = torch.zeros(dv.shape[1], device=dv.device, dtype=torch.float32)
-                dw = torch.zeros(lin[l].w.shape, device=dv.device, dtype=torch.float32)
-                ops.colsum_(dv, db)
-                engine.linear_wgrad_(dv, acts[l], dw)
-                grads = [dw, db] + grads
-                d = ops.gemm_nt(dv, lin[l].wt, K=dv.shape[1], N=acts[l].shape[1])
+            d, grads = _cat_layers_backward(d, dout, lin, acts, pres, p, drop)
             dc = ops.fuse_cat_bwd(d, idx, d_table, pad_id, p, drop.site(0))
             engine.WgradStream.join(dout.device)
         if dc.dtype != in_dtype:
@@ -271,16 +285,8 @@ class FeatProjFn(torch.autograd.Function):
     def forward(ctx, ids, table, dtype, weight, bias):
         need = any(ctx.needs_input_grad)
         idx = ids.reshape(-1).to(torch.int32).contiguous()
-        if table.dtype != dtype or table.dim() != 2 or not table.is_contiguous():
-            raise ValueError(f"featproj: the feature table must be a contiguous {dtype} matrix, got {table.dtype} {tuple(table.shape)}")
-        if weight.shape[1] != table.shape[1]:
-            raise ValueError(f"featproj: fc takes {weight.shape[1]} inputs, the feature table has {table.shape[1]} columns")
-        w = weight.contiguous() if weight.dtype == dtype else ops.cast(weight.contiguous(), dtype)
         ctx.fp32_gemm = ops.FP32_GEMM
-        if ops.featproj_supported(idx.numel(), table.shape[1], w.shape[0], dtype):
-            out, pre = ops.featproj_fwd(table, idx, w, bias, need_pre=need)
-        else:
-            out, pre, _ = ops.featproj_composed(table, idx, w, bias, need_pre=need)
+        out, pre = _featproj_forward(idx, table, dtype, weight, bias, need)
         ctx.stuff = (idx, table, pre, tuple(weight.shape)) if need else None
         return out
 
@@ -288,23 +294,102 @@ class FeatProjFn(torch.autograd.Function):
     def backward(ctx, dout):
         (idx, table, pre, wshape), ctx.stuff = ctx.stuff, None
         d = dout.contiguous().view(idx.numel(), -1)
-        dev = d.device
         with ops.fp32_gemm_mode(ctx.fp32_gemm):
-            dv = ops.act_bwd(d, pre, ops.ACT_GELU)
-            db = torch.zeros(dv.shape[1], device=dev, dtype=torch.float32)
-            dw = torch.zeros(wshape, device=dev, dtype=torch.float32)
-            ops.colsum_(dv, db)
-            # (the side stream exactly where linear_wgrad_ launches on it: 16-bit operands with whole 16-byte rows)
-            side = engine.WgradStream.get(dev) if (ops.is16(dv.dtype) and dv.shape[1] % 8 == 0 and table.shape[1] % 8 == 0) else None
-            if side is None:
-                x = ops.indexed_rows_copy(table, torch.empty((idx.numel(), table.shape[1]), device=dev, dtype=table.dtype), in_idx=idx)
-            else:       # X[idx] is read by the weight gradient alone: gathered on ITS stream (which waits for the main one first)
-                ops.stream_wait_stream(side.cuda_stream)
-                with torch.cuda.stream(side):
-                    x = ops.indexed_rows_copy(table, torch.empty((idx.numel(), table.shape[1]), device=dev, dtype=table.dtype), in_idx=idx)
-            engine.linear_wgrad_(dv, x, dw)
-            engine.WgradStream.join(dev)
+            dw, db = _featproj_backward(d, idx, table, pre, wshape)
+            engine.WgradStream.join(d.device)
         return None, None, None, dw, db
+
+
+def _featproj_forward(idx, table, dtype, weight, bias, need):
+    """``FeatProjFn``'s forward from the int32 ids: (out, pre) by ``ops.featproj_fwd`` where supported, else ``ops.featproj_composed``."""
+    if table.dtype != dtype or table.dim() != 2 or not table.is_contiguous():
+        raise ValueError(f"featproj: the feature table must be a contiguous {dtype} matrix, got {table.dtype} {tuple(table.shape)}")
+    if weight.shape[1] != table.shape[1]:
+        raise ValueError(f"featproj: fc takes {weight.shape[1]} inputs, the feature table has {table.shape[1]} columns")
+    w = weight.contiguous() if weight.dtype == dtype else ops.cast(weight.contiguous(), dtype)
+    if ops.featproj_supported(idx.numel(), table.shape[1], w.shape[0], dtype):
+        return ops.featproj_fwd(table, idx, w, bias, need_pre=need)
+    return ops.featproj_composed(table, idx, w, bias, need_pre=need)[:2]
+
+
+def _featproj_backward(d, idx, table, pre, wshape):
+    """(dW, db) of ``GELU(table[idx] @ W^T + b)`` from the output gradient ``d`` [R, D] and the pre-activation.  The looked-up rows are
+    gathered and multiplied on the weight-gradient stream: the caller joins it."""
+    dev = d.device
+    dv = ops.act_bwd(d, pre, ops.ACT_GELU)
+    db = torch.zeros(dv.shape[1], device=dev, dtype=torch.float32)
+    dw = torch.zeros(wshape, device=dev, dtype=torch.float32)
+    ops.colsum_(dv, db)
+    # (the side stream exactly where linear_wgrad_ launches on it: 16-bit operands with whole 16-byte rows)
+    side = engine.WgradStream.get(dev) if (ops.is16(dv.dtype) and dv.shape[1] % 8 == 0 and table.shape[1] % 8 == 0) else None
+    if side is None:
+        x = ops.indexed_rows_copy(table, torch.empty((idx.numel(), table.shape[1]), device=dev, dtype=table.dtype), in_idx=idx)
+    else:       # X[idx] is read by the weight gradient alone: gathered on ITS stream (which waits for the main one first)
+        ops.stream_wait_stream(side.cuda_stream)
+        with torch.cuda.stream(side):
+            x = ops.indexed_rows_copy(table, torch.empty((idx.numel(), table.shape[1]), device=dev, dtype=table.dtype), in_idx=idx)
+    engine.linear_wgrad_(dv, x, dw)
+    return dw, db
+
+
+class FeatFuseFn(torch.autograd.Function):
+    """The item tower of the two-stage ID (+) modality packages with ``mo_dnn_layers == 0``
+    (``bce_text/id_plus_mo-2stage/model/model.py:48-50``): ``fc(id_embedding(ids), GELU(turn_dim.fc(features[ids])))`` -- the chain
+    ids -> ``FeatProjFn`` -> ``FusionFn`` as one node.  ``cfg = (kind, dtype, drop, pad_id)`` as ``FusionFn``'s; ``table`` [n_rows, W] the
+    frozen features in the compute dtype, ``id_table`` fp32 [n_rows, D], ``weight`` / ``bias`` the projection, ``fc_params`` = (W1, b1) of
+    the CAT layer.  Forward: ``ops.featfuse_fwd`` (one launch) where ``ops.featfuse_supported`` says so, else featproj +
+    ``fuse_add_fwd`` / ``fuse_cat_fwd`` (fp32 modes, odd widths, ``MOREC_FEATFUSE=1``, sizes past the rule) -- the same bits either way.
+    Backward: ``FusionFn``'s and ``FeatProjFn``'s, existing kernels only; the feature table receives no gradient."""
+
+    @staticmethod
+    def forward(ctx, ids, table, id_table, cfg, weight, bias, *fc_params):
+        kind, dtype, drop, pad_id = cfg
+        need = any(ctx.needs_input_grad)
+        idx = ids.reshape(-1).to(torch.int32).contiguous()
+        tab = id_table.contiguous()
+        D = weight.shape[0]
+        if tab.dtype != torch.float32 or tuple(tab.shape) != (table.shape[0], D):
+            raise ValueError(f"featfuse: the id table must be fp32 [{table.shape[0]}, {D}], got {tab.dtype} {tuple(tab.shape)}")
+        if kind == "cat" and fc_params[0].shape[1] != 2 * D:
+            raise ValueError(f"featfuse: the first Linear takes {fc_params[0].shape[1]} inputs, the concatenation has {2 * D}")
+        p = float(drop.p_hidden) if kind == "cat" else 0.0
+        ctx.fp32_gemm = ops.FP32_GEMM
+        ctx.meta = (kind, pad_id, tuple(id_table.shape), tuple(weight.shape))
+        if ops.featfuse_supported(idx.numel(), table.shape[1], D, dtype):
+            if table.dtype != dtype or table.dim() != 2 or not table.is_contiguous():
+                raise ValueError(f"featfuse: the feature table must be a contiguous {dtype} matrix, got {table.dtype} {tuple(table.shape)}")
+            if weight.shape[1] != table.shape[1]:
+                raise ValueError(f"featfuse: fc takes {weight.shape[1]} inputs, the feature table has {table.shape[1]} columns")
+            w = weight.contiguous() if weight.dtype == dtype else ops.cast(weight.contiguous(), dtype)
+            a, pre = ops.featfuse_fwd(table, idx, w, bias, tab, kind, p, drop.site(0) if p > 0 else 0, need_pre=need)
+        else:
+            y, pre = _featproj_forward(idx, table, dtype, weight, bias, need)
+            a = ops.fuse_add_fwd(tab, idx, y) if kind == "add" else ops.fuse_cat_fwd(tab, idx, y, p, drop.site(0))
+        if kind == "add":
+            ctx.stuff = (idx, table, pre) if need else None
+            return a
+        a, lin, acts, pres = _cat_layers_forward(a, fc_params, dtype, drop, need)
+        ctx.stuff = (idx, table, pre, lin, acts, pres, p, drop) if need else None
+        return a
+
+    @staticmethod
+    def backward(ctx, dout):
+        kind, pad_id, tshape, wshape = ctx.meta
+        stuff, ctx.stuff = ctx.stuff, None
+        idx, table, pre = stuff[:3]
+        d_table = torch.zeros(tshape, device=dout.device, dtype=torch.float32)
+        d = dout.contiguous().view(idx.numel(), -1)
+        grads = []
+        with ops.fp32_gemm_mode(ctx.fp32_gemm):
+            if kind == "add":
+                ops.scatter_add_rows_(d, idx, d_table, pad_id)
+            else:
+                lin, acts, pres, p, drop = stuff[3:]
+                d, grads = _cat_layers_backward(d, dout, lin, acts, pres, p, drop)
+                d = ops.fuse_cat_bwd(d, idx, d_table, pad_id, p, drop.site(0))
+            dw, db = _featproj_backward(d, idx, table, pre, wshape)
+            engine.WgradStream.join(dout.device)
+        return (None, None, d_table, None, dw, db) + tuple(grads)
 
 
 class DssmBceFn(torch.autograd.Function):

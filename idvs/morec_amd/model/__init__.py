@@ -5,3 +5,4 @@ from .spec import BertShape  # noqa: F401
 from .bce import BceModel  # noqa: F401  (drop-in for bce_text/main-end2end/model/model.py)
 from .dssm import DssmModel, MLP_Encoder  # noqa: F401  (drop-in for bce_text/main-end2end(DSSM)/model/model.py)
 from .two_stage import MLP_Layers, TwoStageModel  # noqa: F401  (drop-in for bce_text|bce_vision/main-2stage(SASRec)/model/model.py)
+from .id_two_stage import FC_Layers, IdTwoStageModel, IdTwoStageModelVision  # noqa: F401  (drop-in for bce_text|bce_vision/id_plus_mo-2stage/model/model.py)

@@ -8,7 +8,7 @@ part is an MLP over the frozen feature rows, the SASRec user encoder and the one
 ``set_feature_table(table)``, the integer ids ``[B, L + 1, 2]`` themselves: the table then lives on the device in the compute dtype and
 the lookup is part of the first projection (``functional.FeatProjFn``: ``morec_featproj_fwd``).  The remaining layers are
 ``functional.MlpFn``, the user encoder ``User_Encoder.encode``, the loss ``BceLossFn`` -- ``BceModel._forward`` from the item vectors on.
-``id_plus_mo-2stage`` (frozen features fused with a trained id table) is not built."""
+``id_plus_mo-2stage`` (frozen features fused with a trained id table) is ``model/id_two_stage.py``: ``IdTwoStageModel``."""
 import torch
 from torch import nn
 from torch.nn.init import constant_, xavier_normal_

@@ -636,6 +636,43 @@ def featproj_composed(table, idx32, w, bias=None, *, need_pre=False):
     return out, pre, x
 
 
+FUSE_KINDS = {"add": 0, "cat": 1}      # MOREC_FUSE_ADD / MOREC_FUSE_CAT
+
+
+def featfuse_supported(R, Kw, D, dtype) -> bool:
+    """Does the chain lookup -> projection -> GELU -> ID fusion of the id-two-stage tower run as ``featfuse_fwd`` for this shape
+    (``morec_featfuse_supported``: 16-bit, ``Kw % 8 == D % 8 == 0``, the knob ``MOREC_FEATFUSE`` / ``set_featfuse`` and, when that is
+    automatic, ``R Kw D <= 3 * 2^28``: the sizes at which one launch measured faster, ``profiles/id_two_stage_step.txt``)?  Otherwise it is featproj + ``fuse_add_fwd`` / ``fuse_cat_fwd``."""
+    return is16(dtype) and bool(_lib.lib().morec_featfuse_supported(int(R), int(Kw), int(D), code(dtype)))
+
+
+def set_featfuse(mode: int):
+    """The knob of ``featfuse_supported``: 0 automatic | 1 never | 2 wherever the rules allow (``morec_tuning_set("featfuse", mode)``)."""
+    check(_lib.lib().morec_tuning_set(b"featfuse", int(mode)), "morec_tuning_set(featfuse)")
+
+
+def featfuse_fwd(table, idx32, w, bias, id_table, kind, p=0.0, seed=0, *, need_pre=False, out=None, pre=None, R=None):
+    """``y = GELU(table[idx] @ w^T + bias)`` fused with the id rows in ONE launch (``morec_featfuse_fwd``): ``kind`` "add" ->
+    ``id_table[idx] + y`` [R, D]; "cat" -> ``drop(cat([id_table[idx], y], 1))`` [R, 2D] with ``fuse_cat_fwd``'s stream of (p, seed).
+    ``table`` [n_rows, Kw] and ``w`` [D, Kw] in the same 16-bit dtype, ``id_table`` fp32 [n_rows, D], ``idx32`` int32 [R] (clamped into
+    the tables by the kernel), ``bias`` fp32 [D] or None.  Returns ``(out, pre)`` with the bits of ``featproj_fwd`` + ``fuse_*_fwd``;
+    ``pre`` is None unless ``need_pre`` or a buffer is given.  Rows past ``R`` of a given buffer stay untouched."""
+    _dev(table), _dev(w), _dev(id_table)
+    R = idx32.numel() if R is None else R
+    n_rows, Kw = table.shape
+    D = w.shape[0]
+    assert table.is_contiguous() and w.is_contiguous() and id_table.is_contiguous() and idx32.is_contiguous() and idx32.dtype == torch.int32
+    assert w.dtype == table.dtype and w.shape[1] == Kw, "featfuse: table and weight must share the 16-bit dtype and the feature width"
+    assert id_table.dtype == torch.float32 and tuple(id_table.shape) == (n_rows, D), "featfuse: the id table must be fp32 [n_rows, D]"
+    if out is None:
+        out = torch.empty((R, D if kind == "add" else 2 * D), device=table.device, dtype=table.dtype)
+    if pre is None and need_pre:
+        pre = torch.empty((R, D), device=table.device, dtype=table.dtype)
+    check(_lib.lib().morec_featfuse_fwd(_p(table), _p(idx32), _p(w), _p(bias), _p(id_table), _p(out), _p(pre), R, n_rows, Kw, D,
+                                        code(table.dtype), FUSE_KINDS[kind], float(p), int(seed), _stream()), "morec_featfuse_fwd")
+    return out, pre
+
+
 def strided_rows_copy(src, out, R, D, in_stride, out_stride):
     check(_lib.lib().morec_strided_rows_copy(_p(src), _p(out), R, D, in_stride, out_stride, code(src.dtype), _stream()),
           "morec_strided_rows_copy")

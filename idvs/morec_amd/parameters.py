@@ -16,14 +16,19 @@ def build_parser():
     p.add_argument("--item_tower", type=str, default="id", choices=ITEM_TOWERS,
                    help="id | modal, or ID (+) modality fusion (bce_text/id_plus_mo-end2end): modal_add = id vector + content vector, "
                         "modal_cat / modal_cat_3 = their concatenation through one / three Dropout-Linear-GELU layers")
-    p.add_argument("--arch", type=str, default="sasrec", choices=["sasrec", "dssm", "two_stage"],
+    p.add_argument("--arch", type=str, default="sasrec", choices=["sasrec", "dssm", "two_stage", "id_two_stage"],
                    help="sasrec = the sequential user encoder (everything as before); dssm = the two-tower model of "
                         "bce_text/main-end2end(DSSM): user-id embedding + MLP against 1 + neg_num sampled items per (user, item) pair, "
                         "BCE loss; --item_tower id | modal (text), autograd path; --loss is not consulted; two_stage = "
                         "bce_text|bce_vision/main-2stage(SASRec): the item tower runs once over the catalogue (or --features_npy supplies its "
-                        "features), an MLP over the frozen feature rows + SASRec + BCE are trained; --item_tower modal, autograd path")
+                        "features), an MLP over the frozen feature rows + SASRec + BCE are trained; --item_tower modal, autograd path; "
+                        "id_two_stage = bce_text|bce_vision/id_plus_mo-2stage: the same frozen features fused with a trained id table, "
+                        "--item_tower modal_add | modal_cat, --mo_dnn_layers / --dnn_layers")
     p.add_argument("--neg_num", type=int, default=1, help="--arch dssm: sampled negatives per (user, item) pair")
-    p.add_argument("--dnn_layers", type=int, default=0, help="--arch dssm: Dropout-Linear-GELU layers of the user MLP and of the ID tower's item MLP")
+    p.add_argument("--dnn_layers", type=int, default=0, help="--arch dssm: Dropout-Linear-GELU layers of the user MLP and of the ID tower's item "
+                   "MLP; --arch id_two_stage: Dropout-Linear-GELU layers behind the fusion")
+    p.add_argument("--mo_dnn_layers", type=int, default=0, help="--arch id_two_stage: Dropout-Linear-GELU layers between the feature projection "
+                   "and the fusion (0: lookup, projection and fusion run as one kernel)")
     p.add_argument("--dnn_layer", type=int, default=0, help="--arch two_stage: Dropout-Linear-GELU layers behind fc (the reference's spelling)")
     p.add_argument("--features_npy", type=str, default="None", help="--arch two_stage: fp16 / fp32 [item_num + 1, W] item features from any "
                    "encoder (row 0 = padding item); skips stage 1")
@@ -169,13 +174,39 @@ def check_two_stage_args(args):
         why = "--new_seqs needs the item tower over the new items' content; after stage 1 only the feature table exists (--cold_seqs alone is available)"
     elif args.item_tower != "modal":
         why = (f"--item_tower {args.item_tower}: two-stage trains on frozen MODALITY features (--item_tower modal); the ID (+) modality fusion "
-               "towers over frozen features (id_plus_mo-2stage) are not built")
+               "towers over frozen features (id_plus_mo-2stage) are --arch id_two_stage")
     elif getattr(args, "loss", "bce") == "inbatch" and getattr(args, "loss_given", False):
         why = "--loss inbatch: the two-stage packages train with the one-sampled-negative BCE loss only"
     elif args.dnn_layer < 0:
         why = "--dnn_layer must be >= 0"
     if why:
         raise SystemExit("--arch two_stage (two-stage training on frozen item features): " + why)
+    return True
+
+
+def check_id_two_stage_args(args):
+    """What ``--arch id_two_stage`` does not run with: exits with the reason (before anything touches a device).  True for such a run."""
+    if getattr(args, "arch", "sasrec") != "id_two_stage":
+        return False
+    why = None
+    if getattr(args, "fused_step", False):
+        why = "--fused_step (train_step.TrainStep) covers the end-to-end SASRec models only; id-two-stage trains on the autograd path"
+    elif getattr(args, "graph", False):
+        why = "--graph replays the fused step (train_step.TrainStep), which id-two-stage does not use"
+    elif getattr(args, "pool_negatives", False):
+        why = "--pool_negatives pools in-batch negatives; id-two-stage samples one negative per position (BCE)"
+    elif getattr(args, "new_seqs", "None") != "None":
+        why = ("--new_seqs: a new item has neither a row in the id table nor, after stage 1, an item tower to encode it "
+               "(--cold_seqs alone is available)")
+    elif args.item_tower not in ("modal_add", "modal_cat"):
+        why = (f"--item_tower {args.item_tower}: the frozen features are fused with the id table through modal_add | modal_cat "
+               "(--item_tower modal alone: --arch two_stage; modal_cat_3 is not part of the id_plus_mo-2stage packages)")
+    elif getattr(args, "loss", "bce") == "inbatch" and getattr(args, "loss_given", False):
+        why = "--loss inbatch: the id_plus_mo-2stage packages train with the one-sampled-negative BCE loss only"
+    elif args.mo_dnn_layers < 0 or args.dnn_layers < 0:
+        why = "--mo_dnn_layers and --dnn_layers must be >= 0"
+    if why:
+        raise SystemExit("--arch id_two_stage (id-two-stage: frozen item features fused with a trained id table): " + why)
     return True
 
 

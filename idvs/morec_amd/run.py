@@ -30,7 +30,7 @@ from .data_utils import (collate_bce_batch, collate_train_batch, epoch_batches, 
 from .model import BceModel, BertShape, DssmModel, HipBertModel, Model
 from .model.swin import HipSwinForImageClassification
 from .swin_engine import SwinShape
-from .parameters import check_dssm_args, check_fusion_args, check_two_stage_args, parse_args
+from .parameters import check_dssm_args, check_fusion_args, check_id_two_stage_args, check_two_stage_args, parse_args
 from . import engine
 from .train_step import TrainStep
 
@@ -935,6 +935,17 @@ def two_stage_model_dir(args):
     return os.path.join(args.checkpoint_root, f"checkpoint_{args.item_tower}_{load}", "cpt_" + label)
 
 
+def id_two_stage_model_dir(args):
+    """The checkpoint directory of the id_plus_mo-2stage drivers (``bce_text/id_plus_mo-2stage/run.py:284-296``) under ``--checkpoint_root``:
+    ``checkpoint_<behaviors> _<model>_MOdnn_<mo>/cpt_<item_tower>-<model>-MOdnn_<mo>-dnn_<dnn>_ed_<D>_bs_<B>_lr_<lr>`` -- the space in
+    the directory name is the reference's and is kept."""
+    cv = getattr(args, "CV_model_load", "None")
+    load = args.bert_model_load if cv == "None" else cv
+    label = (f"{args.item_tower}-{load}-MOdnn_{args.mo_dnn_layers}-dnn_{args.dnn_layers}_ed_{args.embedding_dim}_bs_{args.batch_size}"
+             f"_lr_{args.lr}")
+    return os.path.join(args.checkpoint_root, f"checkpoint_{args.behaviors} _{load}_MOdnn_{args.mo_dnn_layers}", "cpt_" + label)
+
+
 def two_stage_features(args, item_content, item_num, vision, local_rank, rank):
     """Stage 1 of ``--arch two_stage``: the frozen item tower once over the catalogue (``data_utils.extract_item_features``) -> fp32
     [item_num + 1, W] on the device; ``--save_features`` writes it (rank 0).  The tower is dropped afterwards."""
@@ -960,15 +971,19 @@ def two_stage_features(args, item_content, item_num, vision, local_rank, rank):
     return table
 
 
-def train_two_stage(args, use_modal, local_rank):
-    """``--arch two_stage``: the driver of ``bce_text/main-2stage(SASRec)/run.py`` (and its vision twin) around ``TwoStageModel``.  Stage 1
+def train_two_stage(args, use_modal, local_rank, id_fusion=False):
+    """``id_fusion``: ``--arch id_two_stage`` -- the same driver around ``IdTwoStageModel`` (``bce_text/id_plus_mo-2stage/run.py``): the
+    model class, its call, the checkpoint directory and the log label differ, nothing else (the catalogue function follows the model:
+    ``data_utils.get_item_embeddings``).
+
+    ``--arch two_stage``: the driver of ``bce_text/main-2stage(SASRec)/run.py`` (and its vision twin) around ``TwoStageModel``.  Stage 1
     runs the frozen tower once (or ``--features_npy`` supplies the table); a step is then ids -> ``fc`` over looked-up feature rows ->
     SASRec -> BCE.  One AdamW over ALL parameters (``lr``, ``l2_weight``: ``run.py:124`` there), GradScaler for fp16, a validation per
     epoch with early stopping, ``epoch-N.pt`` (the reference's keys) whenever the validation Hit@10 improves and once more at the end
     (``run.py:182-190``).  ``--mode test`` (with ``--cold_seqs``) and ``--mode recommend`` evaluate a checkpoint through the same catalogue
     paths as ``train()``: the catalogue is ``fc`` over the feature table.  Multi-GPU goes through DDP and is unmeasured."""
     from .data_utils import collate_two_stage_batch, load_feature_table
-    from .model import TwoStageModel
+    from .model import IdTwoStageModel, TwoStageModel
     from .model.encoders import resolve_dtype
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -977,7 +992,8 @@ def train_two_stage(args, use_modal, local_rank):
     S = args.max_seq_len
     have = args.features_npy != "None"
     vision = args.CV_model_load != "None"
-    model_dir = two_stage_model_dir(args)
+    model_dir = (id_two_stage_model_dir if id_fusion else two_stage_model_dir)(args)
+    tag = "id-two-stage" if id_fusion else "two-stage"
     if not vision:
         del args.CV_model_load
     # with a feature file no content is read at all (bare ids, like the ID tower)
@@ -988,7 +1004,10 @@ def train_two_stage(args, use_modal, local_rank):
     else:
         table = two_stage_features(args, item_content, item_num, vision, local_rank, rank)
     del item_content
-    model = TwoStageModel(args, item_num, num_fc_ftr=int(table.shape[1])).to(local_rank)
+    if id_fusion:
+        model = IdTwoStageModel(args, item_num, use_modal, num_fc_ftr=int(table.shape[1])).to(local_rank)
+    else:
+        model = TwoStageModel(args, item_num, num_fc_ftr=int(table.shape[1])).to(local_rank)
     model.set_feature_table(table)
     table = model.feature_table
     users = list(users_train.keys())
@@ -1032,8 +1051,9 @@ def train_two_stage(args, use_modal, local_rank):
     neg = {"rng": None}      # re-seeded per epoch; read by the one thread that builds the batches
     make_batch = lambda idx: collate_two_stage_batch(users_train, [users[i] for i in idx], S, item_num, neg["rng"])
     depth = int(getattr(args, "prefetch", 2))
-    Log.info("two-stage: %d users, %d items, features %d wide in %s, dnn_layer %d" %
-             (len(users), item_num, table.shape[1], str(table.dtype).replace("torch.", ""), args.dnn_layer))
+    Log.info("%s: %d users, %d items, features %d wide in %s, %s" %
+             (tag, len(users), item_num, table.shape[1], str(table.dtype).replace("torch.", ""),
+              "mo_dnn_layers %d, dnn_layers %d" % (args.mo_dnn_layers, args.dnn_layers) if id_fusion else "dnn_layer %d" % args.dnn_layer))
 
     def save(now_epoch):
         if rank == 0:
@@ -1053,7 +1073,7 @@ def train_two_stage(args, use_modal, local_rank):
         for b, (ids, log_mask) in source:
             ids, log_mask = ids.to(local_rank, non_blocking=True), log_mask.to(local_rank, non_blocking=True)
             optimizer.zero_grad()
-            loss = wrapped(ids, log_mask, local_rank)
+            loss = wrapped(ids, None, log_mask, local_rank) if id_fusion else wrapped(ids, log_mask, local_rank)
             if scaler is not None:
                 scaler.scale(loss).backward()
                 scaler.step(optimizer)
@@ -1095,8 +1115,10 @@ def train_two_stage(args, use_modal, local_rank):
 def main(argv=None):
     args = parse_args(argv)
     two_stage = check_two_stage_args(args)
+    id_two_stage = check_id_two_stage_args(args)
     dssm = check_dssm_args(args)
-    check_fusion_args(args)
+    if not id_two_stage:
+        check_fusion_args(args)
     logging.basicConfig(level=logging.INFO, format="[%(levelname)s %(asctime)s] %(message)s")
     local_rank = args.local_rank if args.local_rank >= 0 else int(os.environ.get("LOCAL_RANK", 0))
     if os.environ.get("MOREC_DEVICE_INDEX") is not None:      # several ranks on ONE device (functional tests of the N > 1 driver over gloo)
@@ -1110,7 +1132,10 @@ def main(argv=None):
     use_modal = "modal" in args.item_tower
     if dist.is_initialized() and dist.get_rank() != 0:
         Log.setLevel(logging.WARNING)
-    best = (train_two_stage if two_stage else train_dssm if dssm else train)(args, use_modal, local_rank)
+    if id_two_stage:
+        best = train_two_stage(args, use_modal, local_rank, id_fusion=True)
+    else:
+        best = (train_two_stage if two_stage else train_dssm if dssm else train)(args, use_modal, local_rank)
     Log.info("max eval Hit10 %.5f" % (best * 100))
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -96,6 +96,9 @@ int morec_version(void);
  *   "featproj"           0 automatic | 1 never | 2 wherever the rules allow                            MOREC_FEATPROJ            0
  *                        the fused gather + first projection of the two-stage tower (morec_featproj_fwd; 16-bit, Kw % 8 == D % 8 == 0).
  *                        Automatic: R Kw D <= 2^29 (morec_featproj_supported);
+ *   "featfuse"           0 automatic | 1 never | 2 wherever the rules allow                            MOREC_FEATFUSE            0
+ *                        the fused gather + projection + ID fusion of the two-stage ID (+) modality tower (morec_featfuse_fwd; 16-bit,
+ *                        Kw % 8 == D % 8 == 0).  Automatic: R Kw D <= 3 . 2^28 (morec_featfuse_supported);
  *   "gemm8p_tmr"         0 always 256-row tiles | 1 automatic | 224 | 192 (other values: 1)            MOREC_GEMM8P_TMR          1
  *   "gemm8p_ngroup"      tile order: -1 automatic column groups | 0 row-major | n groups of n N-tiles  MOREC_GEMM8P_NGROUP       -1
  *   "gemm8p_reserve_cus" 0..128 CUs (multiple of 8) left out of the persistent grid for a concurrent RCCL kernel   MOREC_GEMM8P_RESERVE_CUS   0
@@ -413,6 +416,7 @@ int morec_droppath_scale(float* out, int n, float p, uint64_t seed, void* stream
  * BCE variant, one sampled negative per position (bce_text/main-end2end/model/model.py:30-51).
  * E [B, S+1, 2, D] item vectors (pos at [:, :, 0], neg at [:, :, 1]), P [B, S, D] user states, row_valid u8 [B*S].
  * scores fp32 [2][B*S] (pos | neg) are saved for the backward; loss_sum[0] += sum_valid softplus(-pos) + softplus(neg).
+ * The sum is one fp32 atomic per valid row; in the deterministic mode a second one-block launch adds the rows' terms in a fixed order instead.
  * Backward: gscale[0] = dloss / n_valid on the device; writes dP [B, S, D] and EVERY row of dE [B, S+1, 2, D] (no atomics).
  * ------------------------------------------------------------------------------------------ */
 int morec_bce_fwd(const void* P, const void* E, const uint8_t* row_valid, float* scores, float* loss_sum, int B, int S, int D,
@@ -510,6 +514,30 @@ int morec_dropout_apply(const void* x, void* out, size_t n, float p, uint64_t se
 int morec_featproj_fwd(const void* table, const int32_t* idx, const void* W, const float* bias, void* out, void* pre, int R, int n_rows,
                        int Kw, int D, int dtype, void* stream);
 int morec_featproj_supported(int R, int Kw, int D, int dtype);
+
+/* ------------------------------------------------------------------------------------------
+ * Two-stage ID (+) modality fusion (bce_text/id_plus_mo-2stage, bce_vision/id_plus_mo-2stage: model/model.py:48-50 with mo_dnn_layers = 0):
+ * the feature lookup, the projection, the GELU and the fusion with the id row in one launch (csrc/featfuse.hip):
+ *     y[r, :] = GELU(table[idx[r], :] . W^T + b),   pre[r, :] = table[idx[r], :] . W^T + b (unless NULL),   r < R
+ *     MOREC_FUSE_ADD:  out[r, 0:D] = id_table[idx[r], :] + y[r, :]                                       out [R, D]
+ *     MOREC_FUSE_CAT:  out[r, 0:D] = drop(id_table[idx[r], :]),  out[r, D:2D] = drop(y[r, :])            out [R, 2D]
+ * table, W, b, pre: as morec_featproj_fwd;  id_table fp32 [n_rows, D];  (p, seed): morec_fuse_cat_fwd's dropout stream over the [R, 2D]
+ * matrix (ADD: p is checked and unused).  The main loop is morec_featproj_fwd's; y is rounded to dtype before the add / the dropout
+ * scaling, so out and pre carry the bits of morec_featproj_fwd followed by morec_fuse_add_fwd / morec_fuse_cat_fwd with the same inputs, p
+ * and seed.  idx is clamped into [0, n_rows) for BOTH tables; rows past R of out / pre are not touched.  Deterministic.
+ * Checked in this order, before anything is launched: R, n_rows, Kw or D <= 0: MOREC_E_ARG;  dtype MOREC_F32: MOREC_E_DTYPE;  Kw % 8 or
+ * D % 8: MOREC_E_ALIGN;  kind neither MOREC_FUSE_ADD nor MOREC_FUSE_CAT, or p outside [0, 1): MOREC_E_ARG;  a null table, idx, W,
+ * id_table or out: MOREC_E_ARG;  a base pointer off 16 bytes: MOREC_E_ALIGN.
+ * morec_featfuse_supported: 1 where callers should take this kernel instead of the composition.  Knob "featfuse" (MOREC_FEATFUSE):
+ * 0 automatic | 1 never | 2 wherever the rules above allow.  Automatic: where the rules allow and R Kw D <= 3 . 2^28 -- measured
+ * (profiles/id_two_stage_step.txt): ahead of the composition up to 2048 x 768 x 512 and at 21504 x 128 x 64, behind it at 5376 x 768 x 512
+ * (40 us against 25 us), where each wave re-reads its operand rows through L2 as in morec_featproj_fwd.
+ * ------------------------------------------------------------------------------------------ */
+#define MOREC_FUSE_ADD 0
+#define MOREC_FUSE_CAT 1
+int morec_featfuse_fwd(const void* table, const int32_t* idx, const void* W, const float* bias, const float* id_table, void* out, void* pre,
+                       int R, int n_rows, int Kw, int D, int dtype, int kind, float p, uint64_t seed, void* stream);
+int morec_featfuse_supported(int R, int Kw, int D, int dtype);
 
 /* ------------------------------------------------------------------------------------------
  * In-batch debiased sampled-softmax cross-entropy (T/model/model.py:32-33,45-67), fused:
