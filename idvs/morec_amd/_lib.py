@@ -56,7 +56,16 @@ class CeDesc(C.Structure):
 class StepParams(C.Structure):       # morec_step_params (64 bytes, lives on the DEVICE; this mirror is for host-side reads of a copy)
     _fields_ = [("step", C.c_int32), ("found_inf", C.c_int32), ("growth_tracker", C.c_int32), ("skipped", C.c_int32),
                 ("loss_scale", C.c_float), ("inv_scale", C.c_float), ("bc1", C.c_float), ("bc2", C.c_float), ("apply", C.c_int32),
-                ("pad0", C.c_int32), ("drop_seed", C.c_uint64), ("drop_seed_mixed", C.c_uint64), ("reserved", C.c_int32 * 2)]
+                ("ctl_flags", C.c_int32), ("drop_seed", C.c_uint64), ("drop_seed_mixed", C.c_uint64), ("clip_coef", C.c_float),
+                ("lr_mult", C.c_float)]
+
+
+SP_CLIP, SP_LR_MULT = 1, 2                          # morec_step_params.ctl_flags
+LR_CONSTANT, LR_LINEAR, LR_COSINE = 0, 1, 2
+
+
+class LrSchedule(C.Structure):       # morec_lr_schedule
+    _fields_ = [("kind", C.c_int32), ("warmup_steps", C.c_int32), ("total_steps", C.c_int32), ("min_ratio", C.c_float)]
 
 
 class SwinAttnDesc(C.Structure):
@@ -136,6 +145,10 @@ _SIGS = {
     "morec_step_params_init": (C.c_int, [_P, C.c_float, C.c_int, _P]),
     "morec_grad_check_finite": (C.c_int, [_P, C.c_size_t, _P, _P]),
     "morec_step_decide": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, _P]),
+    "morec_grad_norm_blocks": (C.c_size_t, [C.c_size_t]),
+    "morec_grad_norm_check": (C.c_int, [_P, C.c_size_t, _P, _P, C.c_size_t, C.c_size_t, _P]),
+    "morec_step_decide_ex": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, _P, C.c_size_t, C.c_float,
+                                       C.POINTER(LrSchedule), _P, _P]),
     "morec_adamw_sp": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P]),
     "morec_eval_rank": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "morec_eval_rank_cand": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),

@@ -819,6 +819,50 @@ class StepParams:
         check(_lib.lib().morec_step_decide(_p(self.buf), beta1, beta2, self.growth_factor, self.backoff_factor, self.growth_interval,
                                            int(self.dynamic), _stream()), "morec_step_decide")
 
+    # ---- global-norm clipping + LR schedule (morec_grad_norm_check / morec_step_decide_ex) -------------------------------------------
+    @staticmethod
+    def norm_slots(n: int) -> int:
+        """Slots of the partials buffer an arena of ``n`` elements fills (a function of ``n`` alone)."""
+        return int(_lib.lib().morec_grad_norm_blocks(int(n)))
+
+    def reserve_partials(self, n_slots: int):
+        """fp32 ``[n_slots + 1]`` on the block's device: the per-block sums of squares of a step, and ``grad_norm`` in the tail slot."""
+        self.partials = torch.zeros(int(n_slots) + 1, device=self.buf.device, dtype=torch.float32)
+        return self.partials
+
+    def norm_check_(self, grad, slot: int):
+        """``check_finite_`` plus this arena's share of the sum of squares of the UNSCALED gradients into ``partials[slot : slot + norm_slots(n)]``."""
+        pt = getattr(self, "partials", None)
+        if pt is None:
+            raise _lib.MorecError("norm_check_ before reserve_partials")
+        check(_lib.lib().morec_grad_norm_check(_p(grad), grad.numel(), _p(self.buf), _p(pt), int(slot), pt.numel() - 1, _stream()),
+              "morec_grad_norm_check")
+
+    def decide_ex_(self, beta1, beta2, n_partials: int = 0, max_norm: float = 0.0, schedule=None):
+        """``decide_`` with the gradient norm folded from ``partials[:n_partials]`` in front of the verdict, and the clip coefficient
+        (``max_norm`` > 0) / LR multiplier (``schedule``: ``lr_schedule.LrSchedule``) of the step behind it."""
+        pt = getattr(self, "partials", None)
+        if n_partials and (pt is None or n_partials > pt.numel() - 1):
+            raise _lib.MorecError(f"decide_ex_: {n_partials} partials, buffer holds {0 if pt is None else pt.numel() - 1}")
+        sched = schedule.c_struct() if schedule is not None else None
+        check(_lib.lib().morec_step_decide_ex(_p(self.buf), beta1, beta2, self.growth_factor, self.backoff_factor, self.growth_interval,
+                                              int(self.dynamic), _p(pt) if n_partials else None, int(n_partials), float(max_norm),
+                                              C.byref(sched) if sched is not None else None,
+                                              C.c_void_p(pt.data_ptr() + 4 * (pt.numel() - 1)) if n_partials else None, _stream()),
+              "morec_step_decide_ex")
+
+    def grad_norm(self) -> float:
+        """Global gradient norm the last ``decide_ex_`` folded (synchronises: logging only)."""
+        return float(self.partials[-1].item())
+
+    def clip_coef(self) -> float:
+        h = self.host()
+        return float(h.clip_coef) if h.ctl_flags & _lib.SP_CLIP else 1.0
+
+    def lr_mult(self) -> float:
+        h = self.host()
+        return float(h.lr_mult) if h.ctl_flags & _lib.SP_LR_MULT else 1.0
+
     def host(self):
         """Host copy of the block (synchronises): for logging / checkpoints, never inside the step."""
         raw = bytes(self.buf.cpu().numpy().tobytes())

@@ -114,6 +114,13 @@ def build_parser():
                    "(TrainStep.step_graphed; unpadded token rows padded to buckets of 512) instead of host launches")
     p.add_argument("--steady_after", type=int, default=10, help="the epoch log also reports user-seq/s over the steps after this many (allocator "
                    "warm-up, first-call set-up and the loss scaler's initial back-off excluded)")
+    p.add_argument("--max_grad_norm", type=float, default=0.0, help="global-norm gradient clipping over all parameter groups together "
+                   "(torch.nn.utils.clip_grad_norm_; --fused_step: decided on the device); 0 = off")
+    p.add_argument("--lr_schedule", type=str, default="constant", choices=["constant", "linear", "cosine"],
+                   help="LR multiplier shared by all parameter groups: 1 (constant), or a linear / cosine decay to --min_lr_ratio at "
+                        "epochs x steps-per-epoch, each after --warmup_steps of linear warmup; counted in APPLIED steps")
+    p.add_argument("--warmup_steps", type=int, default=0, help="linear LR warmup from 0 over this many applied optimizer steps; 0 = none")
+    p.add_argument("--min_lr_ratio", type=float, default=0.0, help="--lr_schedule linear | cosine: the multiplier the decay ends at (and holds)")
     p.add_argument("--checkpoint_root", type=str, default="./checkpoint", help="parent of checkpoint_<tower>.../cpt_<label>/ (T/run.py:326-331)")
     p.add_argument("--pretrained_dir", type=str, default="../pretrained_models",
                    help="directory holding <bert_model_load>/pytorch_model.bin (T/run.py:29-53 reads ../../pretrained_models/)")

@@ -33,6 +33,7 @@ from .swin_engine import SwinShape
 from .parameters import check_dssm_args, check_fusion_args, check_id_two_stage_args, check_two_stage_args, parse_args
 from . import engine
 from .train_step import TrainStep
+from .lr_schedule import AutogradStepControl, schedule_from_args
 
 Log = logging.getLogger("morec")
 
@@ -502,6 +503,35 @@ def load_dataset(args, use_modal, vision):
     return item_num, item_content, users_train, users_valid, users_test, hist_valid, hist_test, pop, catalogue
 
 
+def clip_schedule_kwargs(args, total_steps):
+    """``--max_grad_norm`` / ``--lr_schedule`` / ``--warmup_steps`` / ``--min_lr_ratio`` as the ``TrainStep`` keyword arguments
+    (``total_steps`` = epochs x steps per epoch)."""
+    return {"max_grad_norm": float(getattr(args, "max_grad_norm", 0.0)), "lr_schedule": schedule_from_args(args, total_steps)}
+
+
+def autograd_step_control(args, optimizer, scaler, total_steps):
+    """The same four flags on the autograd paths (``torch.optim.AdamW`` + GradScaler): ``scaler.unscale_`` +
+    ``torch.nn.utils.clip_grad_norm_`` and a ``LambdaLR`` over all parameter groups, from the one host form of the schedule formula.  A
+    resumed optimizer (its ``step`` counts the applied steps) puts the schedule where it stood."""
+    ctl = AutogradStepControl(optimizer, scaler, **clip_schedule_kwargs(args, total_steps))
+    ctl.resume_from_optimizer()
+    return ctl
+
+
+def _log_step_control(src):
+    """Last gradient norm and current LR multiplier, at a point where the loop has synchronised anyway (``src``: TrainStep or AutogradStepControl)."""
+    if src is None:
+        return
+    if isinstance(src, TrainStep):
+        st = src.step_stats()
+        if st is not None:
+            Log.info("step control: last gradient norm %.4g (clip coefficient %.4g), lr multiplier %.4g" % st)
+        return
+    if src.max_grad_norm > 0.0 or src.scheduler is not None:
+        norm = float(src.last_norm) if src.last_norm is not None else float("nan")
+        Log.info("step control: last gradient norm %.4g, lr multiplier %.4g" % (norm, src.lr_mult()))
+
+
 def train(args, use_modal, local_rank):
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -568,11 +598,13 @@ def train(args, use_modal, local_rank):
         run_recommend(model, item_content, users_test, catalogue, 512, use_modal, args, out_path, local_rank)
         return 0.0
     stepper, optimizer = None, None
+    total_steps = args.epoch * len(epoch_batches(len(users), args.batch_size, world, rank, 1))      # --lr_schedule: epochs x steps per epoch
     if args.fused_step:
         stepper = TrainStep(model, lr=args.lr, fine_tune_lr=args.fine_tune_lr, l2_weight=args.l2_weight,
                             fine_tune_l2_weight=args.fine_tune_l2_weight, pool_negatives=args.pool_negatives,
                             defer_update=os.environ.get("MOREC_DEFER_UPDATE", "1") != "0",      # (the epoch ends with a device synchronisation before eval / save)
-                            graph=(world == 1 and bool(getattr(args, "graph", False))))
+                            graph=(world == 1 and bool(getattr(args, "graph", False))),
+                            **clip_schedule_kwargs(args, total_steps))
         if ckpt is not None and ckpt.get("optimizer") is not None:     # T/run.py:193-195
             stepper.load_optimizer_state_dict(ckpt["optimizer"])
         if ckpt is not None and ckpt.get("scaler_state"):              # (the reference never saves its GradScaler: an empty dict there)
@@ -595,6 +627,7 @@ def train(args, use_modal, local_rank):
     scaler = torch.amp.GradScaler("cuda", enabled=True) if (optimizer is not None and args.compute_dtype in ("fp16", "fp16_res32")) else None
     if scaler is not None and ckpt is not None and ckpt.get("scaler_state"):
         scaler.load_state_dict(ckpt["scaler_state"])
+    ctl = autograd_step_control(args, optimizer, scaler, total_steps) if optimizer is not None else None
     best, step = 0.0, 0
     max_epoch, early_stop_epoch, early_stop_count = 0, args.epoch, 0
     early_stop_gap = 6 if vision else 10                               # T/run.py:221 / V/run.py:185
@@ -651,13 +684,8 @@ def train(args, use_modal, local_rank):
                     loss = wrapped(ids.to(local_rank, non_blocking=True).view(-1), items, log_mask, local_rank)
                 else:
                     loss = wrapped(items, log_mask, local_rank)
-                if scaler is not None:
-                    scaler.scale(loss).backward()
-                    scaler.step(optimizer)
-                    scaler.update()
-                else:
-                    loss.backward()
-                    optimizer.step()
+                (scaler.scale(loss) if scaler is not None else loss).backward()      # T/run.py:243-247
+                ctl.step()      # scaler.step + update | optimizer.step, behind --max_grad_norm / --lr_schedule when given
                 loss_acc = loss.detach() if loss_acc is None else loss_acc + loss.detach()
                 step += 1
                 if args.max_steps and step >= args.max_steps:
@@ -689,13 +717,8 @@ def train(args, use_modal, local_rank):
             else:
                 optimizer.zero_grad()
                 loss = wrapped(ids.view(-1), items, log_mask, local_rank)
-                if scaler is not None:      # T/run.py:243-247
-                    scaler.scale(loss).backward()
-                    scaler.step(optimizer)
-                    scaler.update()
-                else:
-                    loss.backward()
-                    optimizer.step()
+                (scaler.scale(loss) if scaler is not None else loss).backward()      # T/run.py:243-247
+                ctl.step()      # scaler.step + update | optimizer.step, behind --max_grad_norm / --lr_schedule when given
             loss_acc = loss.detach() if loss_acc is None else loss_acc + loss.detach()
             step += 1
             if args.max_steps and step >= args.max_steps:
@@ -721,6 +744,7 @@ def train(args, use_modal, local_rank):
         if stepper is not None and stepper.sp is not None:
             h_ = stepper.sp.host()
             Log.info("loss scaler: scale %g, %d steps applied, %d skipped" % (h_.loss_scale, h_.step, h_.skipped))
+        _log_step_control(stepper if stepper is not None else ctl)
         hit10 = run_eval(wrapped, item_content, hist_valid, users_valid, 512, item_num, use_modal, args, "valid", local_rank)
         need_break = False
         if hit10 > best:                                                # T/run.py:291-304
@@ -844,6 +868,7 @@ def train_dssm(args, use_modal, local_rank):
     if scaler is not None and ckpt is not None and ckpt.get("scaler_state"):
         scaler.load_state_dict(ckpt["scaler_state"])
     step_num = int(np.ceil(len(train_pairs) / world / args.batch_size))
+    ctl = autograd_step_control(args, optimizer, scaler, args.epoch * step_num)
     steps_for_log = max(1, int(step_num / max(1, args.logging_num)))
     steps_for_test = max(1, int(step_num / max(1, args.testing_num)))
     Log.info("dssm: %d users, %d items, %d train pairs; %d steps/epoch, a log every %d steps, a validation every %d" %
@@ -878,13 +903,8 @@ def train_dssm(args, use_modal, local_rank):
                                                    bce_label.to(local_rank, non_blocking=True))
             optimizer.zero_grad()
             loss = wrapped(input_user, sample_items, bce_label)
-            if scaler is not None:
-                scaler.scale(loss).backward()
-                scaler.step(optimizer)
-                scaler.update()
-            else:
-                loss.backward()
-                optimizer.step()
+            (scaler.scale(loss) if scaler is not None else loss).backward()      # T/run.py:243-247
+            ctl.step()      # scaler.step + update | optimizer.step, behind --max_grad_norm / --lr_schedule when given
             loss_acc = loss.detach() if loss_acc is None else loss_acc + loss.detach()
             step += 1
             n_done = b + 1
@@ -895,6 +915,7 @@ def train_dssm(args, use_modal, local_rank):
                     need_break = True
                     break
                 Log.info("step %d (%d pairs): batch loss %.5f, mean loss %.5f" % (n_done, n_done * args.batch_size, bl, float(loss_acc) / n_done))
+                _log_step_control(ctl)
             if n_done % steps_for_test == 0:
                 hit10 = run_eval_dssm(wrapped, item_content, hist_valid, valid_pairs, 512, user_num, item_num, use_modal, args, "valid", local_rank)
                 if hit10 > best:
@@ -1048,6 +1069,7 @@ def train_two_stage(args, use_modal, local_rank, id_fusion=False):
     scaler = torch.amp.GradScaler("cuda", enabled=True) if args.compute_dtype in ("fp16", "fp16_res32") else None
     if scaler is not None and ckpt is not None and ckpt.get("scaler_state"):
         scaler.load_state_dict(ckpt["scaler_state"])
+    ctl = autograd_step_control(args, optimizer, scaler, args.epoch * len(epoch_batches(len(users), args.batch_size, world, rank, 1)))
     neg = {"rng": None}      # re-seeded per epoch; read by the one thread that builds the batches
     make_batch = lambda idx: collate_two_stage_batch(users_train, [users[i] for i in idx], S, item_num, neg["rng"])
     depth = int(getattr(args, "prefetch", 2))
@@ -1074,13 +1096,8 @@ def train_two_stage(args, use_modal, local_rank, id_fusion=False):
             ids, log_mask = ids.to(local_rank, non_blocking=True), log_mask.to(local_rank, non_blocking=True)
             optimizer.zero_grad()
             loss = wrapped(ids, None, log_mask, local_rank) if id_fusion else wrapped(ids, log_mask, local_rank)
-            if scaler is not None:
-                scaler.scale(loss).backward()
-                scaler.step(optimizer)
-                scaler.update()
-            else:
-                loss.backward()
-                optimizer.step()
+            (scaler.scale(loss) if scaler is not None else loss).backward()      # T/run.py:243-247
+            ctl.step()      # scaler.step + update | optimizer.step, behind --max_grad_norm / --lr_schedule when given
             loss_acc = loss.detach() if loss_acc is None else loss_acc + loss.detach()
             step += 1
             n_done = b + 1
@@ -1095,6 +1112,7 @@ def train_two_stage(args, use_modal, local_rank, id_fusion=False):
             break
         Log.info("epoch %d: %d steps, mean loss %.5f, %.1f user-seq/s" %
                  (now_epoch, n_done, mean_loss, sum(len(x) for x in batches[:n_done]) * world / max(time.time() - t0, 1e-9)))
+        _log_step_control(ctl)
         hit10 = run_eval(wrapped, table, hist_valid, users_valid, 512, item_num, True, args, "valid", local_rank)
         need_break = False
         if hit10 > best:

@@ -26,6 +26,7 @@ import torch.distributed as dist
 
 from . import engine, ops, swin_engine
 from .functional import pool_exchange, reduce_scatter_dE
+from .lr_schedule import LrSchedule
 
 
 def _round8(n: int) -> int:
@@ -132,7 +133,8 @@ class TrainStep:
     def __init__(self, model, *, lr: float, fine_tune_lr: float, l2_weight: float, fine_tune_l2_weight: float,
                  betas=(0.9, 0.999), eps: float = 1e-8, pool_negatives: bool = True, dedup_items: bool = False,
                  force_collectives: bool = False, comm: str | None = None, loss_scale: float | None = None,
-                 dynamic_loss_scale: bool = True, growth_interval: int = 2000, defer_update: bool | None = None, graph: bool | None = None):
+                 dynamic_loss_scale: bool = True, growth_interval: int = 2000, defer_update: bool | None = None, graph: bool | None = None,
+                 max_grad_norm: float = 0.0, lr_schedule=None):
         """``loss_scale`` / ``dynamic_loss_scale`` / ``growth_interval``: the GradScaler of the reference's fp16 step (``T/run.py:210``:
         defaults 65536, x2 after 2000 clean steps, x0.5 and a skipped step on inf / NaN), kept in a device block (``ops.StepParams``).
         Engaged automatically for ``compute_dtype == "fp16"``; ``loss_scale=`` a number forces it on for the other dtypes too
@@ -148,7 +150,12 @@ class TrainStep:
         ``graph`` (``MOREC_GRAPH=1``; one rank, no item dedup): ``step_graphed`` captures the whole step -- forward, backward, AdamW, both
         streams -- into a hipGraph per input shape and replays it (``T/run.py:231-247`` as ONE launch: the ~700 kernel launches of a step
         and the idle gaps between them go away).  Needs the step block (created with scale 1 for the non-fp16 dtypes: step count, bias
-        corrections and the dropout seed word then live on the device, so no per-step host scalar is frozen into the graph)."""
+        corrections and the dropout seed word then live on the device, so no per-step host scalar is frozen into the graph).
+        ``max_grad_norm`` (> 0) / ``lr_schedule`` (``lr_schedule.LrSchedule`` or a dict of its fields): global-norm gradient clipping
+        (``torch.nn.utils.clip_grad_norm_`` over BOTH groups together) and an LR multiplier shared by both groups, both decided on the
+        device (``morec_grad_norm_check`` + ``morec_step_decide_ex``): the step block then exists for every dtype and the verdict comes
+        after the whole backward pass, as in the fp16 mode.  A non-finite norm skips the step.  The schedule is a function of the
+        applied-step count in the block, so skipped steps do not advance it and ``load_optimizer_state_dict`` resumes it."""
         self.model = model
         # SURVEY.md §8(f)-2: encode every DISTINCT item of the batch once (the reference re-encodes duplicates: Zipf-popular
         # items fill many of the B (S + 1) slots) and gather the vectors back to the slots; the slot gradients are
@@ -236,14 +243,25 @@ class TrainStep:
         if graph is None:
             graph = os.environ.get("MOREC_GRAPH", "0") == "1"
         self.graph = bool(graph) and self.device.type == "cuda" and not self.collectives and not self.dedup_items
-        if self.dtype == torch.float16 or loss_scale is not None or self.graph or os.environ.get("MOREC_STEP_PARAMS", "0") == "1":
+        self.max_grad_norm = float(max_grad_norm or 0.0)
+        self.lr_schedule = LrSchedule.coerce(lr_schedule)
+        self._clip = self.max_grad_norm > 0.0 or self.lr_schedule is not None
+        if self.dtype == torch.float16 or loss_scale is not None or self.graph or self._clip or os.environ.get("MOREC_STEP_PARAMS", "0") == "1":
             init = float(loss_scale) if loss_scale is not None else (65536.0 if self.dtype == torch.float16 else 1.0)
             self.sp = ops.StepParams(self.device, init_scale=init, step=0, growth_interval=growth_interval,
                                      dynamic=bool(dynamic_loss_scale) and (self.dtype == torch.float16 or loss_scale is not None))
         # A step block WITHOUT loss scaling (bf16 / fp32 under graph capture): nothing can veto the update, so the decision (step count,
         # bias corrections, next dropout seed word) is taken at the START of the step and AdamW may run bucket by bucket under the
         # backward pass as it does without a block.  With scaling the decision needs the whole step's gradients and comes last.
-        self._decide_first = self.sp is not None and not self.sp.dynamic and init == 1.0
+        # Clipping / a schedule: the norm needs the whole step's gradients too, so the verdict comes last whatever the dtype.
+        self._decide_first = self.sp is not None and not self.sp.dynamic and init == 1.0 and not self._clip
+        if self._clip:      # one slot range of the partials buffer per group arena, in group order (every rank folds the same sums in the same order)
+            self._norm_slots, n_slots = [], 0
+            for grp in self.groups:
+                self._norm_slots.append(n_slots)
+                n_slots += ops.StepParams.norm_slots(grp["arena"].numel)
+            self._n_partials = n_slots
+            self.sp.reserve_partials(n_slots)
         self._decided = False
         # one captured graph (+ its static inputs and its share of the graph memory pool) per input shape, at most ``graph_max`` of them
         # (MOREC_GRAPH_MAX, default 8): shapes beyond that run as plain eager steps instead of growing the pool without bound
@@ -748,6 +766,17 @@ class TrainStep:
         self.flush()
         return int(self.sp.host().step) if self.sp is not None else self.step_count
 
+    def step_stats(self):
+        """``(grad_norm, clip_coef, lr_mult)`` of the last step (synchronises: for the logging site, never inside the step); ``None`` when
+        neither clipping nor a schedule is on."""
+        if not self._clip:
+            return None
+        self.flush()
+        h = self.sp.host()
+        from . import _lib
+        return (self.sp.grad_norm(), float(h.clip_coef) if h.ctl_flags & _lib.SP_CLIP else 1.0,
+                float(h.lr_mult) if h.ctl_flags & _lib.SP_LR_MULT else 1.0)
+
     def scaler_state_dict(self):
         """``GradScaler.state_dict()`` of the device block (``T/run.py`` never saves it; offered for exact resumption)."""
         if self.sp is None:
@@ -837,9 +866,14 @@ class TrainStep:
             self._decided = False
         elif self.sp is not None:
             self.flush()      # (a deferred update of the previous step that nothing has waited for yet)
-            for grp in self.groups:
-                self.sp.check_finite_(grp["arena"].grad)
-            self.sp.decide_(self.betas[0], self.betas[1])
+            if self._clip:      # the same single read of every gradient, with the sum of squares riding on it; then verdict + clip coefficient + LR multiplier
+                for grp, slot in zip(self.groups, self._norm_slots):
+                    self.sp.norm_check_(grp["arena"].grad, slot)
+                self.sp.decide_ex_(self.betas[0], self.betas[1], self._n_partials, self.max_grad_norm, self.lr_schedule)
+            else:
+                for grp in self.groups:
+                    self.sp.check_finite_(grp["arena"].grad)
+                self.sp.decide_(self.betas[0], self.betas[1])
             side = engine.WgradStream.get(self.device) if (self.defer_update and self._in_step) else None
             if side is None:
                 for grp in self.groups:

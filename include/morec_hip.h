@@ -610,11 +610,36 @@ typedef struct {
     float inv_scale;        /* 1 / S of the step being applied: what morec_adamw_sp multiplies the gradients with */
     float bc1, bc2;         /* 1 - beta1^step, 1 - beta2^step of the step being applied */
     int32_t apply;          /* decision of the last morec_step_decide: 1 = update, 0 = skip */
-    int32_t pad0;
+    int32_t ctl_flags;      /* MOREC_SP_* bits: which of clip_coef / lr_mult the last decision set.  0 (every block before morec_step_decide_ex
+                             * existed, every checkpoint, morec_step_params_init, morec_step_decide): morec_adamw_sp reads neither */
     uint64_t drop_seed;       /* splitmix64 state, advanced by every morec_step_decide */
     uint64_t drop_seed_mixed; /* its output: the word morec_dropout_seed_source(&sp->drop_seed_mixed) feeds to the dropout kernels */
-    int32_t reserved[2];
+    float clip_coef;        /* min(1, max_norm / (grad_norm + 1e-6)) of the step being applied; read only under MOREC_SP_CLIP */
+    float lr_mult;          /* LR multiplier of the step being applied (0 is a legitimate value); read only under MOREC_SP_LR_MULT */
 } morec_step_params;
+#define MOREC_SP_CLIP 1
+#define MOREC_SP_LR_MULT 2
+/* ZERO-WORDS RULE: ctl_flags, clip_coef and lr_mult occupy the three words that used to be padding.  A block in which they are zero behaves
+ * exactly as it did before they had names; size (64 bytes) and the offset of every other field are unchanged. */
+
+/* LR schedule of morec_step_decide_ex.  The multiplier of the optimizer step with 0-based index t (t = steps APPLIED before it: a skipped
+ * step does not advance the schedule; the first step has t = 0, as torch's LambdaLR numbers them), W = warmup_steps, T = total_steps,
+ * r = min_ratio:
+ *     t < W                  : t / W
+ *     otherwise, CONSTANT    : 1
+ *     otherwise              : q = min(1, (t - W) / max(1, T - W));
+ *                    LINEAR  : r + (1 - r) (1 - q)
+ *                    COSINE  : r + (1 - r) (1 + cos(pi q)) / 2
+ * (it holds at r from t = T on).  Evaluated in double, stored as float. */
+#define MOREC_LR_CONSTANT 0
+#define MOREC_LR_LINEAR 1
+#define MOREC_LR_COSINE 2
+typedef struct {
+    int32_t kind;          /* MOREC_LR_* */
+    int32_t warmup_steps;  /* >= 0 */
+    int32_t total_steps;   /* >= warmup_steps for LINEAR / COSINE; unused for CONSTANT */
+    float min_ratio;       /* in [0, 1] */
+} morec_lr_schedule;
 /* Process-wide dropout seed source (state item 4 of the list at the top of this file): dev_u64 = a DEVICE uint64 (8-byte aligned) that every
  * dropout / DropPath kernel XORs into the two halves of its seed argument at kernel entry, NULL = none (the default).  The mask of a launch
  * is then a function of (seed argument, *dev_u64): a captured graph of the step -- whose seed arguments are frozen at capture -- draws
@@ -631,10 +656,34 @@ int morec_step_params_init(morec_step_params* sp, float init_scale, int step, vo
 /* sp->found_inf |= any element of grad[0 .. n) is inf or NaN   (GradScaler.unscale_'s found_inf; the division by S is left to AdamW) */
 int morec_grad_check_finite(const float* grad, size_t n, morec_step_params* sp, void* stream);
 /* GradScaler.step + update on the device: apply = !found_inf; on apply: ++step, bias corrections (formed in double), growth
- * bookkeeping; on skip: ++skipped, scale *= backoff_factor; found_inf is cleared.  dynamic == 0 keeps the scale fixed. */
+ * bookkeeping; on skip: ++skipped, scale *= backoff_factor; found_inf is cleared.  dynamic == 0 keeps the scale fixed.  ctl_flags is
+ * cleared (no clip coefficient, no LR multiplier: morec_step_decide_ex sets them). */
 int morec_step_decide(morec_step_params* sp, float beta1, float beta2, float growth_factor, float backoff_factor,
                       int growth_interval, int dynamic, void* stream);
+/* Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_) and an LR schedule without a host scalar in the step.  Protocol:
+ * morec_grad_norm_check per gradient arena in place of morec_grad_check_finite, morec_step_decide_ex in place of morec_step_decide.
+ *
+ * morec_grad_norm_blocks(n): slots of `partials` an arena of n elements fills -- a function of n alone.
+ * morec_grad_norm_check: found_inf exactly as morec_grad_check_finite, and partials[slot + b] = block b's share of sum((grad[i] / S)^2), S =
+ * sp->loss_scale (the gradients are unscaled BEFORE squaring).  Bit-reproducible: no floating-point atomics, fixed order of additions in the
+ * thread, the wavefront and the block, every slot written by one lane.  Padding inside the arena must be zero.  n_slots = capacity of
+ * `partials`; slot + morec_grad_norm_blocks(n) > n_slots, or a NULL pointer: MOREC_E_ARG; n % 4 or grad off 16 bytes: MOREC_E_ALIGN; all
+ * before anything is launched. */
+size_t morec_grad_norm_blocks(size_t n);
+int morec_grad_norm_check(const float* grad, size_t n, morec_step_params* sp, float* partials, size_t slot, size_t n_slots, void* stream);
+/* morec_step_decide plus: total = partials[0] + ... + partials[n_partials - 1] (ascending, in double); grad_norm = sqrt(total), written to
+ * *grad_norm_out (DEVICE float, may be NULL: logging only).  A non-finite total counts as found_inf -- the step is skipped and the scale
+ * backs off (torch's clip_grad_norm_ would scale the gradients by NaN / 0 instead; under GradScaler the step is skipped there too).
+ * max_norm > 0: clip_coef = min(1, max_norm / (grad_norm + 1e-6)) and MOREC_SP_CLIP; max_norm <= 0: no clipping (partials may then be NULL
+ * with n_partials 0).  sched != NULL (HOST struct, read during the call): lr_mult by the formula at morec_lr_schedule, with t = sp->step
+ * before this step's increment, and MOREC_SP_LR_MULT; NULL: no schedule.  With max_norm <= 0, sched NULL and no partials it decides what
+ * morec_step_decide decides. */
+int morec_step_decide_ex(morec_step_params* sp, float beta1, float beta2, float growth_factor, float backoff_factor, int growth_interval,
+                         int dynamic, const float* partials, size_t n_partials, float max_norm, const morec_lr_schedule* sched,
+                         float* grad_norm_out, void* stream);
 /* morec_adamw with step count / bias corrections / gradient scale (1 / S) read from *sp; does nothing when sp->apply == 0.
+ * Under MOREC_SP_CLIP the gradient scale is clip_coef / S; under MOREC_SP_LR_MULT the step size AND the weight decay use lr * lr_mult (as
+ * torch under a scheduler).  Flags clear, or both factors 1.0f: the same bits as without them.
  * shadow (may be NULL): 16-bit copy of the updated parameters in shadow_dtype (MOREC_BF16 | MOREC_F16). */
 int morec_adamw_sp(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow, int shadow_dtype, size_t n,
                    float lr, float beta1, float beta2, float eps, float weight_decay, const morec_step_params* sp, void* stream);
