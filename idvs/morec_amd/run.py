@@ -9,15 +9,22 @@ without the fp16 GradScaler, which bf16 does not need) and ``--fused_step`` (``t
 Checkpoints: reference format (``epoch-N.pt``), saved by rank 0 when the validation Hit@10 improves (modal runs only, as
 ``T/run.py:265-267``), resumed with ``--load_ckpt_name epoch-N.pt`` (``T/run.py:130-139,193-195``; early stopping is switched off
 on a resumed run, like there); ``--mode test`` evaluates a checkpoint on the test split (``T/run_test.py:115-128``).  Both
-optimisation paths read and write the SAME optimizer state (``TrainStep.optimizer_state_dict``)."""
+optimisation paths read and write the SAME optimizer state (``TrainStep.optimizer_state_dict``).
+
+Three drivers -- ``train()``, ``train_dssm()`` (``--arch dssm``) and ``train_two_stage()`` (``--arch two_stage`` / ``id_two_stage``) -- keep
+loops of their own (their docstrings say why) and share the parts that are the same: ``build_text_tower``, ``resume_checkpoint``,
+``run_checkpoint_mode``, ``restore_optimizer_and_scaler``, ``autograd_step``, ``epoch_source`` / ``epoch_neg_rng``, ``EarlyStop`` and
+``data_utils.save_model``."""
 from __future__ import annotations
 
 import logging
+import math
 import os
 import queue
 import random
 import threading
 import time
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -27,6 +34,7 @@ from torch.nn.parallel import DistributedDataParallel as DDP
 
 from .data_utils import (collate_bce_batch, collate_train_batch, epoch_batches, eval_model, get_checkpoint, get_item_embeddings,
                          load_model, read_behaviors, read_news, save_model)
+from .data_utils.utils import _unwrap
 from .model import BceModel, BertShape, DssmModel, HipBertModel, Model
 from .model.swin import HipSwinForImageClassification
 from .swin_engine import SwinShape
@@ -328,10 +336,6 @@ def synthetic_new_item_docs(args, item_num, n_new=12, seed=1357):
     return docs
 
 
-def _unwrap(model):
-    return model.module if hasattr(model, "module") else model
-
-
 def run_eval_special(model, item_content, catalogue, batch_size, item_num, use_modal, vision, args, local_rank):
     """``--mode test --cold_seqs ...``: the cold-start / new-item protocol of ``data_utils/special.py`` on the loaded checkpoint.  The
     new items' vectors come from the item tower over their content (text: ``get_doc_input_bert`` tables, vision: ``--new_lmdb_data``
@@ -456,6 +460,21 @@ def _load_pretrained_text_tower(bert, args):
     return False
 
 
+def build_text_tower(args, freeze=True):
+    """The text tower of ``--bert_model_load`` with its pretrained weights (``T/run.py:51-75``); sets ``args.word_embedding_dim``.
+    ``freeze``: the first ``freeze_paras_before`` parameters and the pooler do not train (stage 1 of the two-stage drivers runs the
+    tower without gradients and leaves the flags alone)."""
+    shape = BertShape.named(args.bert_model_load)
+    args.word_embedding_dim = shape.hidden_size
+    bert = HipBertModel(shape)
+    if freeze:
+        for index, (name, param) in enumerate(bert.named_parameters()):   # T/run.py:73-75
+            if index < args.freeze_paras_before or name in ("pooler.dense.weight", "pooler.dense.bias"):
+                param.requires_grad = False
+    _load_pretrained_text_tower(bert, args)
+    return bert
+
+
 def load_dataset(args, use_modal, vision):
     """The data of a SASRec-family run -- ``--synthetic N``, the text tables (tokenizer), the vision catalogue (LMDB) or the bare ids -- as
     ``(item_num, item_content, users_train, users_valid, users_test, hist_valid, hist_test, pop, catalogue)``."""
@@ -532,6 +551,111 @@ def _log_step_control(src):
         Log.info("step control: last gradient norm %.4g, lr multiplier %.4g" % (norm, src.lr_mult()))
 
 
+def resume_checkpoint(model, candidate_dirs, args):
+    """``--load_ckpt_name`` (``T/run.py:130-139``; BEFORE arenas / DDP are built): the file from the first of ``candidate_dirs`` that
+    holds it, read ONCE, into the model; the torch / device RNG states and the call counter of the library's counter-based dropout /
+    DropPath streams continue where they stopped.  Returns ``(the checkpoint's dict, its epoch)``, ``(None, 0)`` without the flag."""
+    if "None" in args.load_ckpt_name:
+        return None, 0
+    ckpt_path = next((p for p in (get_checkpoint(d, args.load_ckpt_name) for d in candidate_dirs) if p is not None), None)
+    if ckpt_path is None:
+        where = f"under {candidate_dirs[0]}" if len(candidate_dirs) == 1 else f"under any of {list(candidate_dirs)}"
+        raise SystemExit(f"--load_ckpt_name {args.load_ckpt_name}: not found {where}")
+    ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=False)
+    start_epoch = load_model(model, ckpt_path, ckpt=ckpt)
+    if ckpt.get("rng_state") is not None:
+        torch.set_rng_state(ckpt["rng_state"])
+    if ckpt.get("cuda_rng_state") is not None and torch.cuda.is_available():
+        torch.cuda.set_rng_state(ckpt["cuda_rng_state"])
+    if ckpt.get("morec_drop_calls") is not None:
+        model._drop_calls = int(ckpt["morec_drop_calls"])
+    Log.info("model loaded from %s (epoch %d)" % (ckpt_path, start_epoch))
+    return ckpt, start_epoch
+
+
+def run_checkpoint_mode(args, model, ckpt, content, catalogue, hist_test, users_test, item_num, model_dir, local_rank, *, use_modal,
+                        special_modal, special_vision, special_catalogue=None):
+    """``--mode test`` (``T/run_test.py:115-128``; with ``--cold_seqs`` the cold-start / new-item protocol too) and ``--mode recommend`` on
+    the loaded checkpoint.  ``content``: what the catalogue is encoded from (item table | feature table); ``special_*``: how
+    ``run_eval_special`` sees the tower, and the catalogue it resolves item names in when that is not ``catalogue``."""
+    if ckpt is None:
+        raise SystemExit(f"--mode {args.mode} needs --load_ckpt_name epoch-N.pt")
+    if args.mode == "recommend":
+        out_path = args.recommend_out if args.recommend_out != "None" else os.path.join(model_dir, "recommend_top%d.tsv" % args.topk)
+        run_recommend(model, content, users_test, catalogue, 512, use_modal, args, out_path, local_rank)
+        return 0.0
+    hit10 = run_eval(model, content, hist_test, users_test, 512, item_num, use_modal, args, "test", local_rank)
+    if getattr(args, "cold_seqs", "None") != "None":
+        run_eval_special(model, content, special_catalogue or catalogue, 512, item_num, special_modal, special_vision, args, local_rank)
+    return hit10
+
+
+def restore_optimizer_and_scaler(optimizer, args, ckpt):
+    """The autograd paths' optimizer state (``T/run.py:193-195``) and GradScaler (``T/run.py:210``: engaged for the fp16 compute dtypes --
+    bf16 / fp32 gradients need no scaling; the reference never saves its scaler: an empty dict there) from a resumed checkpoint.
+    Returns the scaler or None."""
+    if ckpt is not None and ckpt.get("optimizer") is not None:
+        optimizer.load_state_dict(ckpt["optimizer"])
+    if args.compute_dtype not in ("fp16", "fp16_res32"):
+        return None
+    scaler = torch.amp.GradScaler("cuda", enabled=True)
+    if ckpt is not None and ckpt.get("scaler_state"):
+        scaler.load_state_dict(ckpt["scaler_state"])
+    return scaler
+
+
+def autograd_step(forward, optimizer, scaler, ctl, *inputs):
+    """One step of the autograd paths (``T/run.py:241-247``): ``forward(*inputs)`` -> loss, backward (scaled under a GradScaler),
+    ``ctl.step()`` = scaler.step + update | optimizer.step, behind --max_grad_norm / --lr_schedule when given.  Returns the detached
+    loss; nothing here reads the device."""
+    optimizer.zero_grad()
+    loss = forward(*inputs)
+    (scaler.scale(loss) if scaler is not None else loss).backward()
+    ctl.step()
+    return loss.detach()
+
+
+def epoch_neg_rng(rank, now_epoch):
+    """The epoch's negative-sampling generator: the run's seed, the rank and the epoch -- a resumed run draws what it would have drawn."""
+    return np.random.default_rng([torch.initial_seed() % (1 << 63), rank, now_epoch])
+
+
+def epoch_source(make_batch, batches, depth):
+    """``(b, batch)`` pairs of an epoch: built ahead by a ``BatchPrefetcher`` (``depth`` > 0; the caller closes it) or inline.
+    Returns ``(source, feeder | None)``."""
+    feeder = BatchPrefetcher(make_batch, batches, depth) if depth > 0 else None
+    return (feeder if feeder is not None else ((b_, make_batch(idx_)) for b_, idx_ in enumerate(batches))), feeder
+
+
+@dataclass
+class EarlyStop:
+    """The validation record of a run (``T/run.py:291-304``): the best Hit@10 and its epoch, and the count of validations without an
+    improvement -- MORE than ``gap`` of them (10; 6 for vision: ``T/run.py:221`` / ``V/run.py:185``) end the run, unless it was resumed
+    (``enabled`` False).  ``early_stop_epoch`` starts as the run's ``--epoch``."""
+    gap: int
+    enabled: bool
+    early_stop_epoch: int
+    best: float = 0.0
+    max_epoch: int = 0
+    early_stop_count: int = 0
+    need_break: bool = False
+
+    def update(self, hit10, now_epoch) -> bool:
+        """True when ``hit10`` is a new best (the caller saves)."""
+        self.need_break = False
+        if hit10 > self.best:
+            self.best, self.max_epoch, self.early_stop_count = hit10, now_epoch, 0
+            return True
+        self.early_stop_count += 1
+        if self.early_stop_count > self.gap:
+            self.need_break = self.enabled
+            self.early_stop_epoch = now_epoch
+        return False
+
+    def log(self):
+        Log.info("max eval Hit10 %.5f in epoch %d; early stop in epoch %d" % (self.best * 100, self.max_epoch, self.early_stop_epoch))
+
+
 def train(args, use_modal, local_rank):
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -549,15 +673,7 @@ def train(args, use_modal, local_rank):
             if index < args.freeze_paras_before:
                 param.requires_grad = False
     elif use_modal:
-        shape = BertShape.named(args.bert_model_load)
-        args.word_embedding_dim = shape.hidden_size              # T/run.py:55-72
-        bert = HipBertModel(shape)
-        pooler = {"pooler.dense.weight", "pooler.dense.bias"}
-        for index, (name, param) in enumerate(bert.named_parameters()):   # T/run.py:73-75
-            if index < args.freeze_paras_before or name in pooler:
-                param.requires_grad = False
-    if use_modal and not vision:
-        _load_pretrained_text_tower(bert, args)
+        bert = build_text_tower(args)
     bce = args.loss == "bce"
     fusion = check_fusion_args(args) if use_modal else None
     if bce and (args.fused_step or vision):
@@ -565,39 +681,12 @@ def train(args, use_modal, local_rank):
     model = (BceModel(args, item_num, use_modal, bert) if bce else Model(args, item_num, use_modal, bert, pop)).to(local_rank)
     users = list(users_train.keys())
     model_dir = model_dir_of(args, world)
-    ckpt, start_epoch, is_early_stop = None, 0, True
-    if "None" not in args.load_ckpt_name:                               # T/run.py:130-139: BEFORE the arenas / DDP are built
-        ckpt_path = None
-        for cand in model_dir_candidates(args, world):      # the reference's directory first, then the older spellings
-            ckpt_path = get_checkpoint(cand, args.load_ckpt_name)
-            if ckpt_path is not None:
-                break
-        if ckpt_path is None:
-            raise SystemExit(f"--load_ckpt_name {args.load_ckpt_name}: not found under any of {model_dir_candidates(args, world)}")
-        start_epoch = load_model(model, ckpt_path)
-        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=False)
-        if ckpt.get("rng_state") is not None:
-            torch.set_rng_state(ckpt["rng_state"])
-        if ckpt.get("cuda_rng_state") is not None and torch.cuda.is_available():
-            torch.cuda.set_rng_state(ckpt["cuda_rng_state"])
-        if ckpt.get("morec_drop_calls") is not None:      # the library's counter-based dropout / DropPath streams continue where they stopped
-            model._drop_calls = int(ckpt["morec_drop_calls"])
-        is_early_stop = False
-        Log.info("model loaded from %s (epoch %d)" % (ckpt_path, start_epoch))
-    if args.mode == "test":                                             # T/run_test.py:115-128
-        if ckpt is None:
-            raise SystemExit("--mode test needs --load_ckpt_name epoch-N.pt")
-        hit10 = run_eval(model, item_content, hist_test, users_test, 512, item_num, use_modal, args, "test", local_rank)
-        if getattr(args, "cold_seqs", "None") != "None":
-            run_eval_special(model, item_content, catalogue, 512, item_num, use_modal, vision, args, local_rank)
-        return hit10
-    if args.mode == "recommend":
-        if ckpt is None:
-            raise SystemExit("--mode recommend needs --load_ckpt_name epoch-N.pt")
-        out_path = args.recommend_out if args.recommend_out != "None" else os.path.join(model_dir, "recommend_top%d.tsv" % args.topk)
-        run_recommend(model, item_content, users_test, catalogue, 512, use_modal, args, out_path, local_rank)
-        return 0.0
-    stepper, optimizer = None, None
+    # the reference's directory first, then the older spellings
+    ckpt, start_epoch = resume_checkpoint(model, model_dir_candidates(args, world), args)
+    if args.mode in ("test", "recommend"):
+        return run_checkpoint_mode(args, model, ckpt, item_content, catalogue, hist_test, users_test, item_num, model_dir, local_rank,
+                                   use_modal=use_modal, special_modal=use_modal, special_vision=vision)
+    stepper, optimizer, scaler = None, None, None
     total_steps = args.epoch * len(epoch_batches(len(users), args.batch_size, world, rank, 1))      # --lr_schedule: epochs x steps per epoch
     if args.fused_step:
         stepper = TrainStep(model, lr=args.lr, fine_tune_lr=args.fine_tune_lr, l2_weight=args.l2_weight,
@@ -620,17 +709,9 @@ def train(args, use_modal, local_rank):
         groups = [{"params": [p for n, p in named if tower(n)], "lr": args.fine_tune_lr, "weight_decay": args.fine_tune_l2_weight},
                   {"params": [p for n, p in named if not tower(n)], "lr": args.lr, "weight_decay": args.l2_weight}]
         optimizer = optim.AdamW([g for g in groups if g["params"]])   # T/run.py:159-162
-        if ckpt is not None and ckpt.get("optimizer") is not None:
-            optimizer.load_state_dict(ckpt["optimizer"])
-    # T/run.py:210: `scaler = torch.cuda.amp.GradScaler()` -- engaged for the fp16 compute dtype (bf16 / fp32 gradients need no scaling);
-    # the fused step keeps the same protocol in its device block (TrainStep.sp)
-    scaler = torch.amp.GradScaler("cuda", enabled=True) if (optimizer is not None and args.compute_dtype in ("fp16", "fp16_res32")) else None
-    if scaler is not None and ckpt is not None and ckpt.get("scaler_state"):
-        scaler.load_state_dict(ckpt["scaler_state"])
+        scaler = restore_optimizer_and_scaler(optimizer, args, ckpt)      # (the fused step keeps the GradScaler protocol in its device block: TrainStep.sp)
     ctl = autograd_step_control(args, optimizer, scaler, total_steps) if optimizer is not None else None
-    best, step = 0.0, 0
-    max_epoch, early_stop_epoch, early_stop_count = 0, args.epoch, 0
-    early_stop_gap = 6 if vision else 10                               # T/run.py:221 / V/run.py:185
+    stop, step = EarlyStop(6 if vision else 10, ckpt is None, args.epoch), 0
     on_device = hasattr(item_content, "device_batch")       # LMDB catalogue: the collate itself issues device work (decode -> H2D -> resize)
     n_workers = 0 if (bce or on_device) else max(0, int(getattr(args, "collate_workers", 0)))
     depth = 0 if on_device else int(getattr(args, "prefetch", 2))
@@ -660,8 +741,7 @@ def train(args, use_modal, local_rank):
             sampler.set_epoch(now_epoch, len(batches))
             source = enumerate(loader)
         else:
-            feeder = BatchPrefetcher(make_batch, batches, depth) if depth > 0 else None
-            source = feeder if feeder is not None else ((b_, make_batch(idx_)) for b_, idx_ in enumerate(batches))
+            source, feeder = epoch_source(make_batch, batches, depth)
         t0, loss_acc, t_mark, n_mark = time.time(), None, None, 0
         b = -1
         # Vision catalogue held as uint8 arrays on the host (--images_npy / synthetic; not the LMDB, whose collate does device work itself):
@@ -676,21 +756,6 @@ def train(args, use_modal, local_rank):
                 torch.cuda.synchronize()
                 t_mark, n_mark = time.time(), 0
             n_mark += len(batches[b])
-            if bce:
-                items, log_mask = items.to(local_rank, non_blocking=True), log_mask.to(local_rank, non_blocking=True)
-                items = items.view(-1, items.size(-1)) if use_modal else items.view(-1)
-                optimizer.zero_grad()
-                if fusion:      # bce_text/id_plus_mo-end2end/run.py: ids and content
-                    loss = wrapped(ids.to(local_rank, non_blocking=True).view(-1), items, log_mask, local_rank)
-                else:
-                    loss = wrapped(items, log_mask, local_rank)
-                (scaler.scale(loss) if scaler is not None else loss).backward()      # T/run.py:243-247
-                ctl.step()      # scaler.step + update | optimizer.step, behind --max_grad_norm / --lr_schedule when given
-                loss_acc = loss.detach() if loss_acc is None else loss_acc + loss.detach()
-                step += 1
-                if args.max_steps and step >= args.max_steps:
-                    break
-                continue
             pack = _to_device(pack, local_rank)
             img_slot = None
             if img_feed is not None and items.dtype == torch.uint8 and not items.is_cuda:
@@ -704,8 +769,11 @@ def train(args, use_modal, local_rank):
                 items = img_feed.take(img_slot)
                 ids, log_mask = ids.to(local_rank, non_blocking=True), log_mask.to(local_rank, non_blocking=True)
             else:
-                ids, items, log_mask = (ids.to(local_rank, non_blocking=True), items.to(local_rank, non_blocking=True),
-                                        log_mask.to(local_rank, non_blocking=True))
+                dev = lambda t: None if t is None else t.to(local_rank, non_blocking=True)
+                if bce:      # content first; ids travel with a fusion tower only (bce_text/id_plus_mo-end2end/run.py: ids and content)
+                    items, log_mask, ids = dev(items), dev(log_mask), dev(ids)
+                else:
+                    ids, items, log_mask = dev(ids), dev(items), dev(log_mask)
                 if vision:
                     items = items.view(-1, *items.shape[-3:])                # [B*(S+1), R, R, 3] uint8 (V/run.py:203 views to NCHW floats)
                 else:
@@ -714,11 +782,8 @@ def train(args, use_modal, local_rank):
                 loss = stepper.global_loss(stepper.step_graphed(ids.view(-1), items, log_mask, token_packing=pack))    # pooled negatives: a rank's step returns its SHARE; one rank: hipGraph replay per input shape
                 if img_slot is not None:
                     img_feed.release(img_slot)
-            else:
-                optimizer.zero_grad()
-                loss = wrapped(ids.view(-1), items, log_mask, local_rank)
-                (scaler.scale(loss) if scaler is not None else loss).backward()      # T/run.py:243-247
-                ctl.step()      # scaler.step + update | optimizer.step, behind --max_grad_norm / --lr_schedule when given
+            else:      # (BceModel without a fusion tower takes no ids)
+                loss = autograd_step(wrapped, optimizer, scaler, ctl, *(() if ids is None else (ids.view(-1),)), items, log_mask, local_rank)
             loss_acc = loss.detach() if loss_acc is None else loss_acc + loss.detach()
             step += 1
             if args.max_steps and step >= args.max_steps:
@@ -729,14 +794,14 @@ def train(args, use_modal, local_rank):
         t_end = time.time()
         dt = t_end - t0
         mean_loss = float(loss_acc.item()) / max(1, b + 1)
-        if torch.isnan(torch.tensor(mean_loss)):                        # T/run.py:249-251
+        if math.isnan(mean_loss):                                       # T/run.py:249-251
             Log.info("NaN loss, stopping")
             break
         n_seq = sum(len(x) for x in batches[:b + 1]) * world
         Log.info("epoch %d: %d steps, mean loss %.5f, %.1f user-seq/s" % (now_epoch, b + 1, mean_loss, n_seq / dt))
         if t_mark is not None and n_mark > 0:
             steady = n_mark * world / max(t_end - t_mark, 1e-9)
-            train.last_steady_rate = steady          # (read by bench.py's run.py-vs-bench comparison)
+            train.last_steady_rate = steady          # (for a caller that measures the driver: the log line's figure without parsing the log)
             Log.info("epoch %d: steady state (after step %d): %.1f user-seq/s, %s" % (now_epoch, int(getattr(args, "steady_after", 10)), steady,
                                                                                     ("%d collate worker processes" % n_workers) if n_workers > 0 else ("collate thread, depth %d" % depth)))
             if feeder is not None and feeder.n:
@@ -746,23 +811,15 @@ def train(args, use_modal, local_rank):
             Log.info("loss scaler: scale %g, %d steps applied, %d skipped" % (h_.loss_scale, h_.step, h_.skipped))
         _log_step_control(stepper if stepper is not None else ctl)
         hit10 = run_eval(wrapped, item_content, hist_valid, users_valid, 512, item_num, use_modal, args, "valid", local_rank)
-        need_break = False
-        if hit10 > best:                                                # T/run.py:291-304
-            best, max_epoch, early_stop_count = hit10, now_epoch, 0
-            if use_modal and rank == 0:                                 # T/run.py:265-267: modal runs only, rank 0 only
-                save_model(now_epoch, model, model_dir, stepper if stepper is not None else optimizer, torch.get_rng_state(),
-                           torch.cuda.get_rng_state() if torch.cuda.is_available() else None,
-                           stepper if (stepper is not None and stepper.sp is not None) else scaler, Log,      # loss-scaler state: exact fp16 resumption
-                           extra={"morec_drop_calls": int(getattr(model, "_drop_calls", 0))})
-        else:
-            early_stop_count += 1
-            if early_stop_count > early_stop_gap:
-                need_break = is_early_stop
-                early_stop_epoch = now_epoch
-        if need_break or (args.max_steps and step >= args.max_steps):
+        if stop.update(hit10, now_epoch) and use_modal and rank == 0:   # T/run.py:265-267: modal runs only, rank 0 only
+            save_model(now_epoch, model, model_dir, stepper if stepper is not None else optimizer, torch.get_rng_state(),
+                       torch.cuda.get_rng_state() if torch.cuda.is_available() else None,
+                       stepper if (stepper is not None and stepper.sp is not None) else scaler, Log,      # loss-scaler state: exact fp16 resumption
+                       extra={"morec_drop_calls": int(getattr(model, "_drop_calls", 0))})
+        if stop.need_break or (args.max_steps and step >= args.max_steps):
             break
-    Log.info("max eval Hit10 %.5f in epoch %d; early stop in epoch %d" % (best * 100, max_epoch, early_stop_epoch))
-    return best
+    stop.log()
+    return stop.best
 
 
 def dssm_model_dir(args):
@@ -795,8 +852,9 @@ def train_dssm(args, use_modal, local_rank):
     (``run.py:251-253`` there).  Evaluation runs in chunks of 512 rows, the constant ``train()`` and the reference use.  The negatives come
     from a numpy generator seeded from the run's seed (``torch.initial_seed()``), the rank and the epoch -- a resumed run draws the
     epoch's negatives it would have drawn.  This is a loop of its own beside ``train()``: that one iterates users and steps once per
-    sequence batch, this one iterates pairs, validates inside the epoch and names its files differently; they share the loaders of
-    pretrained weights, ``epoch_batches``, ``BatchPrefetcher`` and ``load_model``."""
+    sequence batch, this one iterates pairs, validates inside the epoch and names its files differently; they share the tower
+    construction, resume, optimizer / GradScaler restore, the autograd step, the epoch's batch source and negatives generator, the
+    early-stop record and ``save_model`` (the module docstring names the functions), and ``epoch_batches``."""
     from .data_utils import dssm as dd
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -826,32 +884,9 @@ def train_dssm(args, use_modal, local_rank):
         user_num, item_num, _, users_train, _, train_pairs, valid_pairs, test_pairs, hist_valid, hist_test = dd.read_behaviors(
             os.path.join(args.root_data_dir, args.dataset, args.behaviors), a, b, args.min_seq_len, S, Log)
         item_content = np.arange(item_num + 1)
-    bert = None
-    if use_modal:
-        shape = BertShape.named(args.bert_model_load)
-        args.word_embedding_dim = shape.hidden_size
-        bert = HipBertModel(shape)
-        for index, (name, param) in enumerate(bert.named_parameters()):
-            if index < args.freeze_paras_before or name in ("pooler.dense.weight", "pooler.dense.bias"):
-                param.requires_grad = False
-        _load_pretrained_text_tower(bert, args)
-    model = DssmModel(args, user_num, item_num, use_modal, bert).to(local_rank)
+    model = DssmModel(args, user_num, item_num, use_modal, build_text_tower(args) if use_modal else None).to(local_rank)
     model_dir = dssm_model_dir(args)
-    ckpt, start_epoch, is_early_stop = None, 0, True
-    if "None" not in args.load_ckpt_name:
-        ckpt_path = get_checkpoint(model_dir, args.load_ckpt_name)
-        if ckpt_path is None:
-            raise SystemExit(f"--load_ckpt_name {args.load_ckpt_name}: not found under {model_dir}")
-        start_epoch = load_model(model, ckpt_path)
-        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=False)
-        if ckpt.get("rng_state") is not None:
-            torch.set_rng_state(ckpt["rng_state"])
-        if ckpt.get("cuda_rng_state") is not None and torch.cuda.is_available():
-            torch.cuda.set_rng_state(ckpt["cuda_rng_state"])
-        if ckpt.get("morec_drop_calls") is not None:
-            model._drop_calls = int(ckpt["morec_drop_calls"])
-        is_early_stop = False
-        Log.info("model loaded from %s (epoch %d)" % (ckpt_path, start_epoch))
+    ckpt, start_epoch = resume_checkpoint(model, [model_dir], args)
     if args.mode == "test":
         if ckpt is None:
             raise SystemExit("--mode test needs --load_ckpt_name epoch-N-<label>.pt")
@@ -862,11 +897,7 @@ def train_dssm(args, use_modal, local_rank):
     groups = [{"params": [p for n, p in named if "bert_model" in n], "lr": args.fine_tune_lr, "weight_decay": args.l2_weight},
               {"params": [p for n, p in named if "bert_model" not in n], "lr": args.lr, "weight_decay": args.l2_weight}]
     optimizer = optim.AdamW([g for g in groups if g["params"]])
-    if ckpt is not None and ckpt.get("optimizer") is not None:
-        optimizer.load_state_dict(ckpt["optimizer"])
-    scaler = torch.amp.GradScaler("cuda", enabled=True) if args.compute_dtype in ("fp16", "fp16_res32") else None
-    if scaler is not None and ckpt is not None and ckpt.get("scaler_state"):
-        scaler.load_state_dict(ckpt["scaler_state"])
+    scaler = restore_optimizer_and_scaler(optimizer, args, ckpt)
     step_num = int(np.ceil(len(train_pairs) / world / args.batch_size))
     ctl = autograd_step_control(args, optimizer, scaler, args.epoch * step_num)
     steps_for_log = max(1, int(step_num / max(1, args.logging_num)))
@@ -879,70 +910,56 @@ def train_dssm(args, use_modal, local_rank):
     depth = int(getattr(args, "prefetch", 2))
 
     def save(now_epoch, label):
-        if rank != 0:
-            return
-        os.makedirs(model_dir, exist_ok=True)
-        path = os.path.join(model_dir, f"epoch-{now_epoch}-{label}.pt")
-        torch.save({"model_state_dict": model.state_dict(), "optimizer": optimizer.state_dict(), "rng_state": torch.get_rng_state(),
-                    "cuda_rng_state": torch.cuda.get_rng_state() if torch.cuda.is_available() else None,
-                    "scaler_state": scaler.state_dict() if scaler is not None else {}, "morec_drop_calls": int(model._drop_calls)}, path)
-        Log.info(f"Model saved to {path}")
+        if rank == 0:
+            save_model(now_epoch, model, model_dir, optimizer, torch.get_rng_state(),
+                       torch.cuda.get_rng_state() if torch.cuda.is_available() else None, scaler, Log,
+                       extra={"morec_drop_calls": int(model._drop_calls)}, name=f"epoch-{now_epoch}-{label}.pt")
 
-    best, max_epoch, early_stop_epoch, early_stop_count, step, need_break = 0.0, 0, args.epoch, 0, 0, False
+    stop, step = EarlyStop(10, ckpt is None, args.epoch), 0
     now_epoch, save_label = start_epoch, "0"
     for ep in range(1, args.epoch + 1):
         now_epoch = start_epoch + ep
         model.train()
         batches = epoch_batches(len(train_pairs), args.batch_size, world, rank, now_epoch)
-        neg["rng"] = np.random.default_rng([torch.initial_seed() % (1 << 63), rank, now_epoch])
-        feeder = BatchPrefetcher(make_batch, batches, depth) if depth > 0 else None
-        source = feeder if feeder is not None else ((b_, make_batch(idx_)) for b_, idx_ in enumerate(batches))
+        neg["rng"] = epoch_neg_rng(rank, now_epoch)
+        source, feeder = epoch_source(make_batch, batches, depth)
         t0, loss_acc, n_done = time.time(), None, 0
         for b, (input_user, sample_items, bce_label) in source:
             input_user, sample_items, bce_label = (input_user.to(local_rank, non_blocking=True), sample_items.to(local_rank, non_blocking=True),
                                                    bce_label.to(local_rank, non_blocking=True))
-            optimizer.zero_grad()
-            loss = wrapped(input_user, sample_items, bce_label)
-            (scaler.scale(loss) if scaler is not None else loss).backward()      # T/run.py:243-247
-            ctl.step()      # scaler.step + update | optimizer.step, behind --max_grad_norm / --lr_schedule when given
-            loss_acc = loss.detach() if loss_acc is None else loss_acc + loss.detach()
+            loss = autograd_step(wrapped, optimizer, scaler, ctl, input_user, sample_items, bce_label)
+            loss_acc = loss if loss_acc is None else loss_acc + loss
             step += 1
             n_done = b + 1
             if n_done % steps_for_log == 0:
                 bl = float(loss.detach())
-                if bl != bl:
+                if math.isnan(bl):
                     Log.info("NaN loss, stopping")
-                    need_break = True
+                    stop.need_break = True
                     break
                 Log.info("step %d (%d pairs): batch loss %.5f, mean loss %.5f" % (n_done, n_done * args.batch_size, bl, float(loss_acc) / n_done))
                 _log_step_control(ctl)
             if n_done % steps_for_test == 0:
                 hit10 = run_eval_dssm(wrapped, item_content, hist_valid, valid_pairs, 512, user_num, item_num, use_modal, args, "valid", local_rank)
-                if hit10 > best:
-                    best, max_epoch, early_stop_count = hit10, now_epoch, 0
+                if stop.update(hit10, now_epoch):
                     save_label = str(n_done // steps_for_test)
                     save(now_epoch, save_label)
-                else:
-                    early_stop_count += 1
-                    if early_stop_count > 10:
-                        need_break = is_early_stop
-                        early_stop_epoch = now_epoch
                 model.train()
-            if need_break or (args.max_steps and step >= args.max_steps):
+            if stop.need_break or (args.max_steps and step >= args.max_steps):
                 break
         if feeder is not None:
             feeder.close()
         torch.cuda.synchronize()
         Log.info("epoch %d: %d steps, mean loss %.5f, %.1f pairs/s" % (now_epoch, n_done, float(loss_acc) / max(1, n_done) if loss_acc is not None else 0.0,
                                                                     sum(len(x) for x in batches[:n_done]) * world / max(time.time() - t0, 1e-9)))
-        if need_break or (args.max_steps and step >= args.max_steps):
+        if stop.need_break or (args.max_steps and step >= args.max_steps):
             break
     if args.max_steps and step >= args.max_steps and step % steps_for_test != 0:      # a run cut short still reports a validation
-        best = max(best, run_eval_dssm(wrapped, item_content, hist_valid, valid_pairs, 512, user_num, item_num, use_modal, args, "valid", local_rank))
+        stop.best = max(stop.best, run_eval_dssm(wrapped, item_content, hist_valid, valid_pairs, 512, user_num, item_num, use_modal, args, "valid", local_rank))
     save(now_epoch, save_label)
     run_eval_dssm(wrapped, item_content, hist_test, test_pairs, 512, user_num, item_num, use_modal, args, "test", local_rank)
-    Log.info("max eval Hit10 %.5f in epoch %d; early stop in epoch %d" % (best * 100, max_epoch, early_stop_epoch))
-    return best
+    stop.log()
+    return stop.best
 
 
 def two_stage_model_dir(args):
@@ -977,11 +994,7 @@ def two_stage_features(args, item_content, item_num, vision, local_rank, rank):
         tower = Vit_Encoder(image_net=HipSwinForImageClassification(SwinShape.named(args.CV_model_load), args.embedding_dim),
                             compute_dtype=resolve_dtype(args))
     else:
-        shape = BertShape.named(args.bert_model_load)
-        args.word_embedding_dim = shape.hidden_size
-        bert = HipBertModel(shape)
-        _load_pretrained_text_tower(bert, args)
-        tower = Bert_Encoder(args=args, bert_model=bert)
+        tower = Bert_Encoder(args=args, bert_model=build_text_tower(args, freeze=False))
     table = extract_item_features(tower.to(local_rank), item_content, 512, local_rank)
     del tower
     Log.info("two-stage: stage 1 -- %d x %d item features in %.1f s" % (table.shape[0], table.shape[1], time.time() - t0))
@@ -1032,43 +1045,15 @@ def train_two_stage(args, use_modal, local_rank, id_fusion=False):
     model.set_feature_table(table)
     table = model.feature_table
     users = list(users_train.keys())
-    ckpt, start_epoch, is_early_stop = None, 0, True
-    if "None" not in args.load_ckpt_name:
-        ckpt_path = get_checkpoint(model_dir, args.load_ckpt_name)
-        if ckpt_path is None:
-            raise SystemExit(f"--load_ckpt_name {args.load_ckpt_name}: not found under {model_dir}")
-        start_epoch = load_model(model, ckpt_path)
-        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=False)
-        if ckpt.get("rng_state") is not None:
-            torch.set_rng_state(ckpt["rng_state"])
-        if ckpt.get("cuda_rng_state") is not None and torch.cuda.is_available():
-            torch.cuda.set_rng_state(ckpt["cuda_rng_state"])
-        if ckpt.get("morec_drop_calls") is not None:
-            model._drop_calls = int(ckpt["morec_drop_calls"])
-        is_early_stop = False
-        Log.info("model loaded from %s (epoch %d)" % (ckpt_path, start_epoch))
-    if args.mode == "test":
-        if ckpt is None:
-            raise SystemExit("--mode test needs --load_ckpt_name epoch-N.pt")
-        hit10 = run_eval(model, table, hist_test, users_test, 512, item_num, True, args, "test", local_rank)
-        if getattr(args, "cold_seqs", "None") != "None":      # cold users only: a new item has no row in the feature table
-            if args.synthetic > 0:
-                catalogue = dict(item_name_to_id={synthetic_item_name(i, False): i for i in range(1, item_num + 1)})
-            run_eval_special(model, table, catalogue, 512, item_num, False, False, args, local_rank)
-        return hit10
-    if args.mode == "recommend":
-        if ckpt is None:
-            raise SystemExit("--mode recommend needs --load_ckpt_name epoch-N.pt")
-        out_path = args.recommend_out if args.recommend_out != "None" else os.path.join(model_dir, "recommend_top%d.tsv" % args.topk)
-        run_recommend(model, table, users_test, catalogue, 512, True, args, out_path, local_rank)
-        return 0.0
+    ckpt, start_epoch = resume_checkpoint(model, [model_dir], args)
+    if args.mode in ("test", "recommend"):
+        # --cold_seqs: cold users only (a new item has no row in the feature table), by the text names of a synthetic catalogue
+        names = dict(item_name_to_id={synthetic_item_name(i, False): i for i in range(1, item_num + 1)}) if args.synthetic > 0 else None
+        return run_checkpoint_mode(args, model, ckpt, table, catalogue, hist_test, users_test, item_num, model_dir, local_rank,
+                                   use_modal=True, special_modal=False, special_vision=False, special_catalogue=names)
     wrapped = DDP(model, device_ids=[local_rank], output_device=local_rank) if world > 1 else model
     optimizer = optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.l2_weight)
-    if ckpt is not None and ckpt.get("optimizer") is not None:
-        optimizer.load_state_dict(ckpt["optimizer"])
-    scaler = torch.amp.GradScaler("cuda", enabled=True) if args.compute_dtype in ("fp16", "fp16_res32") else None
-    if scaler is not None and ckpt is not None and ckpt.get("scaler_state"):
-        scaler.load_state_dict(ckpt["scaler_state"])
+    scaler = restore_optimizer_and_scaler(optimizer, args, ckpt)
     ctl = autograd_step_control(args, optimizer, scaler, args.epoch * len(epoch_batches(len(users), args.batch_size, world, rank, 1)))
     neg = {"rng": None}      # re-seeded per epoch; read by the one thread that builds the batches
     make_batch = lambda idx: collate_two_stage_batch(users_train, [users[i] for i in idx], S, item_num, neg["rng"])
@@ -1083,22 +1068,18 @@ def train_two_stage(args, use_modal, local_rank, id_fusion=False):
                        torch.cuda.get_rng_state() if torch.cuda.is_available() else None, scaler, Log,
                        extra={"morec_drop_calls": int(model._drop_calls)})
 
-    best, step, max_epoch, early_stop_epoch, early_stop_count, now_epoch = 0.0, 0, 0, args.epoch, 0, start_epoch
+    stop, step, now_epoch = EarlyStop(10, ckpt is None, args.epoch), 0, start_epoch
     for ep in range(1, args.epoch + 1):
         now_epoch = start_epoch + ep
         model.train()
         batches = epoch_batches(len(users), args.batch_size, world, rank, now_epoch)
-        neg["rng"] = np.random.default_rng([torch.initial_seed() % (1 << 63), rank, now_epoch])
-        feeder = BatchPrefetcher(make_batch, batches, depth) if depth > 0 else None
-        source = feeder if feeder is not None else ((b_, make_batch(idx_)) for b_, idx_ in enumerate(batches))
+        neg["rng"] = epoch_neg_rng(rank, now_epoch)
+        source, feeder = epoch_source(make_batch, batches, depth)
         t0, loss_acc, n_done = time.time(), None, 0
         for b, (ids, log_mask) in source:
             ids, log_mask = ids.to(local_rank, non_blocking=True), log_mask.to(local_rank, non_blocking=True)
-            optimizer.zero_grad()
-            loss = wrapped(ids, None, log_mask, local_rank) if id_fusion else wrapped(ids, log_mask, local_rank)
-            (scaler.scale(loss) if scaler is not None else loss).backward()      # T/run.py:243-247
-            ctl.step()      # scaler.step + update | optimizer.step, behind --max_grad_norm / --lr_schedule when given
-            loss_acc = loss.detach() if loss_acc is None else loss_acc + loss.detach()
+            loss = autograd_step(wrapped, optimizer, scaler, ctl, ids, *((None,) if id_fusion else ()), log_mask, local_rank)
+            loss_acc = loss if loss_acc is None else loss_acc + loss
             step += 1
             n_done = b + 1
             if args.max_steps and step >= args.max_steps:
@@ -1107,27 +1088,20 @@ def train_two_stage(args, use_modal, local_rank, id_fusion=False):
             feeder.close()
         torch.cuda.synchronize()
         mean_loss = float(loss_acc) / max(1, n_done) if loss_acc is not None else 0.0
-        if mean_loss != mean_loss:
+        if math.isnan(mean_loss):
             Log.info("NaN loss, stopping")
             break
         Log.info("epoch %d: %d steps, mean loss %.5f, %.1f user-seq/s" %
                  (now_epoch, n_done, mean_loss, sum(len(x) for x in batches[:n_done]) * world / max(time.time() - t0, 1e-9)))
         _log_step_control(ctl)
         hit10 = run_eval(wrapped, table, hist_valid, users_valid, 512, item_num, True, args, "valid", local_rank)
-        need_break = False
-        if hit10 > best:
-            best, max_epoch, early_stop_count = hit10, now_epoch, 0
+        if stop.update(hit10, now_epoch):
             save(now_epoch)
-        else:
-            early_stop_count += 1
-            if early_stop_count > 10:
-                need_break = is_early_stop
-                early_stop_epoch = now_epoch
-        if need_break or (args.max_steps and step >= args.max_steps):
+        if stop.need_break or (args.max_steps and step >= args.max_steps):
             break
     save(now_epoch)      # run.py:189-190 of the two-stage packages: the final weights, whatever the validation said
-    Log.info("max eval Hit10 %.5f in epoch %d; early stop in epoch %d" % (best * 100, max_epoch, early_stop_epoch))
-    return best
+    stop.log()
+    return stop.best
 
 
 def main(argv=None):
