@@ -14,174 +14,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include "common.hpp"
+#include "attention_valu.hpp"
 
 namespace {
-// Tile edge TP = 8 TB: the 8 x 8 lanes of the wavefront own TB x TB blocks of the TP x TP score tile.  TB = 4 (T <= 32: titles of 30 tokens,
-// histories of 20 / 10) is the shape everything on the benchmarked path has; TB = 8 (T <= 64) serves the reference's longer inputs --
-// abstracts / bodies of 50 tokens (T/parameters.py:43-44), longer behaviour sequences -- on the same code.
-template <int TB>
-struct Tile {
-    static constexpr int TP = 8 * TB;      // padded tile edge
-    static constexpr int PP = TP + 4;      // pitch (floats) of the TP x TP probability tiles
-};
-
-struct AttnArgs {
-    const void* qkv;
-    const float* key_keep;
-    void* ctx;         // fwd: output; bwd: dctx input
-    void* dqkv;        // bwd only
-    int n_seq, T, n_heads, dh;
-    int causal;
-    float scale, mask_value;
-    DropRng drop;      // attention-probability dropout (modules.py:30; HF attention_probs_dropout_prob)
-    const int32_t* cu; // packed-row offsets (unpadded layout) or nullptr
-    int total_rows;    // rows of the packed buffers (>= cu[n_seq]); the spare ones are zero-filled by the blocks behind the grid
-};
-
-// stage a [T x DC] chunk (columns col0 + d0 .. of the packed row) into LDS as fp32, zero-padded to TP rows
-template <typename T, int DC, int TB>
-__device__ __forceinline__ void stage_chunk(const T* __restrict__ src, size_t row0, int pitch, int col0, int d0, int dh,
-                                            int Tlen, float* __restrict__ dst) {
-    constexpr int P = DC + 4;
-    constexpr int VEC = Tile<TB>::TP * DC / 4;  // float4 slots
-    const int lane = threadIdx.x;
-#pragma unroll
-    for (int i = 0; i < VEC / 64; ++i) {
-        const int v = lane + i * 64;
-        const int r = v / (DC / 4), c = (v % (DC / 4)) * 4;
-        float o[4] = {0.f, 0.f, 0.f, 0.f};
-        if (r < Tlen && d0 + c < dh) io<T>::load4(src + (row0 + r) * (size_t)pitch + col0 + d0 + c, o);
-        *reinterpret_cast<float4*>(dst + r * P + c) = make_float4(o[0], o[1], o[2], o[3]);
-    }
-}
-
-// s[r][c] += sum_d X[i0 + r][d] * Y[j0 + c][d] over one staged chunk
-template <int DC, int TB>
-__device__ __forceinline__ void block_dot(const float* __restrict__ X, const float* __restrict__ Y, int i0, int j0,
-                                          float (&s)[TB][TB]) {
-    constexpr int P = DC + 4;
-#pragma unroll 4
-    for (int d = 0; d < DC; d += 4) {
-        float4 x[TB], y[TB];
-#pragma unroll
-        for (int r = 0; r < TB; ++r) x[r] = *reinterpret_cast<const float4*>(X + (i0 + r) * P + d);
-#pragma unroll
-        for (int c = 0; c < TB; ++c) y[c] = *reinterpret_cast<const float4*>(Y + (j0 + c) * P + d);
-#pragma unroll
-        for (int r = 0; r < TB; ++r)
-#pragma unroll
-            for (int c = 0; c < TB; ++c)
-                s[r][c] += x[r].x * y[c].x + x[r].y * y[c].y + x[r].z * y[c].z + x[r].w * y[c].w;
-    }
-}
-
-// masked, scaled softmax of the lane's TB x TB block; rows are shared by the 8 lanes with equal (lane >> 3)
-template <int TB>
-__device__ __forceinline__ void block_softmax(float (&s)[TB][TB], int i0, int j0, int Tlen, int causal, float scale,
-                                              float mask_value, const float* __restrict__ keep_row) {
-    float keep[TB];
-#pragma unroll
-    for (int c = 0; c < TB; ++c) keep[c] = (j0 + c < Tlen) ? keep_row[j0 + c] : 0.f;
-#pragma unroll
-    for (int r = 0; r < TB; ++r) {
-        const int i = i0 + r;
-        float m = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < TB; ++c) {
-            const int j = j0 + c;
-            const bool kept = (keep[c] != 0.f) && (!causal || j <= i);
-            // reference arithmetic: score * scale + additive mask (the large-magnitude mask absorbs the score)
-            const float v = s[r][c] * scale + (kept ? 0.f : mask_value);
-            s[r][c] = (j < Tlen) ? v : -INFINITY;
-            m = fmaxf(m, s[r][c]);
-        }
-        m = fmaxf(m, __shfl_xor(m, 1, 64));
-        m = fmaxf(m, __shfl_xor(m, 2, 64));
-        m = fmaxf(m, __shfl_xor(m, 4, 64));
-        float sum = 0.f;
-#pragma unroll
-        for (int c = 0; c < TB; ++c) {
-            const float e = (j0 + c < Tlen) ? expf(s[r][c] - m) : 0.f;
-            s[r][c] = e;
-            sum += e;
-        }
-        sum += __shfl_xor(sum, 1, 64);
-        sum += __shfl_xor(sum, 2, 64);
-        sum += __shfl_xor(sum, 4, 64);
-        const float inv = (i < Tlen) ? 1.0f / sum : 0.f;   // padded query rows contribute nothing downstream
-#pragma unroll
-        for (int c = 0; c < TB; ++c) s[r][c] *= inv;
-    }
-}
-
-// dropout keep-mask of the lane's TB x TB block: element index ((tile * TP + i) * TP + j)  (TP = 32 for T <= 32: the same stream as
-// the MFMA kernels of attention_mfma.hip draw)
-template <int TB>
-__device__ __forceinline__ void block_drop_mask(const DropRng& d, uint64_t tile, int i0, int j0, float (&m)[TB][TB]) {
-    constexpr uint64_t TP = Tile<TB>::TP;
-#pragma unroll
-    for (int r = 0; r < TB; ++r)
-#pragma unroll
-        for (int c4 = 0; c4 < TB; c4 += 4) {
-            bool kp[4];
-            drop_keep_vec<4>(d, (tile * TP + (uint64_t)(i0 + r)) * TP + (uint64_t)(j0 + c4), kp);   // j0 + c4 is a multiple of 4: even start
-#pragma unroll
-            for (int c = 0; c < 4; ++c) m[r][c4 + c] = kp[c] ? d.inv_keep : 0.f;
-        }
-}
-
-// o[r][0..CW-1] = sum_k W[k][w0 + r] * V[k][c0 .. c0+CW-1]   (W stored [k][TP + pad]: "weights by row k");
-// CW = DC / 8 columns per lane so that the 8 x 8 lane grid covers a [TP x DC] output chunk exactly.
-template <int DC, int TB>
-__device__ __forceinline__ void block_pv(const float* __restrict__ W, const float* __restrict__ V, int w0, int c0,
-                                         int klen, float (&o)[TB][DC / 8]) {
-    constexpr int P = DC + 4, CW = DC / 8, PP = Tile<TB>::PP;
-#pragma unroll
-    for (int r = 0; r < TB; ++r)
-#pragma unroll
-        for (int c = 0; c < CW; ++c) o[r][c] = 0.f;
-    for (int k = 0; k < klen; ++k) {
-        float wr[TB];
-#pragma unroll
-        for (int r4 = 0; r4 < TB; r4 += 4) {
-            const float4 w = *reinterpret_cast<const float4*>(W + k * PP + w0 + r4);
-            wr[r4] = w.x; wr[r4 + 1] = w.y; wr[r4 + 2] = w.z; wr[r4 + 3] = w.w;
-        }
-#pragma unroll
-        for (int q = 0; q < CW / 4; ++q) {
-            const float4 v = *reinterpret_cast<const float4*>(V + k * P + c0 + 4 * q);
-#pragma unroll
-            for (int r = 0; r < TB; ++r) {
-                o[r][4 * q + 0] += wr[r] * v.x; o[r][4 * q + 1] += wr[r] * v.y;
-                o[r][4 * q + 2] += wr[r] * v.z; o[r][4 * q + 3] += wr[r] * v.w;
-            }
-        }
-    }
-}
-
-template <typename T, int CW, int TB>
-__device__ __forceinline__ void store_rows(T* __restrict__ dst, size_t row0, int pitch, int col, int r0, int Tlen,
-                                           int dcol, int dh, const float (&o)[TB][CW]) {
-#pragma unroll
-    for (int r = 0; r < TB; ++r) {
-        if (r0 + r < Tlen) {
-            T* p = dst + (row0 + r0 + r) * (size_t)pitch + col;
-#pragma unroll
-            for (int q = 0; q < CW / 4; ++q) {
-                const float v[4] = {o[r][4 * q], o[r][4 * q + 1], o[r][4 * q + 2], o[r][4 * q + 3]};
-                if (dcol + 4 * q < dh) io<T>::store4(p + 4 * q, v);
-            }
-        }
-    }
-}
-
-// row r of a TB-wide register block -> TB consecutive floats of an LDS row
-template <int TB>
-__device__ __forceinline__ void put_row(float* __restrict__ dst, const float (&v)[TB]) {
-#pragma unroll
-    for (int c = 0; c < TB; c += 4) *reinterpret_cast<float4*>(dst + c) = make_float4(v[c], v[c + 1], v[c + 2], v[c + 3]);
-}
-
 template <int DC, int TB>
 constexpr size_t attn_fwd_lds() { return (size_t)(2 * Tile<TB>::TP * (DC + 4) + Tile<TB>::TP * Tile<TB>::PP) * sizeof(float); }
 template <int DC, int TB>
@@ -360,50 +195,6 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(AttnArgs a) {
 // times the minimum: this path is a fallback, 5 - 20 x slower per token than the matrix-core kernels).
 // Dropout stream: element index ((tile * TPD + i) * TPD + j) with TPD = 32 * ceil(T / 32).
 constexpr int T_LONG_MAX = 256;
-constexpr int LDC = 64;                                   // head-width chunk of the long kernels
-constexpr int LP = LDC + 4, LPP = Tile<4>::PP, LCW = LDC / 8;
-
-// s[r][c] = sum_d X[qt*32 + i0 + r][d] * Y[kt*32 + j0 + c][d] over the whole head width (chunks restaged per call)
-template <typename T>
-__device__ __forceinline__ void long_dot(const T* __restrict__ xsrc, int xpitch, int xcol, const T* __restrict__ ysrc, int ypitch, int ycol,
-                                         size_t row0, int dh, int Tlen, int qt, int kt, float* sX, float* sY, float (&s)[4][4]) {
-    const int lane = threadIdx.x, i0 = (lane >> 3) * 4, j0 = (lane & 7) * 4;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) s[r][c] = 0.f;
-    for (int d0 = 0; d0 < dh; d0 += LDC) {
-        stage_chunk<T, LDC, 4>(xsrc, row0 + (size_t)qt * 32, xpitch, xcol, d0, dh, min(32, Tlen - qt * 32), sX);
-        stage_chunk<T, LDC, 4>(ysrc, row0 + (size_t)kt * 32, ypitch, ycol, d0, dh, min(32, Tlen - kt * 32), sY);
-        __syncthreads();
-        block_dot<LDC, 4>(sX, sY, i0, j0, s);
-        __syncthreads();
-    }
-}
-
-// reference arithmetic of one score: scaled + additive mask; keys >= T never enter (-inf)
-__device__ __forceinline__ float long_masked(float s, int i, int j, int Tlen, int causal, float scale, float mask_value, const float* __restrict__ keep_row) {
-    if (j >= Tlen) return -INFINITY;
-    const bool kept = (keep_row[j] != 0.f) && (!causal || j <= i);
-    return s * scale + (kept ? 0.f : mask_value);
-}
-
-// o[r][c] += sum_{k < klen} W[k][w0 + r] * V[k][c0 + c]
-__device__ __forceinline__ void long_pv_acc(const float* __restrict__ W, const float* __restrict__ V, int w0, int c0, int klen, float (&o)[4][LCW]) {
-    for (int k = 0; k < klen; ++k) {
-        const float4 w = *reinterpret_cast<const float4*>(W + k * LPP + w0);
-        const float wr[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-        for (int q = 0; q < LCW / 4; ++q) {
-            const float4 v = *reinterpret_cast<const float4*>(V + k * LP + c0 + 4 * q);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                o[r][4 * q + 0] += wr[r] * v.x; o[r][4 * q + 1] += wr[r] * v.y;
-                o[r][4 * q + 2] += wr[r] * v.z; o[r][4 * q + 3] += wr[r] * v.w;
-            }
-        }
-    }
-}
 
 template <typename T>
 __global__ __launch_bounds__(64) void attn_fwd_long_kernel(AttnArgs a) {
@@ -649,7 +440,7 @@ int launch_long(const morec_attn_desc* d, const AttnArgs& a, dim3 grid, hipStrea
     return MOREC_OK;
 }
 
-constexpr int T_MAX = T_LONG_MAX;     // 256: the long kernels above; 64 for the tile kernels (launch_valu)
+constexpr int T_MAX = 1024;           // the streaming kernels (attention_stream.hip); 256 for the strip kernels above, 64 for the tile kernels (launch_valu)
 
 // one launch of the VALU kernels (forward: d-chunks of 64; backward: of 32), tile edge by sequence length
 template <bool BWD>
@@ -683,7 +474,8 @@ int launch_valu(const morec_attn_desc* d, const AttnArgs& a, dim3 grid, hipStrea
 int check_desc(const morec_attn_desc* d) {
     if (!d) return MOREC_E_ARG;
     if (d->n_seq <= 0 || d->T <= 0 || d->n_heads <= 0 || d->dh <= 0) return MOREC_E_ARG;
-    if (d->T > T_MAX) return MOREC_E_UNSUPPORTED;      // 256: the strip kernels (64 < T <= 256); beyond, a row strip no longer fits LDS
+    // 1024: the streaming kernels (256 < T <= 1024; attn_stream = 1 takes them away: beyond 256 a row strip no longer fits LDS)
+    if (d->T > T_MAX || (d->T > T_LONG_MAX && tuning().attn_stream == 1)) return MOREC_E_UNSUPPORTED;
     if (d->dh % 8) return MOREC_E_ALIGN;
     if (d->p_drop < 0.f || d->p_drop >= 1.f) return MOREC_E_ARG;
     if (d->total_rows < 0 || d->spare_rows_max < 0 || (d->spare_rows_max > 0 && (!d->cu_seqlens || d->total_rows <= 0))) return MOREC_E_ARG;
@@ -701,6 +493,10 @@ int colsum_f32_launch(const float* in, float* out, int rows, int N, hipStream_t 
 int morec_attn_f32mfma_launch(const morec_attn_desc* d, const void* qkv, const float* key_keep, void* ctx_or_dctx, void* dqkv, bool backward,
                               hipStream_t s);
 
+// the streaming kernels (attention_stream.hip: stream16 on the matrix cores, streamgen in fp32 for every other shape)
+int morec_attn_stream_launch(const morec_attn_desc* d, const void* qkv, const float* key_keep, void* ctx_or_dctx, void* dqkv, bool backward,
+                             hipStream_t s);
+
 // A 16-bit problem outside the matrix-core path's shape rules (T <= 64, head width a multiple of 32) runs on the exact-fp32 VALU
 // kernels -- correct, several times slower.  Said ONCE per process on stderr (MOREC_QUIET=1 silences it) so that e.g. a run with
 // num_words_title > 64 does not lose the MFMA attention without a trace.
@@ -708,17 +504,22 @@ static void warn_valu_fallback(const morec_attn_desc* d) {
     if (!is_h16(d->dtype)) return;
     static const bool once = [](const morec_attn_desc* q) {
         if (!tuning().quiet)
-            fprintf(stderr, "libmorec_hip: attention with T = %d, head width %d is outside the MFMA path (T <= 64, head width %% 32 == 0): "
+            fprintf(stderr, "libmorec_hip: attention with T = %d, head width %d is outside the MFMA paths (T <= 64 or T > 256, head width %% 32 == 0): "
                             "running the VALU kernels for this and every later such call\n", q->T, q->dh);
         return true;
     }(d);
     (void)once;
 }
 
-// The one place that picks the kernels of a checked call: 16-bit MFMA, else fp32 MFMA, else (with the warning above) the strip
-// kernels for T > 64 and the VALU tile kernels below that.
+// The one place that picks the kernels of a checked call: the streaming kernels for T > 256 (attn_stream = 2: for every T > 64), else
+// 16-bit MFMA, else fp32 MFMA, else (with the warning above) the strip kernels for T > 64 and the VALU tile kernels below that.
+// With attn_stream = 0 every T <= 256 call reaches the kernel it reached before the streaming kernels existed.
 template <bool BWD>
 static int attn_dispatch(const morec_attn_desc* d, const void* qkv, const float* key_keep, void* ctx_or_dctx, void* dqkv, hipStream_t s) {
+    if (d->T > T_LONG_MAX || (tuning().attn_stream == 2 && d->T > Tile<8>::TP)) {      // (attn_stream = 1 with T > 256: refused by check_desc)
+        if (d->dh % 32 != 0 || d->dh > 256) warn_valu_fallback(d);      // streamgen from a 16-bit type; stream16 is a matrix-core path: no note
+        return morec_attn_stream_launch(d, qkv, key_keep, ctx_or_dctx, dqkv, BWD, s);
+    }
     int rc = morec_attn_mfma_launch(d, qkv, key_keep, ctx_or_dctx, dqkv, BWD, s);
     if (rc != MOREC_E_UNSUPPORTED) return rc;
     rc = morec_attn_f32mfma_launch(d, qkv, key_keep, ctx_or_dctx, dqkv, BWD, s);

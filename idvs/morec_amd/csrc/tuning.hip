@@ -45,6 +45,7 @@ const Row ROWS[] = {
     {"gemm8p_stamps_hi", nullptr, &Tuning::gemm8p_stamps_hi, 0, RAW},
     {"deterministic", "MOREC_DETERMINISTIC", &Tuning::deterministic, 0, FLAG},
     {"fold_defer", "MOREC_FOLD_DEFER", &Tuning::fold_defer, 1, FLAG},
+    {"attn_stream", "MOREC_ATTN_STREAM", &Tuning::attn_stream, 0, RAW},
     {nullptr, "MOREC_GEMM_TILE", &Tuning::gemm_tile, 0, RAW},
     {nullptr, "MOREC_GEMM_EPI", &Tuning::gemm_epi, 2, EPI},
     {nullptr, "MOREC_GEMM2W_STAGGER", &Tuning::gemm2w_stagger, 0, RAW},

@@ -19,6 +19,7 @@ struct Tuning {
     int gemm8p_stamps_lo, gemm8p_stamps_hi;      // device address of the cycle-stamp buffer, in halves
     int deterministic;
     int fold_defer;            // deterministic mode: morec_fold_defer_begin opens a scope (0: it does not, every fold launches in place)
+    int attn_stream;           // the streaming attention kernels (attention_stream.hip): 0 = for T > 256 only, 1 = never (T > 256 is unsupported), 2 = for every T > 64
     // environment only
     int gemm_tile;             // MOREC_GEMM_TILE: 0 = automatic, 128 / 129 / 256 / 1024 / 2128 = one two-buffer tile shape everywhere
     int gemm_epi;              // MOREC_GEMM_EPI: 2 = automatic, 1 = per-wave epilogue (w...), 0 = block epilogue (anything else)

@@ -495,7 +495,17 @@ def attn_desc(n_seq, T, n_heads, dh, causal, scale, mask_value, dtype, p_drop=0.
                     SPARE_ROWS_MAX if (cu_seqlens is not None and total_rows) else 0)
 
 
+ATTN_T_MAX = 1024      # longest sequence of morec_attn_fwd / morec_attn_bwd (the streaming kernels, csrc/attention_stream.hip)
+
+
+def _attn_cap(desc):
+    if desc.T > ATTN_T_MAX:
+        raise _lib.MorecError(f"attention over {desc.T} positions: the kernels end at {ATTN_T_MAX} positions per sequence "
+                              f"(MOREC_E_UNSUPPORTED; 256 with MOREC_ATTN_STREAM=1)")
+
+
 def attn_fwd(desc, qkv, key_keep):
+    _attn_cap(desc)
     _dev(qkv), _dev(key_keep)
     ctx = torch.empty((qkv.shape[0], qkv.shape[1] // 3), device=qkv.device, dtype=qkv.dtype)
     check(_lib.lib().morec_attn_fwd(C.byref(desc), _p(qkv), _p(key_keep), _p(ctx), _stream()), "morec_attn_fwd")
@@ -504,6 +514,7 @@ def attn_fwd(desc, qkv, key_keep):
 
 def attn_bwd(desc, qkv, key_keep, dctx, dbias=None):
     """``dbias``: fp32 [3 H] gradient buffer of the fused q|k|v bias, accumulated into (column sums of dqkv)."""
+    _attn_cap(desc)
     _dev(dctx)
     dqkv = torch.empty_like(qkv)
     if dbias is None:

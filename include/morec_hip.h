@@ -110,6 +110,9 @@ int morec_version(void);
  *   "gemm8p_stamps_lo", "gemm8p_stamps_hi"  device address of a cycle-stamp buffer, in halves          -                         0
  *   "deterministic"      1 = fixed summation order everywhere (state item 6) | 0 off                   MOREC_DETERMINISTIC       0
  *   "fold_defer"         1 = morec_fold_defer_begin opens a scope (state item 7) | 0 = it never does   MOREC_FOLD_DEFER          1
+ *   "attn_stream"        the streaming attention kernels (attention_stream.hip): 0 = for T > 256 only (every T <= 256 call     MOREC_ATTN_STREAM         0
+ *                        reaches the kernel it reaches without them) | 1 = never: T > 256 is MOREC_E_UNSUPPORTED | 2 = for every T > 64
+ *                        (tests and measurements: the tile edges with small inputs, the strip kernels' range on the matrix cores)
  * Environment only:
  *   MOREC_GEMM_TILE      one tile shape for every two-buffer GEMM: 128 | 129 | 256 | 1024 | 2128 (csrc/gemm_plan.hpp)          0 = automatic
  *   MOREC_GEMM_EPI       w = per-wave epilogue, anything else = block epilogue, in the two-buffer GEMMs                      unset = automatic
@@ -329,10 +332,14 @@ int morec_pos_grad(const void* dz, float* dpos, int M, int N, int period, int dt
 
 /* ------------------------------------------------------------------------------------------
  * Small-tile multi-head attention on packed projections qkv[M, 3*H] = [Q | K | V], M = n_seq*T,
- * H = n_heads*dh, T <= 256.  16-bit storage, head width % 32 == 0: the matrix-core kernels for T <= 32 and for 32 < T <= 64 (abstracts /
+ * H = n_heads*dh, T <= 1024 (beyond: MOREC_E_UNSUPPORTED).  16-bit storage, head width % 32 == 0: the matrix-core kernels for T <= 32 and for 32 < T <= 64 (abstracts /
  * bodies of 50 tokens, T/parameters.py:43-44); fp32 storage, T <= 32, head width % 16 == 0: exact-fp32 MFMA (attention_f32mfma.hip: the
  * parity and fp32x3 modes); other head widths and fp32 up to T = 64: the exact-fp32 VALU tile kernels; 64 < T <= 256 (longer than any
- * launcher of the reference sets, accepted by its command line): the row-strip VALU kernels, every dtype; T > 256: MOREC_E_UNSUPPORTED.
+ * launcher of the reference sets, accepted by its command line): the row-strip VALU kernels, every dtype; 256 < T <= 1024 (BERT's 512 positions, long behaviour
+ * sequences): the streaming kernels of attention_stream.hip, which walk the keys in tiles of 64 / 32 with a running softmax and never hold
+ * a full score row -- stream16 (16-bit storage, head width % 32 == 0 and <= 256: 4 wavefronts per (sequence, head), all five products on
+ * the matrix cores) and streamgen (every other shape: fp32 arithmetic, one wavefront per (sequence, head)); the "attn_stream" knob moves
+ * their lower edge to 64 or takes them away; T > 1024: MOREC_E_UNSUPPORTED.
  * scores = (q.k) * scale + (key masked ? mask_value : 0), causal option,
  * softmax, ctx = P.V.   SASRec: T/model/encoders.py:24-27 + T/model/modules.py:27-31 (causal,
  * mask_value -1e9, scale 1/sqrt(d_k)).  BERT: HF BertSelfAttention eager (mask_value finfo.min).
