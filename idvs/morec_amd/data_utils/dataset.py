@@ -67,10 +67,12 @@ def collate_bce_batch(u2seq, users, item_content, max_seq_len, item_num, use_mod
             while neg in seen:
                 neg = int(rng.integers(1, item_num + 1))
             items[r, L - n + j, 1] = neg
-    out = np.asarray(item_content)[items] if use_modal else items
+    out = torch.from_numpy(np.ascontiguousarray(np.asarray(item_content)[items] if use_modal else items))
+    if out.dtype != torch.uint8:          # uint8 = decoded images of the vision variant (normalised on the device)
+        out = out.long()
     if with_ids:
-        return torch.from_numpy(items), torch.from_numpy(np.ascontiguousarray(out)).long(), torch.from_numpy(log_mask)
-    return torch.from_numpy(np.ascontiguousarray(out)).long(), torch.from_numpy(log_mask)
+        return torch.from_numpy(items), out, torch.from_numpy(log_mask)
+    return out, torch.from_numpy(log_mask)
 
 
 class BuildEvalDataset(Dataset):

@@ -14,8 +14,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .. import engine, ops, swin_engine
-from ..model.encoders import Bert_Encoder, Vit_Encoder, resolve_fp32_gemm
+from .. import engine, mae_engine, ops, swin_engine
+from ..model.encoders import Bert_Encoder, MAE_Encoder, Vit_Encoder, resolve_fp32_gemm
 from .dataset import collate_bce_batch
 from .metrics import _module
 
@@ -48,6 +48,18 @@ def _vision_features_fn(enc: Vit_Encoder):
     return run
 
 
+def _mae_features_fn(enc: MAE_Encoder):
+    p = dict(enc.named_parameters())
+    shape = enc.image_net.shape
+    prep = mae_engine.mae_prepare(p, shape, enc.compute_dtype, "", features_only=True)
+    seed, ratio = enc.masking()      # evaluation mode: the fixed seed, keyed by the row within the chunk
+
+    def run(pixels):
+        cls, _ = mae_engine.mae_forward(p, prep, shape, pixels, enc.compute_dtype, False, "", seed=seed, mask_ratio=ratio, features_only=True)
+        return cls.float()
+    return run
+
+
 def extract_item_features(encoder, item_content, batch_size, device=None):
     """Stage 1: ``encoder`` (a ``Bert_Encoder`` or a ``Vit_Encoder``) in eval mode, without gradients or saved activations, over every
     catalogue row of ``item_content`` (token rows ``[item_num + 1, 2T...]``; images as a float ``[n, 3, R, R]`` / uint8 ``[n, R, R, 3]``
@@ -61,6 +73,8 @@ def extract_item_features(encoder, item_content, batch_size, device=None):
         run, mode = _text_features_fn(enc), resolve_fp32_gemm(enc.args)
     elif isinstance(enc, Vit_Encoder):
         run, mode = _vision_features_fn(enc), ops.FP32_GEMM
+    elif isinstance(enc, MAE_Encoder):      # the normalised [CLS] rows in front of cv_proj (image_net(x)[0][:, 0]): this project's definition
+        run, mode = _mae_features_fn(enc), ops.FP32_GEMM
     else:
         raise TypeError(f"extract_item_features: no features_only path for {type(enc).__name__}; write the features to a .npy file and use "
                         "load_feature_table")

@@ -8,7 +8,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from . import engine, ops, swin_engine
+from . import engine, mae_engine, ops, swin_engine
 
 
 def _zeros_like_params(names, params, skip=()):
@@ -110,6 +110,37 @@ class SwinEncoderFn(torch.autograd.Function):
             engine.WgradStream.join(d_item.device)
         needs = ctx.needs[2:]
         return (None, None) + tuple(grads[n] if nd else None for n, nd in zip(names, needs))
+
+
+class MaeEncoderFn(torch.autograd.Function):
+    """``MAE_Encoder.forward`` (``V/model/encoders.py:20-21``) over HF ``ViTMAEModel`` arithmetic.  ``cfg = (names, shape, dtype, prefix,
+    noise, seed, mask_ratio)``: ``noise`` fp32 [n_img, N] or None (the kept patches are then drawn from ``seed``)."""
+
+    @staticmethod
+    def forward(ctx, pixels, cfg, *params):
+        names, shape, dtype, prefix, noise, seed, mask_ratio = cfg
+        p = dict(zip(names, params))
+        need = any(ctx.needs_input_grad)
+        prep = mae_engine.mae_prepare(p, shape, dtype, prefix)
+        item, saved = mae_engine.mae_forward(p, prep, shape, pixels, dtype, need, prefix, noise=noise, seed=seed, mask_ratio=mask_ratio)
+        ctx.stuff = (p, prep, saved, names, prefix, shape)
+        ctx.needs = ctx.needs_input_grad
+        ctx.fp32_gemm = ops.FP32_GEMM
+        return item
+
+    @staticmethod
+    def backward(ctx, d_item):
+        p, prep, saved, names, prefix, shape = ctx.stuff
+        ctx.stuff = None
+        skip = {mae_engine.mae_layer_names(prefix, l) + f"attention.{n}.{k}" for l in range(shape.num_hidden_layers)
+                for n in ("q_proj", "k_proj", "v_proj") for k in ("weight", "bias")}
+        skip.add(prefix + "image_net.embeddings.position_embeddings")      # frozen in HF: no gradient
+        grads = _zeros_like_params(names, [p[n] for n in names], skip=skip)
+        with ops.fp32_gemm_mode(ctx.fp32_gemm):
+            mae_engine.mae_backward(p, prep, saved, d_item.contiguous(), grads, prefix)
+            engine.WgradStream.join(d_item.device)
+        needs = ctx.needs[2:]
+        return (None, None) + tuple(grads.get(n) if nd else None for n, nd in zip(names, needs))
 
 
 class IdEmbeddingFn(torch.autograd.Function):

@@ -10,7 +10,8 @@ from torch import nn
 from torch.nn.init import xavier_normal_
 
 from .. import engine, ops
-from .encoders import Bert_Encoder, IdEmbedding, User_Encoder, fusion_tower, make_fusion, resolve_dtype, resolve_fp32_gemm, resolve_res32
+from .encoders import (Bert_Encoder, IdEmbedding, MAE_Encoder, User_Encoder, fusion_tower, is_mae_name, make_fusion, resolve_dtype, resolve_fp32_gemm,
+                       resolve_res32)
 
 
 class BceLossFn(torch.autograd.Function):
@@ -46,7 +47,15 @@ class BceModel(nn.Module):
         self.user_encoder = User_Encoder(item_num=item_num, max_seq_len=args.max_seq_len, item_dim=args.embedding_dim,
                                          num_attention_heads=args.num_attention_heads, dropout=args.drop_rate,
                                          n_layers=args.transformer_block, compute_dtype=self.compute_dtype, res32=resolve_res32(args))
-        if self.use_modal:
+        # the vision twin (bce_vision/main-end2end/model/model.py): the MAE tower; Swin under this loss is not built
+        self.vision = bool(self.use_modal and getattr(args, "CV_model_load", "None") not in ("None", None))
+        if self.vision:
+            cv = args.CV_model_load
+            if "swin" in cv or "resnet" in cv or "beit" in cv or not is_mae_name(cv):
+                raise NotImplementedError(f"BceModel: CV_model_load {cv!r}: only the MAE tower is built for the BCE loss (Swin runs under the "
+                                          "in-batch loss; ResNet / BEiT are not implemented)")
+            self.cv_encoder = MAE_Encoder(image_net=bert_model, item_dim=args.embedding_dim, compute_dtype=self.compute_dtype)
+        elif self.use_modal:
             self.bert_encoder = Bert_Encoder(args=args, bert_model=bert_model)
         # ID (+) modality fusion (bce_text/id_plus_mo-end2end/model/model.py:23-39): encoder AND fc AND id_embedding
         self.fusion = fusion_tower(args)[0] if self.use_modal else None
@@ -62,11 +71,12 @@ class BceModel(nn.Module):
         """(item, user, fusion) dropout streams.  The encoders of this model run without dropout, as before the fusion towers; the
         fusion MLP draws ``args.drop_rate`` in training mode, from ``torch.initial_seed()`` and a per-call counter."""
         p = float(self.args.drop_rate)
-        if not self.training or not self.fusion or p <= 0:
+        if not self.training or not ((self.fusion and p > 0) or self.vision):
             return engine.NO_DROP, engine.NO_DROP, engine.NO_DROP
         self._drop_calls += 1
         base = (torch.initial_seed() * 0x9E3779B97F4A7C15 + self._drop_calls * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
-        return engine.NO_DROP, engine.NO_DROP, engine.DropCfg(p, 0.0, base ^ 0x3C6EF372FE94F82B)
+        d_item = engine.DropCfg(0.0, 0.0, base) if self.vision else engine.NO_DROP      # the MAE tower's patch-masking noise
+        return d_item, engine.NO_DROP, (engine.DropCfg(p, 0.0, base ^ 0x3C6EF372FE94F82B) if (self.fusion and p > 0) else engine.NO_DROP)
 
     def forward(self, *inputs, local_rank=None):
         """``(sample_items, log_mask, local_rank)`` (bce_text/main-end2end), or with a fusion tower the four-argument form of
@@ -83,9 +93,13 @@ class BceModel(nn.Module):
     def _forward(self, sample_items, log_mask, local_rank=None, sample_items_id=None):
         D = self.args.embedding_dim
         if self.use_modal:
-            E = self.bert_encoder.encode(sample_items.reshape(-1, sample_items.shape[-1]))
+            d_item, _, d_fuse = self.dropout_cfgs()
+            if self.vision:
+                E = self.cv_encoder.encode(sample_items.reshape(-1, *sample_items.shape[-3:]), d_item)
+            else:
+                E = self.bert_encoder.encode(sample_items.reshape(-1, sample_items.shape[-1]))
             if self.fusion:
-                E = self.fc.encode(sample_items_id.reshape(-1), E, self.id_embedding.weight, self.dropout_cfgs()[2])
+                E = self.fc.encode(sample_items_id.reshape(-1), E, self.id_embedding.weight, d_fuse)
         else:
             E = self.id_embedding.encode(sample_items.reshape(-1))
         E = E.reshape(-1, D)

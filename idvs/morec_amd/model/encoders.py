@@ -12,6 +12,8 @@ from ..engine import NO_DROP, DropCfg
 from ..ops import FLT_MIN_MASK
 from .bert import HipBertModel
 from .swin import HipSwinForImageClassification
+from .mae import HipViTMAEModel
+from ..mae_engine import MAE_SEED_EVAL, MAE_SEED_TRAIN, mae_keep
 from .modules import TransformerEncoder
 
 
@@ -221,6 +223,58 @@ class Vit_Encoder(nn.Module):
 
     def forward(self, item_content):
         return self.encode(item_content).float()
+
+
+def is_mae_name(name) -> bool:
+    """``V/model/model.py:28``: the names the reference routes to ``MAE_Encoder``."""
+    return "mae" in str(name) or "checkpoint" in str(name)
+
+
+class MAE_Encoder(nn.Module):
+    """``V/model/encoders.py:7-21``: ``GELU(cv_proj(image_net(item_content)[0][:, 0]))`` with ``image_net`` a HF ``ViTMAEModel``.  The
+    reference hard-codes ``word_emb = 768``; here it is the model's hidden size (equal for the checkpoints it ships).
+
+    ``ViTMAEModel`` masks ``config.mask_ratio`` of the patches in every forward -- in evaluation too, with fresh ``torch.rand`` noise.  The
+    masking is kept as the default; the noise is drawn by the counter-based generator instead: in training from the step's dropout seed
+    (``drop.seed``) with a constant of its own, so a resumed run and a replayed seed repeat; in evaluation from a fixed seed keyed by the
+    row within the call, so a catalogue pass repeats bit for bit.  ``config.eval_mask_ratio`` (None = the training value; 0 = encode
+    from every patch) applies in evaluation mode.  ``noise`` fp32 [n_img, N] decides the kept patches as HF's ``noise=`` argument does."""
+
+    def __init__(self, image_net, item_dim, compute_dtype=None):
+        super().__init__()
+        self.item_dim = item_dim
+        self.image_net = image_net if isinstance(image_net, HipViTMAEModel) else HipViTMAEModel.from_hf(image_net)
+        self.word_emb = self.image_net.shape.hidden_size
+        self.activate = nn.GELU()
+        self.cv_proj = nn.Linear(self.word_emb, self.item_dim)
+        xavier_normal_(self.cv_proj.weight.data)
+        constant_(self.cv_proj.bias.data, 0)
+        self.compute_dtype = compute_dtype or resolve_dtype()
+        self.noise = None      # fp32 [n_img, N]: stands in for an absent ``noise`` argument (parity runs through ``Model.forward``)
+
+    def masking(self, drop: DropCfg = NO_DROP):
+        """(seed, mask_ratio) of a forward in the current mode."""
+        c = self.image_net.config
+        if float(getattr(c, "hidden_dropout_prob", 0.0)) or float(getattr(c, "attention_probs_dropout_prob", 0.0)):
+            raise NotImplementedError("MAE hidden / attention dropout (0.0 in every MAE config the reference ships)")
+        if self.training:
+            return (int(drop.seed) ^ MAE_SEED_TRAIN) & 0xFFFFFFFFFFFFFFFF, float(c.mask_ratio)
+        ratio = getattr(c, "eval_mask_ratio", None)
+        return MAE_SEED_EVAL, float(c.mask_ratio if ratio is None else ratio)
+
+    def keep_ids(self, n_img, drop: DropCfg = NO_DROP, noise=None, device="cuda"):
+        """The kept-patch ids int32 [n_img, len_keep] that ``encode`` with the same arguments uses."""
+        seed, ratio = self.masking(drop)
+        return mae_keep(self.image_net.shape, n_img, device, self.noise if noise is None else noise, seed, ratio)
+
+    def encode(self, item_content, drop: DropCfg = NO_DROP, noise=None):
+        names, params = zip(*self.named_parameters())
+        seed, ratio = self.masking(drop)
+        cfg = (names, self.image_net.shape, self.compute_dtype, "", self.noise if noise is None else noise, seed, ratio)
+        return F_.MaeEncoderFn.apply(item_content, cfg, *params)
+
+    def forward(self, item_content, noise=None):
+        return self.encode(item_content, noise=noise).float()
 
 
 class IdEmbedding(nn.Module):

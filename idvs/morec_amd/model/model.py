@@ -12,8 +12,8 @@ from torch.nn.init import xavier_normal_
 
 from .. import engine, ops
 from .. import functional as F_
-from .encoders import (Bert_Encoder, IdEmbedding, User_Encoder, Vit_Encoder, fusion_tower, make_fusion, resolve_dtype, resolve_fp32_gemm,
-                       resolve_res32)
+from .encoders import (Bert_Encoder, IdEmbedding, MAE_Encoder, User_Encoder, Vit_Encoder, fusion_tower, is_mae_name, make_fusion, resolve_dtype,
+                       resolve_fp32_gemm, resolve_res32)
 
 
 class Model(nn.Module):
@@ -40,10 +40,13 @@ class Model(nn.Module):
                                          n_layers=args.transformer_block, compute_dtype=self.compute_dtype, res32=self.res32)
         self.vision = hasattr(args, "CV_model_load")
         if self.use_modal and self.vision:
-            if "swin" not in args.CV_model_load:
-                raise NotImplementedError("only the Swin tower of V/model/model.py:24-29 is implemented (ResNet / BEiT / MAE "
+            if "swin" in args.CV_model_load:
+                self.cv_encoder = Vit_Encoder(image_net=bert_model, compute_dtype=self.compute_dtype)
+            elif "resnet" not in args.CV_model_load and "beit" not in args.CV_model_load and is_mae_name(args.CV_model_load):
+                self.cv_encoder = MAE_Encoder(image_net=bert_model, item_dim=args.embedding_dim, compute_dtype=self.compute_dtype)
+            else:
+                raise NotImplementedError("only the Swin and MAE towers of V/model/model.py:24-29 are implemented (ResNet / BEiT "
                                           "launchers are outside the benchmarked path)")
-            self.cv_encoder = Vit_Encoder(image_net=bert_model, compute_dtype=self.compute_dtype)
         elif self.use_modal:
             self.bert_encoder = Bert_Encoder(args=args, bert_model=bert_model)
         # ID (+) modality fusion (bce_text/id_plus_mo-end2end/model/model.py:23-39, here under the in-batch loss too): the model then owns
@@ -72,7 +75,7 @@ class Model(nn.Module):
         d_user = engine.DropCfg(p, p, base ^ 0x5555555555555555) if p > 0 else engine.NO_DROP
         d_item = engine.NO_DROP
         if self.use_modal and self.vision:
-            d_item = engine.DropCfg(0.0, 0.0, base)      # only the DropPath streams are drawn from it
+            d_item = engine.DropCfg(0.0, 0.0, base)      # only the DropPath streams (Swin) / the patch-masking noise (MAE) are drawn from it
         elif self.use_modal:
             c = self.bert_encoder.text_encoders["title"].bert_model.config
             ph, pa = float(getattr(c, "hidden_dropout_prob", 0.0)), float(getattr(c, "attention_probs_dropout_prob", 0.0))

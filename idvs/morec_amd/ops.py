@@ -1040,6 +1040,75 @@ def droppath_scale(n, p, seed, device="cuda"):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------
+# MAE (ViT) tower front (csrc/mae.hip)
+# ---------------------------------------------------------------------------------------------------------
+def mae_len_keep(N: int, mask_ratio: float) -> int:
+    """HF ``random_masking`` (``modeling_vit_mae.py:308``): Python double arithmetic, truncated."""
+    return int(N * (1 - mask_ratio))
+
+
+def mae_keep_ids(n_img, N, len_keep, *, noise=None, seed=0, device="cuda"):
+    """int32 [n_img, len_keep]: ``argsort(noise)[:, :len_keep]`` (ties to the lower index).  ``noise``: fp32 [n_img, N], or None: drawn from
+    ``(seed, image, patch)`` by the counter-based generator of the dropout masks."""
+    if noise is not None:
+        _dev(noise)
+        if noise.dtype != torch.float32 or tuple(noise.shape) != (n_img, N):
+            raise _lib.MorecError(f"mae noise must be fp32 [{n_img}, {N}], got {noise.dtype} {tuple(noise.shape)}")
+        device = noise.device
+    keep = torch.empty((n_img, len_keep), device=device, dtype=torch.int32)
+    check(_lib.lib().morec_mae_keep_ids(_p(noise), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(keep), n_img, N, len_keep, _stream()), "morec_mae_keep_ids")
+    return keep
+
+
+def mae_patchify_keep(pixels, keep, patch, dtype, mean=0.5, std=0.5):
+    """The im2col rows of the kept patches only: fp32 NCHW pixels, or uint8 [n, R, R, 3] decoded images (normalised in flight) ->
+    [n * len_keep, 3 patch^2] of ``dtype``; bit-equal to ``swin_patchify[_u8]`` followed by a row gather."""
+    _dev(pixels), _dev(keep)
+    n_img, len_keep = keep.shape
+    if keep.dtype != torch.int32 or pixels.shape[0] != n_img:
+        raise _lib.MorecError("mae keep must be int32 [n_img, len_keep]")
+    if pixels.dtype == torch.uint8:
+        _, R, _, c = pixels.shape
+        out = torch.empty((n_img * len_keep, c * patch * patch), device=pixels.device, dtype=dtype)
+        check(_lib.lib().morec_mae_patchify_keep_u8(_p(pixels), _p(keep), _p(out), n_img, c, R, patch, len_keep, out.stride(0), mean, std,
+                                                    code(dtype), _stream()), "morec_mae_patchify_keep_u8")
+        return out
+    if pixels.dtype != torch.float32:
+        raise _lib.MorecError("pixels must be fp32 NCHW or uint8 NHWC")
+    _, c, R, _ = pixels.shape
+    out = torch.empty((n_img * len_keep, c * patch * patch), device=pixels.device, dtype=dtype)
+    check(_lib.lib().morec_mae_patchify_keep(_p(pixels), _p(keep), _p(out), n_img, c, R, patch, len_keep, out.stride(0), code(dtype), _stream()),
+          "morec_mae_patchify_keep")
+    return out
+
+
+def mae_assemble_fwd(e, cls_token, pos, keep):
+    """[n_img * (1 + len_keep), C]: row 0 of an image = cls_token + pos[0], row 1 + j = e[i * len_keep + j] + pos[1 + keep[i, j]]."""
+    _dev(e), _dev(keep), _dev(cls_token), _dev(pos)
+    n_img, len_keep = keep.shape
+    C_ = e.shape[1]
+    N = pos.numel() // C_ - 1
+    assert e.shape[0] == n_img * len_keep and cls_token.numel() == C_ and cls_token.dtype == pos.dtype == torch.float32
+    x = torch.empty((n_img * (1 + len_keep), C_), device=e.device, dtype=e.dtype)
+    check(_lib.lib().morec_mae_assemble_fwd(_p(e), _p(cls_token), _p(pos), _p(keep), _p(x), n_img, len_keep, N, C_, code(e.dtype), _stream()),
+          "morec_mae_assemble_fwd")
+    return x
+
+
+def mae_assemble_bwd(dx, n_img, len_keep, d_cls=None):
+    """(de [n_img * len_keep, C], d_cls fp32 [C]): the patch rows of ``dx`` and the fixed-order sum of its [CLS] rows (written into ``d_cls``)."""
+    _dev(dx)
+    C_ = dx.shape[1]
+    assert dx.shape[0] == n_img * (1 + len_keep)
+    de = torch.empty((n_img * len_keep, C_), device=dx.device, dtype=dx.dtype)
+    if d_cls is None:
+        d_cls = torch.empty(C_, device=dx.device, dtype=torch.float32)
+    assert d_cls.dtype == torch.float32 and d_cls.numel() == C_ and d_cls.is_contiguous()
+    check(_lib.lib().morec_mae_assemble_bwd(_p(dx), _p(de), _p(d_cls), n_img, len_keep, C_, code(dx.dtype), _stream()), "morec_mae_assemble_bwd")
+    return de, d_cls
+
+
 def dropout_keep_mask(n, p, seed, device="cuda"):
     out = torch.empty(n, device=device, dtype=torch.uint8)
     check(_lib.lib().morec_dropout_keep_mask(_p(out), n, p, seed, _stream()), "morec_dropout_keep_mask")

@@ -67,7 +67,12 @@ def build_parser():
     p.add_argument("--num_words_body", type=int, default=50)
     p.add_argument("--news_attributes", type=str, default="title")
     # ============== vision variant (V/parameters.py:34-39) ==============
-    p.add_argument("--CV_model_load", type=str, default="None", help="swin_tiny | swin_small | swin_base (vision item tower)")
+    p.add_argument("--CV_model_load", type=str, default="None", help="swin_tiny | swin_small | swin_base, or mae_base | mae_large (a name with 'mae' "
+                   "or 'checkpoint': the MAE / ViT tower of V/model/model.py:28) (vision item tower)")
+    p.add_argument("--mae_mask_ratio", type=float, default=None, help="MAE tower: share of the patches masked in a training forward "
+                   "(default: the model's, 0.75)")
+    p.add_argument("--mae_eval_mask_ratio", type=float, default=None, help="MAE tower: the same in evaluation mode (catalogue passes); default: "
+                   "the training value, as the reference (ViTMAEModel masks at evaluation too); 0 encodes the catalogue from all patches")
     p.add_argument("--CV_resize", type=int, default=224)
     p.add_argument("--image_lmdb", type=str, default="None", help="LMDB of pickled LMDB_Image records (dataset/HM/build_lmdb_hm.py; "
                    "V/parameters.py --lmdb_data): decoded per batch, resized on the GPU; needs the optional `lmdb` module")
@@ -140,6 +145,33 @@ def check_fusion_args(args):
         raise SystemExit(f"--item_tower {args.item_tower}: a new item has no row in the id table, so the fused vector fc(id, content) "
                          "does not exist for it; --new_seqs is not available with a fusion tower (--cold_seqs alone is)")
     return kind
+
+
+def is_mae_run(args) -> bool:
+    """A run whose item tower is the MAE (ViT) tower: a modal tower with a ``--CV_model_load`` the reference routes to ``MAE_Encoder``."""
+    cv = str(getattr(args, "CV_model_load", "None"))
+    return "modal" in str(args.item_tower) and cv != "None" and "swin" not in cv and ("mae" in cv or "checkpoint" in cv)
+
+
+def check_mae_args(args):
+    """What the MAE tower does not run with: exits with the reason (before anything touches a device).  True for an MAE run."""
+    if not is_mae_run(args):
+        return False
+    why = None
+    if getattr(args, "fused_step", False):
+        why = ("--fused_step" + (" --pool_negatives" if getattr(args, "pool_negatives", False) else "") +
+               ": train_step.TrainStep covers the text, ID and Swin towers; the MAE tower trains on the drop-in autograd path")
+    elif getattr(args, "graph", False):
+        why = "--graph replays the fused step (train_step.TrainStep), which the MAE tower does not use"
+    elif getattr(args, "arch", "sasrec") == "dssm":
+        why = "--arch dssm: a vision item tower is not built for DSSM"
+    for name in ("mae_mask_ratio", "mae_eval_mask_ratio"):
+        v = getattr(args, name, None)
+        if why is None and v is not None and not 0.0 <= v < 1.0:
+            why = f"--{name} must lie in [0, 1)"
+    if why:
+        raise SystemExit(f"--CV_model_load {args.CV_model_load} (MAE / ViT item tower): " + why)
+    return True
 
 
 def check_dssm_args(args):

@@ -38,7 +38,10 @@ from .data_utils.utils import _unwrap
 from .model import BceModel, BertShape, DssmModel, HipBertModel, Model
 from .model.swin import HipSwinForImageClassification
 from .swin_engine import SwinShape
-from .parameters import check_dssm_args, check_fusion_args, check_id_two_stage_args, check_two_stage_args, parse_args
+from .model.mae import HipViTMAEModel
+from .mae_engine import MaeShape
+from .parameters import (check_dssm_args, check_fusion_args, check_id_two_stage_args, check_mae_args, check_two_stage_args, is_mae_run,
+                         parse_args)
 from . import engine
 from .train_step import TrainStep
 from .lr_schedule import AutogradStepControl, schedule_from_args
@@ -475,6 +478,23 @@ def build_text_tower(args, freeze=True):
     return bert
 
 
+def build_vision_tower(args):
+    """The image network of a vision run, keyed on ``--CV_model_load`` the way ``V/model/model.py:24-29`` is: a Swin classifier
+    (``V/run.py:47-54``) or, for a name with 'mae' / 'checkpoint', the ``ViTMAEModel`` container (``--mae_mask_ratio`` /
+    ``--mae_eval_mask_ratio`` override the shape's masking)."""
+    if is_mae_run(args):
+        shape = MaeShape.named(args.CV_model_load)
+        if getattr(args, "mae_mask_ratio", None) is not None:
+            shape.mask_ratio = float(args.mae_mask_ratio)
+        if shape.image_size != args.CV_resize:
+            raise SystemExit(f"--CV_model_load {args.CV_model_load}: the MAE tower takes {shape.image_size} px images (--CV_resize {args.CV_resize}); "
+                             "interpolated position embeddings are not implemented")
+        net = HipViTMAEModel(shape)
+        net.config.eval_mask_ratio = getattr(args, "mae_eval_mask_ratio", None)
+        return net
+    return HipSwinForImageClassification(SwinShape.named(args.CV_model_load), args.embedding_dim)   # V/run.py:47-54
+
+
 def load_dataset(args, use_modal, vision):
     """The data of a SASRec-family run -- ``--synthetic N``, the text tables (tokenizer), the vision catalogue (LMDB) or the bare ids -- as
     ``(item_num, item_content, users_train, users_valid, users_test, hist_valid, hist_test, pop, catalogue)``."""
@@ -668,7 +688,7 @@ def train(args, use_modal, local_rank):
     item_num, item_content, users_train, users_valid, users_test, hist_valid, hist_test, pop, catalogue = load_dataset(args, use_modal, vision)
     bert = None
     if vision:
-        bert = HipSwinForImageClassification(SwinShape.named(args.CV_model_load), args.embedding_dim)   # V/run.py:47-54
+        bert = build_vision_tower(args)
         for index, (name, param) in enumerate(bert.named_parameters()):   # V/run.py:58-60
             if index < args.freeze_paras_before:
                 param.requires_grad = False
@@ -676,8 +696,9 @@ def train(args, use_modal, local_rank):
         bert = build_text_tower(args)
     bce = args.loss == "bce"
     fusion = check_fusion_args(args) if use_modal else None
-    if bce and (args.fused_step or vision):
-        raise SystemExit("--loss bce runs on the drop-in autograd path with the text / ID towers (bce_text/main-end2end)")
+    if bce and (args.fused_step or (vision and not is_mae_run(args))):
+        raise SystemExit("--loss bce runs on the drop-in autograd path with the text / ID / MAE towers (bce_text/main-end2end, "
+                         "bce_vision/main-end2end)")
     model = (BceModel(args, item_num, use_modal, bert) if bce else Model(args, item_num, use_modal, bert, pop)).to(local_rank)
     users = list(users_train.keys())
     model_dir = model_dir_of(args, world)
@@ -702,7 +723,9 @@ def train(args, use_modal, local_rank):
     else:
         wrapped = DDP(model, device_ids=[local_rank], output_device=local_rank, find_unused_parameters=True) if world > 1 else model
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
-        if vision:   # V/run.py:121-135
+        if vision and is_mae_run(args):      # V/run.py:121-135 over the reference's own (transformers 4.20.1) MAE names, none of which
+            tower = lambda n: "image_net" in n      # holds 'fc' or 'classifier' (the installed names' mlp.fc1 / mlp.fc2 are its *.dense)
+        elif vision:   # V/run.py:121-135
             tower = lambda n: "image_net" in n and not ("fc" in n or "classifier" in n)
         else:        # T/run.py:150-162
             tower = lambda n: "bert_model" in n
@@ -988,11 +1011,12 @@ def two_stage_features(args, item_content, item_num, vision, local_rank, rank):
     """Stage 1 of ``--arch two_stage``: the frozen item tower once over the catalogue (``data_utils.extract_item_features``) -> fp32
     [item_num + 1, W] on the device; ``--save_features`` writes it (rank 0).  The tower is dropped afterwards."""
     from .data_utils import extract_item_features
-    from .model.encoders import Bert_Encoder, Vit_Encoder, resolve_dtype
+    from .model.encoders import Bert_Encoder, MAE_Encoder, Vit_Encoder, resolve_dtype
     t0 = time.time()
-    if vision:
-        tower = Vit_Encoder(image_net=HipSwinForImageClassification(SwinShape.named(args.CV_model_load), args.embedding_dim),
-                            compute_dtype=resolve_dtype(args))
+    if vision and is_mae_run(args):
+        tower = MAE_Encoder(image_net=build_vision_tower(args), item_dim=args.embedding_dim, compute_dtype=resolve_dtype(args))
+    elif vision:
+        tower = Vit_Encoder(image_net=build_vision_tower(args), compute_dtype=resolve_dtype(args))
     else:
         tower = Bert_Encoder(args=args, bert_model=build_text_tower(args, freeze=False))
     table = extract_item_features(tower.to(local_rank), item_content, 512, local_rank)
@@ -1106,6 +1130,7 @@ def train_two_stage(args, use_modal, local_rank, id_fusion=False):
 
 def main(argv=None):
     args = parse_args(argv)
+    check_mae_args(args)
     two_stage = check_two_stage_args(args)
     id_two_stage = check_id_two_stage_args(args)
     dssm = check_dssm_args(args)

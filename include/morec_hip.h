@@ -420,6 +420,31 @@ int morec_bias_residual(const void* a, const float* bias, const void* res, const
 int morec_droppath_scale(float* out, int n, float p, uint64_t seed, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The front of the MAE (ViT) item tower (csrc/mae.hip): HF ViTMAEEmbeddings (modeling_vit_mae.py:182-327) for the KEPT patches only.
+ * fp32, bf16 and fp16 storage; 16-byte accesses; no atomics, every output element written once, the same bits on every run.
+ *
+ * keep[n_img, len_keep] (int32) = the patch indices of each image in ascending order of noise, ties to the lower index --
+ * torch.argsort(noise)[:, :len_keep] of random_masking (:297-327) for distinct values.  noise: fp32 [n_img, N] (HF's noise= argument),
+ * or NULL: the key of (image, patch) is the counter-based generator of the dropout masks at counter image * N + patch under `seed`
+ * (32 uniform bits).  len_keep = int(N * (1 - mask_ratio)) is the caller's (host double arithmetic, as HF); len_keep == N returns the
+ * whole shuffled order.  One workgroup per image, the keys in LDS: N <= 1024 (beyond: MOREC_E_UNSUPPORTED). */
+int morec_mae_keep_ids(const float* noise, uint64_t seed, int32_t* keep, int n_img, int N, int len_keep, void* stream);
+/* morec_swin_patchify / morec_swin_patchify_u8 for the kept patches only: out[i * len_keep + j] = the im2col row of patch keep[i, j] of
+ * image i, bit-equal to the full im2col followed by a row gather.  patch % 4 != 0, ld_out not a multiple of a 16-byte lane or a base
+ * pointer off 16 bytes: MOREC_E_ALIGN.  A keep entry outside [0, (R / patch)^2) leaves a zero row. */
+int morec_mae_patchify_keep(const float* pixels, const int32_t* keep, void* out, int n_img, int channels, int R, int patch, int len_keep,
+                            int ld_out, int dtype, void* stream);
+int morec_mae_patchify_keep_u8(const uint8_t* pixels_hwc, const int32_t* keep, void* out, int n_img, int channels, int R, int patch,
+                               int len_keep, int ld_out, float mean, float std, int dtype, void* stream);
+/* x[n_img, 1 + len_keep, C]: x[i, 0] = cls_token + pos[0], x[i, 1 + j] = e[i * len_keep + j] + pos[1 + keep[i, j]] (:259-267; e = the
+ * patch GEMM's output, bias included; cls_token fp32 [C], pos fp32 [N + 1, C]): one fp32 add, one rounding to the storage type.
+ * Backward: de = the patch rows of dx, d_cls[c] = sum_i dx[i, 0, c] (fp32, fixed order, WRITTEN not accumulated); the position table is
+ * frozen (requires_grad=False in HF) and has no gradient.  C % 8 != 0 (every dtype) or a base pointer off 16 bytes: MOREC_E_ALIGN. */
+int morec_mae_assemble_fwd(const void* e, const float* cls_token, const float* pos, const int32_t* keep, void* x, int n_img, int len_keep,
+                           int N, int C, int dtype, void* stream);
+int morec_mae_assemble_bwd(const void* dx, void* de, float* d_cls, int n_img, int len_keep, int C, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * BCE variant, one sampled negative per position (bce_text/main-end2end/model/model.py:30-51).
  * E [B, S+1, 2, D] item vectors (pos at [:, :, 0], neg at [:, :, 1]), P [B, S, D] user states, row_valid u8 [B*S].
  * scores fp32 [2][B*S] (pos | neg) are saved for the backward; loss_sum[0] += sum_valid softplus(-pos) + softplus(neg).
