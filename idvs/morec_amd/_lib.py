@@ -175,6 +175,16 @@ _SIGS = {
                                              _P]),
     "morec_mae_assemble_fwd": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "morec_mae_assemble_bwd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "morec_attn_bias_ws_bytes": (C.c_size_t, [C.POINTER(AttnDesc)]),
+    "morec_attn_bias_fwd": (C.c_int, [C.POINTER(AttnDesc), _P, _P, _P, _P, _P]),
+    "morec_attn_bias_bwd": (C.c_int, [C.POINTER(AttnDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "morec_beit_bias_expand": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "morec_beit_bias_reduce": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "morec_layerscale_res_fwd": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, C.c_long, C.c_int, C.c_int, _P]),
+    "morec_layerscale_res_bwd": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_long, C.c_int, C.c_int, _P]),
+    "morec_beit_pool_fwd": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "morec_beit_pool_bwd": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "morec_beit_assemble_fwd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "morec_image_resize_u8": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P]),
     "morec_comm_available": (C.c_int, []),
     "morec_comm_unique_id": (C.c_int, [_P]),

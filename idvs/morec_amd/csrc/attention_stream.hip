@@ -20,6 +20,9 @@
 //   streamgen -- everything else (fp32 storage, other head widths): one wavefront per (sequence, head), fp32 arithmetic on the 4 x 4
 //                register blocks of attention_valu.hpp: the row-strip kernels' phases with the strip cut into 32-key tiles.  Correctness
 //                first: the forward runs a statistics pass and then recomputes the score tiles once per 64-column chunk of the head width.
+//
+// Both families also exist with a per-head additive position bias (BIAS = true, morec_attn_bias_fwd / _bwd; see StreamArgs below); only
+// those hand anything to another kernel: the row statistics, in the caller's workspace, for the bias-gradient pass at the end of the file.
 #include <stdio.h>
 #include <stdlib.h>
 #include "common.hpp"
@@ -39,6 +42,21 @@ __device__ __forceinline__ float masked_score(float s, float scale, float add) {
     const float t = s * scale;
     return t + add;
 }
+
+// The position-bias variants (morec_attn_bias_fwd / _bwd, the BEiT tower): BIAS = true instantiations of the same kernels.  The bias is
+// fp32 [heads][T][Tp], Tp = 64 ceil(T / 64) (rows padded to the key-tile width, pad cells zero), the same for every sequence, and is added
+// in fp32 AFTER the mask.  A lane reads the cells of its own scores straight from global memory (the table of a layer stays in cache):
+// rows are clamped to the sequence, columns stay below Tp by the layout, and a cell past the sequence only ever meets a score that is
+// already -inf.  BIAS = false is the code it was: StreamArgs<false> is AttnArgs, no pointer is read and the LDS plan is untouched.
+template <bool BIAS>
+struct StreamArgs : AttnArgs {};
+template <>
+struct StreamArgs<true> : AttnArgs {
+    const float* bias;      // [heads][T][Tp]
+    float* stats;           // backward: m, 1 / l, delta of every query row, [n_seq * heads][3][T], for the bias-gradient pass; or nullptr
+    int Tp;
+};
+constexpr int BIAS_NCH = 8;      // the bias-gradient pass folds the sequences in this many chunks, in chunk order
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // stream16
@@ -157,6 +175,22 @@ __device__ __forceinline__ void s16_mask(f32x4_t (&s)[4], const AttnArgs& a, con
             s[kb][r] = (j < L) ? v : -INFINITY;
         }
 }
+// the bias cells of the same scores: row i (clamped by the caller) of one head's table, 16 bytes per 16-key block
+__device__ __forceinline__ void s16_bias_load(const float* __restrict__ brow, int jb, int g, f32x4_t (&b)[4]) {
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb) b[kb] = *reinterpret_cast<const f32x4_t*>(brow + jb + kb * 16 + 4 * g);
+}
+// the same for a transposed tile: the lane's row is key j, its cells are the queries i = ib + qb*16 + 4g + r (clamped to the sequence)
+__device__ __forceinline__ void s16_bias_load_t(const float* __restrict__ bhead, int Tp, int j, int ib, int g, int L, f32x4_t (&b)[4]) {
+#pragma unroll
+    for (int qb = 0; qb < 4; ++qb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) b[qb][r] = bhead[(size_t)min(ib + qb * 16 + 4 * g + r, L - 1) * Tp + j];
+}
+__device__ __forceinline__ void s16_bias_add(f32x4_t (&s)[4], const f32x4_t (&b)[4]) {
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb) s[kb] += b[kb];
+}
 // dropout factors (0 or 1 / (1 - p)) of the same cells
 __device__ __forceinline__ void s16_drop(const AttnArgs& a, const S16Seq& q, int i, int jb, int g, float (&ks)[4][4]) {
 #pragma unroll
@@ -168,8 +202,8 @@ __device__ __forceinline__ void s16_drop(const AttnArgs& a, const S16Seq& q, int
     }
 }
 
-template <typename T16, int NC>
-__global__ __launch_bounds__(256) void attn_fwd_stream16_kernel(AttnArgs a) {
+template <typename T16, int NC, bool BIAS>
+__global__ __launch_bounds__(256) void attn_fwd_stream16_kernel(StreamArgs<BIAS> a) {
     S16Seq q;
     if (!s16_enter(a, a.ctx, (size_t)a.n_heads * a.dh * 2, q)) return;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -196,8 +230,11 @@ __global__ __launch_bounds__(256) void attn_fwd_stream16_kernel(AttnArgs a) {
             s16_stage<NC>(qkv, q.row0, pitch, 2 * H + q.head * a.dh, a.dh, kt * SKT, L, sV);
             __syncthreads();
             f32x4_t s[4];
+            [[maybe_unused]] f32x4_t bz[4];
+            if constexpr (BIAS) s16_bias_load(a.bias + ((size_t)q.head * a.T + min(i, L - 1)) * a.Tp, kt * SKT, g, bz);
             s16_dots<T16, NC>(sK, pb, nch, lane, qf, s);
             s16_mask(s, a, sKeep, i, kt * SKT, g, L);
+            if constexpr (BIAS) s16_bias_add(s, bz);
             float mt = -INFINITY;
 #pragma unroll
             for (int kb = 0; kb < 4; ++kb)
@@ -246,8 +283,8 @@ __global__ __launch_bounds__(256) void attn_fwd_stream16_kernel(AttnArgs a) {
 
 // Backward: (A) m, 1 / l, delta = rowsum(P o dP) of every query row into LDS, delta accumulated next to l with the same rescaling;
 // (B) dQ per query round; (C) dK, dV per key round, the score tiles computed transposed (the lane's row is its key).
-template <typename T16, int NC>
-__global__ __launch_bounds__(256) void attn_bwd_stream16_kernel(AttnArgs a) {
+template <typename T16, int NC, bool BIAS>
+__global__ __launch_bounds__(256) void attn_bwd_stream16_kernel(StreamArgs<BIAS> a) {
     S16Seq q;
     if (!s16_enter(a, a.dqkv, (size_t)3 * a.n_heads * a.dh * 2, q)) return;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -279,9 +316,12 @@ __global__ __launch_bounds__(256) void attn_bwd_stream16_kernel(AttnArgs a) {
             s16_stage<NC>(qkv, q.row0, pitch, colV, a.dh, kt * SKT, L, sB);
             __syncthreads();
             f32x4_t s[4], dp[4];
+            [[maybe_unused]] f32x4_t bz[4];
+            if constexpr (BIAS) s16_bias_load(a.bias + ((size_t)q.head * a.T + min(i, L - 1)) * a.Tp, kt * SKT, g, bz);
             s16_dots<T16, NC>(sA, pb, nch, lane, qf, s);
             s16_dots<T16, NC>(sB, pb, nch, lane, of, dp);
             s16_mask(s, a, sKeep, i, kt * SKT, g, L);
+            if constexpr (BIAS) s16_bias_add(s, bz);
             if (a.drop.thresh) {
                 float ks[4][4];
                 s16_drop(a, q, i, kt * SKT, g, ks);
@@ -313,6 +353,13 @@ __global__ __launch_bounds__(256) void attn_bwd_stream16_kernel(AttnArgs a) {
         const float inv = (i < L) ? 1.0f / l : 0.f;      // rows past the sequence contribute nothing to dK / dV
         if (g == 0) { st_m[i] = m; st_i[i] = inv; st_d[i] = dl * inv; }
     }
+    if constexpr (BIAS) {
+        if (a.stats) {      // the row statistics leave for the bias-gradient pass
+            __syncthreads();
+            float* st = a.stats + (size_t)blockIdx.x * 3 * a.T;
+            for (int i = threadIdx.x; i < L; i += 256) { st[i] = st_m[i]; st[a.T + i] = st_i[i]; st[2 * a.T + i] = st_d[i]; }
+        }
+    }
     // ---- pass B: dQ
     for (int rd = 0; rd < q.nkt; ++rd) {
         const int i = rd * SKT + wave * 16 + c;
@@ -330,9 +377,12 @@ __global__ __launch_bounds__(256) void attn_bwd_stream16_kernel(AttnArgs a) {
             __syncthreads();
             if (kt == 0) { m = st_m[i]; inv = st_i[i]; delta = st_d[i]; }
             f32x4_t s[4], dp[4];
+            [[maybe_unused]] f32x4_t bz[4];
+            if constexpr (BIAS) s16_bias_load(a.bias + ((size_t)q.head * a.T + min(i, L - 1)) * a.Tp, kt * SKT, g, bz);
             s16_dots<T16, NC>(sA, pb, nch, lane, qf, s);
             s16_dots<T16, NC>(sB, pb, nch, lane, of, dp);
             s16_mask(s, a, sKeep, i, kt * SKT, g, L);
+            if constexpr (BIAS) s16_bias_add(s, bz);
             float ks[4][4];
             if (a.drop.thresh) s16_drop(a, q, i, kt * SKT, g, ks);
 #pragma unroll
@@ -363,6 +413,8 @@ __global__ __launch_bounds__(256) void attn_bwd_stream16_kernel(AttnArgs a) {
             s16_stage<NC>(dctx, q.row0, H, colQ, a.dh, qt * SKT, L, sB);
             __syncthreads();
             f32x4_t s[4], dp[4];      // [key = the lane's j][query = qt*64 + qb*16 + 4g + r]
+            [[maybe_unused]] f32x4_t bz[4];
+            if constexpr (BIAS) s16_bias_load_t(a.bias + (size_t)q.head * a.T * a.Tp, a.Tp, j, qt * SKT, g, L, bz);
             s16_dots<T16, NC>(sA, pb, nch, lane, kf, s);
             s16_dots<T16, NC>(sB, pb, nch, lane, vf, dp);
 #pragma unroll
@@ -371,7 +423,8 @@ __global__ __launch_bounds__(256) void attn_bwd_stream16_kernel(AttnArgs a) {
                 for (int r = 0; r < 4; ++r) {
                     const int i = qt * SKT + qb * 16 + 4 * g + r;
                     const bool kept = jkeep && (!a.causal || j <= i);
-                    const float v = masked_score(s[qb][r], a.scale, kept ? 0.f : a.mask_value);
+                    float v = masked_score(s[qb][r], a.scale, kept ? 0.f : a.mask_value);
+                    if constexpr (BIAS) v += bz[qb][r];
                     const float p = (j < L) ? expf(v - st_m[i]) * st_i[i] : 0.f;      // st_i = 0 for query rows past the sequence
                     float ksc = 1.f;
                     if (a.drop.thresh)
@@ -389,17 +442,17 @@ __global__ __launch_bounds__(256) void attn_bwd_stream16_kernel(AttnArgs a) {
     }
 }
 
-template <typename T16, int NC>
-void s16_launch(bool backward, const AttnArgs& a, dim3 grid, size_t lds, hipStream_t s) {
+template <typename T16, int NC, bool BIAS>
+void s16_launch(bool backward, const StreamArgs<BIAS>& a, dim3 grid, size_t lds, hipStream_t s) {
     // the tiles of a 256-wide head pass the 64 KB a kernel gets without asking
-    static const hipError_t rc_f = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_stream16_kernel<T16, NC>),
+    static const hipError_t rc_f = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_stream16_kernel<T16, NC, BIAS>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)s16_lds(32 * NC));
-    static const hipError_t rc_b = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_stream16_kernel<T16, NC>),
+    static const hipError_t rc_b = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_stream16_kernel<T16, NC, BIAS>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)s16_lds(32 * NC));
     (void)rc_f;
     (void)rc_b;
-    if (backward) hipLaunchKernelGGL((attn_bwd_stream16_kernel<T16, NC>), grid, dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((attn_fwd_stream16_kernel<T16, NC>), grid, dim3(256), lds, s, a);
+    if (backward) hipLaunchKernelGGL((attn_bwd_stream16_kernel<T16, NC, BIAS>), grid, dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((attn_fwd_stream16_kernel<T16, NC, BIAS>), grid, dim3(256), lds, s, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
@@ -451,6 +504,15 @@ __device__ __forceinline__ void gen_mask(float (&s)[4][4], const AttnArgs& a, in
             s[r][c] = (j < L) ? masked_score(s[r][c], a.scale, kept ? 0.f : a.mask_value) : -INFINITY;
         }
 }
+// + the bias cells of the same block (rows clamped to the sequence; the columns of a 32-key tile stay below Tp)
+__device__ __forceinline__ void gen_bias(float (&s)[4][4], const float* __restrict__ bhead, int Tp, int L, int qt, int kt) {
+    const int lane = threadIdx.x, i0 = (lane >> 3) * 4, j0 = (lane & 7) * 4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float4 b = *reinterpret_cast<const float4*>(bhead + (size_t)min(qt * 32 + i0 + r, L - 1) * Tp + kt * 32 + j0);
+        s[r][0] += b.x; s[r][1] += b.y; s[r][2] += b.z; s[r][3] += b.w;
+    }
+}
 __device__ __forceinline__ float row8_max(float v) {
     v = fmaxf(v, __shfl_xor(v, 1, 64));
     v = fmaxf(v, __shfl_xor(v, 2, 64));
@@ -499,8 +561,8 @@ __device__ __forceinline__ bool gen_enter(AttnArgs& a, void* out, size_t out_row
 constexpr size_t gen_fwd_lds() { return (size_t)(3 * 32 * LP + 32 * LPP) * sizeof(float); }
 constexpr size_t gen_bwd_lds() { return (size_t)(4 * 32 * LP + 2 * 32 * LPP + 3 * ST_MAX) * sizeof(float); }
 
-template <typename T>
-__global__ __launch_bounds__(64) void attn_fwd_streamgen_kernel(AttnArgs a) {
+template <typename T, bool BIAS>
+__global__ __launch_bounds__(64) void attn_fwd_streamgen_kernel(StreamArgs<BIAS> a) {
     GenSeq q;
     if (!gen_enter(a, a.ctx, (size_t)a.n_heads * a.dh * sizeof(T), q)) return;
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
@@ -523,6 +585,7 @@ __global__ __launch_bounds__(64) void attn_fwd_streamgen_kernel(AttnArgs a) {
             float s[4][4];
             gen_dot<T>(qkv, pitch, colQ, qkv, pitch, colK, q.row0, a.dh, L, qt, kt, sA, sB, s);
             gen_mask(s, a, L, qt, kt, keep_row);
+            if constexpr (BIAS) gen_bias(s, a.bias + (size_t)q.head * a.T * a.Tp, a.Tp, L, qt, kt);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float mn = fmaxf(m[r], row8_max(fmaxf(fmaxf(s[r][0], s[r][1]), fmaxf(s[r][2], s[r][3]))));      // finite: tile 0 holds key 0
@@ -543,6 +606,7 @@ __global__ __launch_bounds__(64) void attn_fwd_streamgen_kernel(AttnArgs a) {
                 float s[4][4];
                 gen_dot<T>(qkv, pitch, colQ, qkv, pitch, colK, q.row0, a.dh, L, qt, kt, sA, sB, s);
                 gen_mask(s, a, L, qt, kt, keep_row);
+                if constexpr (BIAS) gen_bias(s, a.bias + (size_t)q.head * a.T * a.Tp, a.Tp, L, qt, kt);
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -564,8 +628,8 @@ __global__ __launch_bounds__(64) void attn_fwd_streamgen_kernel(AttnArgs a) {
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(64) void attn_bwd_streamgen_kernel(AttnArgs a) {
+template <typename T, bool BIAS>
+__global__ __launch_bounds__(64) void attn_bwd_streamgen_kernel(StreamArgs<BIAS> a) {
     GenSeq q;
     if (!gen_enter(a, a.dqkv, (size_t)3 * a.n_heads * a.dh * sizeof(T), q)) return;
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
@@ -600,6 +664,7 @@ __global__ __launch_bounds__(64) void attn_bwd_streamgen_kernel(AttnArgs a) {
             gen_dot<T>(qkv, pitch, colQ, qkv, pitch, colK, q.row0, a.dh, L, qt, kt, sA, sB, s);
             gen_dot<T>(dctx, H, colQ, qkv, pitch, colV, q.row0, a.dh, L, qt, kt, sA, sB, dp);
             gen_mask(s, a, L, qt, kt, keep_row);
+            if constexpr (BIAS) gen_bias(s, a.bias + (size_t)q.head * a.T * a.Tp, a.Tp, L, qt, kt);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float mn = fmaxf(m[r], row8_max(fmaxf(fmaxf(s[r][0], s[r][1]), fmaxf(s[r][2], s[r][3]))));
@@ -626,12 +691,19 @@ __global__ __launch_bounds__(64) void attn_bwd_streamgen_kernel(AttnArgs a) {
         }
     }
     __syncthreads();
+    if constexpr (BIAS) {
+        if (a.stats) {      // the row statistics leave for the bias-gradient pass
+            float* st = a.stats + (size_t)blockIdx.x * 3 * a.T;
+            for (int i = lane; i < L; i += 64) { st[i] = st_m[i]; st[a.T + i] = st_i[i]; st[2 * a.T + i] = st_d[i]; }
+        }
+    }
     // P (dropped) and dS of the lane's 4 x 4 block of tile (qt, kt) from the stored statistics
     auto tile_p_ds = [&](int qt, int kt, float (&p)[4][4], float (&ds)[4][4]) {
         float s[4][4], dp[4][4];
         gen_dot<T>(qkv, pitch, colQ, qkv, pitch, colK, q.row0, a.dh, L, qt, kt, sA, sB, s);
         gen_dot<T>(dctx, H, colQ, qkv, pitch, colV, q.row0, a.dh, L, qt, kt, sA, sB, dp);
         gen_mask(s, a, L, qt, kt, keep_row);
+        if constexpr (BIAS) gen_bias(s, a.bias + (size_t)q.head * a.T * a.Tp, a.Tp, L, qt, kt);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int i = qt * 32 + i0 + r;
@@ -689,32 +761,260 @@ __global__ __launch_bounds__(64) void attn_bwd_streamgen_kernel(AttnArgs a) {
             store_rows<T, LCW, 4>(dqkv, q.row0 + (size_t)kt * 32, pitch, colV + d0 + c0, i0, klen, d0 + c0, a.dh, ov);
         }
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// bias gradient: d_pos_bias[h][i][j] = sum over the sequences of dS[n, h, i, j], dS = P o (dP - delta) -- the gradient at the score, so
+// `scale` is not applied.  The backward kernels above leave m, 1 / l and delta of every query row in `stats`; a workgroup here owns one
+// (head, query block, key block) tile and one of BIAS_NCH chunks of the sequences, walks its sequences in index order, recomputes the S
+// and dP tiles and keeps the dS sums in registers (fp32, never rounded to the storage type).  The chunk partials are then added in chunk
+// order by attn_bias_fold_kernel: no atomics, one fixed order, the same bits on every call.
+// ---------------------------------------------------------------------------------------------------------------------------------------
+struct BiasGradArgs : StreamArgs<true> {      // ctx = dctx; stats is read
+    float* part;                              // [BIAS_NCH][heads][T][Tp]; cells with j >= T are neither written nor read
+};
+
+template <typename T16, int NC>
+__global__ __launch_bounds__(256) void attn_bias_grad16_kernel(BiasGradArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int pb = s16_pitch(a.dh), nch = a.dh / 32;
+    char* sK = smem;
+    char* sV = sK + SKT * pb;
+    float* sKeep = reinterpret_cast<float*>(sV + SKT * pb);      // the flags of the 64 keys of the tile
+    const int nt = a.Tp / SKT;
+    const int head = blockIdx.x / (nt * nt), rem = blockIdx.x % (nt * nt), qb = rem / nt, kb = rem % nt;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+    const int H = a.n_heads * a.dh, pitch = 3 * H, L = a.T;
+    const bf16* qkv = reinterpret_cast<const bf16*>(a.qkv);
+    const bf16* dctx = reinterpret_cast<const bf16*>(a.ctx);
+    const int colQ = head * a.dh, colK = H + colQ, colV = 2 * H + colQ;
+    const int i = qb * SKT + wave * 16 + c, ic = min(i, L - 1);      // the lane's query row
+    const int per = (a.n_seq + BIAS_NCH - 1) / BIAS_NCH, s0 = blockIdx.y * per, s1 = min(s0 + per, a.n_seq);
+    f32x4_t bz[4], acc[4];
+    s16_bias_load(a.bias + ((size_t)head * a.T + ic) * a.Tp, kb * SKT, g, bz);
+    const f32x4_t zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[k] = zero;
+    for (int seq = s0; seq < s1; ++seq) {
+        const size_t row0 = (size_t)seq * a.T;
+        bf16x8_t qf[NC], of[NC];
+        s16_row_frags<NC>(qkv, row0, pitch, colQ, a.dh, i, L, g, qf);
+        s16_row_frags<NC>(dctx, row0, H, colQ, a.dh, i, L, g, of);
+        const float* st = a.stats + ((size_t)seq * a.n_heads + head) * 3 * a.T;
+        const float m = st[ic], inv = st[a.T + ic], delta = st[2 * a.T + ic];
+        __syncthreads();      // the tiles of the previous sequence are consumed
+        s16_stage<NC>(qkv, row0, pitch, colK, a.dh, kb * SKT, L, sK);
+        s16_stage<NC>(qkv, row0, pitch, colV, a.dh, kb * SKT, L, sV);
+        if (threadIdx.x < SKT) {
+            const int j = kb * SKT + threadIdx.x;
+            const float v = a.key_keep[row0 + min(j, L - 1)];
+            sKeep[threadIdx.x] = j < L ? v : 0.f;
+        }
+        __syncthreads();
+        f32x4_t s[4], dp[4];
+        s16_dots<T16, NC>(sK, pb, nch, lane, qf, s);
+        s16_dots<T16, NC>(sV, pb, nch, lane, of, dp);
+        s16_mask(s, a, sKeep - kb * SKT, i, kb * SKT, g, L);      // (s16_mask indexes the flags by the key's position in the sequence)
+        s16_bias_add(s, bz);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float p = expf(s[k][r] - m) * inv;      // 0 for keys past the sequence (-inf)
+                acc[k][r] += p * (dp[k][r] - delta);
+            }
+    }
+    if (i < L) {
+        float* dst = a.part + (((size_t)blockIdx.y * a.n_heads + head) * a.T + i) * a.Tp + kb * SKT;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) *reinterpret_cast<f32x4_t*>(dst + k * 16 + 4 * g) = acc[k];
+    }
+}
+
+// the same on streamgen's 32 x 32 tiles: one wavefront per (head, query tile, key tile) and chunk
+template <typename T>
+__global__ __launch_bounds__(64) void attn_bias_gradgen_kernel(BiasGradArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem_f[];
+    float* sA = smem_f;
+    float* sB = sA + 32 * LP;
+    const int nt = (a.T + 31) / 32;
+    const int head = blockIdx.x / (nt * nt), rem = blockIdx.x % (nt * nt), qt = rem / nt, kt = rem % nt;
+    const int lane = threadIdx.x, i0 = (lane >> 3) * 4, j0 = (lane & 7) * 4;
+    const int H = a.n_heads * a.dh, pitch = 3 * H, L = a.T;
+    const T* qkv = reinterpret_cast<const T*>(a.qkv);
+    const T* dctx = reinterpret_cast<const T*>(a.ctx);
+    const int colQ = head * a.dh, colK = H + colQ, colV = 2 * H + colQ;
+    const int per = (a.n_seq + BIAS_NCH - 1) / BIAS_NCH, s0 = blockIdx.y * per, s1 = min(s0 + per, a.n_seq);
+    const float* bhead = a.bias + (size_t)head * a.T * a.Tp;
+    float acc[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = 0.f;
+    for (int seq = s0; seq < s1; ++seq) {
+        const size_t row0 = (size_t)seq * a.T;
+        float s[4][4], dp[4][4];
+        gen_dot<T>(qkv, pitch, colQ, qkv, pitch, colK, row0, a.dh, L, qt, kt, sA, sB, s);
+        gen_dot<T>(dctx, H, colQ, qkv, pitch, colV, row0, a.dh, L, qt, kt, sA, sB, dp);
+        gen_mask(s, a, L, qt, kt, a.key_keep + row0);
+        gen_bias(s, bhead, a.Tp, L, qt, kt);
+        const float* st = a.stats + ((size_t)seq * a.n_heads + head) * 3 * a.T;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ic = min(qt * 32 + i0 + r, L - 1);
+            const float m = st[ic], inv = st[a.T + ic], delta = st[2 * a.T + ic];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[r][c] += expf(s[r][c] - m) * inv * (dp[r][c] - delta);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int i = qt * 32 + i0 + r;
+        if (i < L)
+            *reinterpret_cast<float4*>(a.part + (((size_t)blockIdx.y * a.n_heads + head) * a.T + i) * a.Tp + kt * 32 + j0) =
+                make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+    }
+}
+
+// out[e] = part[0][e] + part[1][e] + ... in chunk order; the pad cells of a row (j >= T) are written as zero
+__global__ __launch_bounds__(256) void attn_bias_fold_kernel(const float* __restrict__ part, float* __restrict__ out, size_t n, int T, int Tp) {
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
+        float acc = 0.f;
+        if ((int)(e % Tp) < T)
+            for (int c = 0; c < BIAS_NCH; ++c) acc += part[(size_t)c * n + e];
+        out[e] = acc;
+    }
+}
+
+template <typename T16, int NC>
+void bias_grad16_launch(const BiasGradArgs& a, dim3 grid, hipStream_t s) {
+    const size_t lds = 2 * SKT * s16_pitch(a.dh) + SKT * sizeof(float);
+    static const hipError_t rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bias_grad16_kernel<T16, NC>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     (int)(2 * SKT * s16_pitch(32 * NC) + SKT * sizeof(float)));
+    (void)rc;
+    hipLaunchKernelGGL((attn_bias_grad16_kernel<T16, NC>), grid, dim3(256), lds, s, a);
+}
+
+inline bool stream16_shape(const morec_attn_desc* d) { return is_h16(d->dtype) && d->dh % 32 == 0 && d->dh <= 256; }
+
+// stream16 for 16-bit storage with a head width that is a multiple of 32 and at most 256, streamgen for everything else
+template <bool BIAS>
+int stream_launch(const morec_attn_desc* d, const StreamArgs<BIAS>& a, dim3 grid, bool backward, hipStream_t s) {
+    if (stream16_shape(d)) {
+        const size_t lds = s16_lds(d->dh);
+        by_h16(d->dtype, [&](auto* t) {
+            using T = MOREC_TAG_T(t);
+            if (d->dh <= 64) s16_launch<T, 2, BIAS>(backward, a, grid, lds, s);
+            else if (d->dh <= 128) s16_launch<T, 4, BIAS>(backward, a, grid, lds, s);
+            else s16_launch<T, 8, BIAS>(backward, a, grid, lds, s);
+        });
+    } else if (!by_dtype(d->dtype, [&](auto* t) {
+                   using T = MOREC_TAG_T(t);
+                   if (backward) hipLaunchKernelGGL((attn_bwd_streamgen_kernel<T, BIAS>), grid, dim3(64), gen_bwd_lds(), s, a);
+                   else hipLaunchKernelGGL((attn_fwd_streamgen_kernel<T, BIAS>), grid, dim3(64), gen_fwd_lds(), s, a);
+               }))
+        return MOREC_E_DTYPE;
+    MOREC_CHECK_LAUNCH();
+    return MOREC_OK;
+}
+
+// what the bias entry points take: the descriptor is judged before any pointer
+int bias_check_desc(const morec_attn_desc* d) {
+    if (!d) return MOREC_E_ARG;
+    if (d->n_seq <= 0 || d->T <= 0 || d->n_heads <= 0 || d->dh <= 0) return MOREC_E_ARG;
+    if (d->p_drop < 0.f || d->p_drop >= 1.f) return MOREC_E_ARG;
+    if (d->causal != 0 || d->p_drop > 0.f || d->cu_seqlens != nullptr || d->T > ST_MAX) return MOREC_E_UNSUPPORTED;      // no caller uses them
+    if (d->dh % 8) return MOREC_E_ALIGN;
+    if (d->dtype != MOREC_F32 && !is_h16(d->dtype)) return MOREC_E_DTYPE;
+    return MOREC_OK;
+}
+inline int bias_tp(int T) { return (T + SKT - 1) / SKT * SKT; }
+inline size_t bias_stats_floats(const morec_attn_desc* d) { return ((size_t)d->n_seq * d->n_heads * 3 * d->T + 3) & ~(size_t)3; }
+inline size_t bias_table_floats(const morec_attn_desc* d) { return (size_t)d->n_heads * d->T * bias_tp(d->T); }
+
+StreamArgs<true> bias_args(const morec_attn_desc* d, const void* qkv, const float* key_keep, const float* pos_bias, void* ctx_or_dctx,
+                           void* dqkv, float* stats) {
+    StreamArgs<true> a;
+    static_cast<AttnArgs&>(a) = AttnArgs{qkv, key_keep, ctx_or_dctx, dqkv, d->n_seq, d->T, d->n_heads, d->dh, 0, d->scale, d->mask_value,
+                                         make_drop(0.f, 0), nullptr, 0};
+    a.bias = pos_bias;
+    a.stats = stats;
+    a.Tp = bias_tp(d->T);
+    return a;
+}
 }  // namespace
 
 int attn_spare_blocks(const morec_attn_desc* d);      // attention.hip
 
-// The streaming kernels of a checked call (attn_dispatch in attention.hip decides WHETHER they run): stream16 for 16-bit storage with a head
-// width that is a multiple of 32 and at most 256, streamgen for everything else.  MOREC_E_UNSUPPORTED: a sequence beyond the cap.
+// The streaming kernels of a checked call (attn_dispatch in attention.hip decides WHETHER they run).  MOREC_E_UNSUPPORTED: a sequence
+// beyond the cap.
 int morec_attn_stream_launch(const morec_attn_desc* d, const void* qkv, const float* key_keep, void* ctx_or_dctx, void* dqkv, bool backward,
                              hipStream_t s) {
     if (d->T > ST_MAX) return MOREC_E_UNSUPPORTED;
-    AttnArgs a{qkv, key_keep, ctx_or_dctx, dqkv, d->n_seq, d->T, d->n_heads, d->dh, d->causal, d->scale, d->mask_value,
-               make_drop(d->p_drop, d->seed), d->cu_seqlens, d->total_rows};
-    dim3 grid(d->n_seq * d->n_heads + attn_spare_blocks(d));
-    if (is_h16(d->dtype) && d->dh % 32 == 0 && d->dh <= 256) {
-        const size_t lds = s16_lds(d->dh);
+    StreamArgs<false> a;
+    static_cast<AttnArgs&>(a) = AttnArgs{qkv, key_keep, ctx_or_dctx, dqkv, d->n_seq, d->T, d->n_heads, d->dh, d->causal, d->scale, d->mask_value,
+                                         make_drop(d->p_drop, d->seed), d->cu_seqlens, d->total_rows};
+    return stream_launch<false>(d, a, dim3(d->n_seq * d->n_heads + attn_spare_blocks(d)), backward, s);
+}
+
+// ---- attention with a per-head position bias (include/morec_hip.h: morec_attn_bias_fwd) ------------------------------------------------
+extern "C" size_t morec_attn_bias_ws_bytes(const morec_attn_desc* d) {
+    if (bias_check_desc(d) != MOREC_OK) return 0;
+    return (bias_stats_floats(d) + (size_t)BIAS_NCH * bias_table_floats(d)) * sizeof(float);
+}
+
+extern "C" int morec_attn_bias_fwd(const morec_attn_desc* d, const void* qkv, const float* key_keep, const float* pos_bias, void* ctx,
+                                   void* stream) {
+    const int rc = bias_check_desc(d);
+    if (rc) return rc;
+    if (!qkv || !key_keep || !pos_bias || !ctx) return MOREC_E_ARG;
+    if (!aligned16(qkv) || !aligned16(pos_bias) || !aligned16(ctx)) return MOREC_E_ALIGN;
+    return stream_launch<true>(d, bias_args(d, qkv, key_keep, pos_bias, ctx, nullptr, nullptr), dim3(d->n_seq * d->n_heads), false,
+                               reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int morec_attn_bias_bwd(const morec_attn_desc* d, const void* qkv, const float* key_keep, const float* pos_bias, const void* dctx,
+                                   void* dqkv, float* dqkv_bias, float* d_pos_bias, float* ws, size_t ws_bytes, void* stream) {
+    int rc = bias_check_desc(d);
+    if (rc) return rc;
+    if (!qkv || !key_keep || !pos_bias || !dctx || !dqkv) return MOREC_E_ARG;
+    if (d_pos_bias && (!ws || ws_bytes < morec_attn_bias_ws_bytes(d))) return MOREC_E_ARG;
+    if (!aligned16(qkv) || !aligned16(pos_bias) || !aligned16(dctx) || !aligned16(dqkv) || (d_pos_bias && (!aligned16(d_pos_bias) || !aligned16(ws))))
+        return MOREC_E_ALIGN;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    rc = stream_launch<true>(d, bias_args(d, qkv, key_keep, pos_bias, const_cast<void*>(dctx), dqkv, d_pos_bias ? ws : nullptr),
+                             dim3(d->n_seq * d->n_heads), true, s);
+    if (rc) return rc;
+    const int H3 = 3 * d->n_heads * d->dh;
+    if (dqkv_bias) {
+        rc = morec_colsum(dqkv, dqkv_bias, d->n_seq * d->T, H3, H3, d->dtype, stream);
+        if (rc) return rc;
+    }
+    if (!d_pos_bias) return MOREC_OK;      // a frozen table: nothing more is launched
+    BiasGradArgs g;
+    static_cast<StreamArgs<true>&>(g) = bias_args(d, qkv, key_keep, pos_bias, const_cast<void*>(dctx), nullptr, ws);
+    g.part = ws + bias_stats_floats(d);
+    if (stream16_shape(d)) {
+        const int nt = g.Tp / SKT;
+        dim3 grid(d->n_heads * nt * nt, BIAS_NCH);
         by_h16(d->dtype, [&](auto* t) {
             using T = MOREC_TAG_T(t);
-            if (d->dh <= 64) s16_launch<T, 2>(backward, a, grid, lds, s);
-            else if (d->dh <= 128) s16_launch<T, 4>(backward, a, grid, lds, s);
-            else s16_launch<T, 8>(backward, a, grid, lds, s);
+            if (d->dh <= 64) bias_grad16_launch<T, 2>(g, grid, s);
+            else if (d->dh <= 128) bias_grad16_launch<T, 4>(g, grid, s);
+            else bias_grad16_launch<T, 8>(g, grid, s);
         });
-    } else if (!by_dtype(d->dtype, [&](auto* t) {
-                   using T = MOREC_TAG_T(t);
-                   if (backward) hipLaunchKernelGGL((attn_bwd_streamgen_kernel<T>), grid, dim3(64), gen_bwd_lds(), s, a);
-                   else hipLaunchKernelGGL((attn_fwd_streamgen_kernel<T>), grid, dim3(64), gen_fwd_lds(), s, a);
-               }))
-        return MOREC_E_DTYPE;
+    } else {
+        const int nt = (d->T + 31) / 32;
+        dim3 grid(d->n_heads * nt * nt, BIAS_NCH);
+        by_dtype(d->dtype, [&](auto* t) {
+            using T = MOREC_TAG_T(t);
+            hipLaunchKernelGGL((attn_bias_gradgen_kernel<T>), grid, dim3(64), 2 * 32 * LP * sizeof(float), s, g);
+        });
+    }
+    MOREC_CHECK_LAUNCH();
+    const size_t n = bias_table_floats(d);
+    hipLaunchKernelGGL(attn_bias_fold_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 8192)), dim3(256), 0, s, g.part, d_pos_bias, n,
+                       d->T, g.Tp);
     MOREC_CHECK_LAUNCH();
     return MOREC_OK;
 }

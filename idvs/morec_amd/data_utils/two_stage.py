@@ -14,7 +14,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .. import engine, mae_engine, ops, swin_engine
+from .. import beit_engine, engine, mae_engine, ops, swin_engine
 from ..model.encoders import Bert_Encoder, MAE_Encoder, Vit_Encoder, resolve_fp32_gemm
 from .dataset import collate_bce_batch
 from .metrics import _module
@@ -40,6 +40,13 @@ def _text_features_fn(enc: Bert_Encoder):
 def _vision_features_fn(enc: Vit_Encoder):
     p = dict(enc.named_parameters())
     shape = enc.image_net.shape
+    if getattr(enc, "is_beit", False):      # the pooler output = the classifier's input
+        bprep = beit_engine.beit_prepare(p, shape, enc.compute_dtype, "image_net.", features_only=True)
+
+        def run_beit(pixels):
+            pooled, _ = beit_engine.beit_forward(p, bprep, shape, pixels, enc.compute_dtype, False, "image_net.", features_only=True)
+            return pooled.float()
+        return run_beit
     prep = swin_engine.swin_prepare(p, shape, enc.compute_dtype, "image_net.")
 
     def run(pixels):

@@ -8,7 +8,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from . import engine, mae_engine, ops, swin_engine
+from . import beit_engine, engine, mae_engine, ops, swin_engine
 
 
 def _zeros_like_params(names, params, skip=()):
@@ -140,6 +140,38 @@ class MaeEncoderFn(torch.autograd.Function):
             mae_engine.mae_backward(p, prep, saved, d_item.contiguous(), grads, prefix)
             engine.WgradStream.join(d_item.device)
         needs = ctx.needs[2:]
+        return (None, None) + tuple(grads.get(n) if nd else None for n, nd in zip(names, needs))
+
+
+class BeitEncoderFn(torch.autograd.Function):
+    """``Vit_Encoder.forward`` (``V/model/encoders.py:30-31``) over HF ``BeitForImageClassification`` arithmetic.  ``cfg = (names, shape,
+    dtype, prefix, drop, training)`` as ``SwinEncoderFn``'s.  A frozen bias table or layer scale gets no buffer: its gradient work is
+    skipped (``beit_engine.beit_backward``)."""
+
+    @staticmethod
+    def forward(ctx, pixels, cfg, *params):
+        names, shape, dtype, prefix, drop, training = cfg
+        p = dict(zip(names, params))
+        need = any(ctx.needs_input_grad)
+        prep = beit_engine.beit_prepare(p, shape, dtype, prefix)
+        item, saved = beit_engine.beit_forward(p, prep, shape, pixels, dtype, need, prefix, drop, training)
+        ctx.stuff = (p, prep, saved, names, prefix, shape)
+        ctx.needs = ctx.needs_input_grad
+        ctx.fp32_gemm = ops.FP32_GEMM
+        return item
+
+    @staticmethod
+    def backward(ctx, d_item):
+        p, prep, saved, names, prefix, shape = ctx.stuff
+        ctx.stuff = None
+        needs = ctx.needs[2:]
+        skip = {beit_engine.beit_layer_names(prefix, l) + f"attention.{n}" for l in range(shape.num_hidden_layers)
+                for n in ("q_proj.weight", "q_proj.bias", "k_proj.weight", "v_proj.weight", "v_proj.bias")}
+        skip |= {n for n, nd in zip(names, needs) if not nd and n.endswith((beit_engine.TABLE, ".lambda_1", ".lambda_2"))}
+        grads = _zeros_like_params(names, [p[n] for n in names], skip=skip)
+        with ops.fp32_gemm_mode(ctx.fp32_gemm):
+            beit_engine.beit_backward(p, prep, saved, d_item.contiguous(), grads, prefix)
+            engine.WgradStream.join(d_item.device)
         return (None, None) + tuple(grads.get(n) if nd else None for n, nd in zip(names, needs))
 
 

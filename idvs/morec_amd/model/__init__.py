@@ -2,6 +2,7 @@ from .model import Model  # noqa: F401  (same import surface as the reference: `
 from .encoders import ADD, CAT, Bert_Encoder, IdEmbedding, MAE_Encoder, Text_Encoder, User_Encoder  # noqa: F401
 from .bert import HipBertModel  # noqa: F401
 from .spec import BertShape  # noqa: F401
+from .beit import HipBeitForImageClassification  # noqa: F401
 from .mae import HipViTMAEModel  # noqa: F401
 from .bce import BceModel  # noqa: F401  (drop-in for bce_text/main-end2end/model/model.py)
 from .dssm import DssmModel, MLP_Encoder  # noqa: F401  (drop-in for bce_text/main-end2end(DSSM)/model/model.py)

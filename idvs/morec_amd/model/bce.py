@@ -10,7 +10,7 @@ from torch import nn
 from torch.nn.init import xavier_normal_
 
 from .. import engine, ops
-from .encoders import (Bert_Encoder, IdEmbedding, MAE_Encoder, User_Encoder, fusion_tower, is_mae_name, make_fusion, resolve_dtype, resolve_fp32_gemm,
+from .encoders import (Bert_Encoder, IdEmbedding, MAE_Encoder, User_Encoder, Vit_Encoder, fusion_tower, is_mae_name, make_fusion, resolve_dtype, resolve_fp32_gemm,
                        resolve_res32)
 
 
@@ -47,14 +47,17 @@ class BceModel(nn.Module):
         self.user_encoder = User_Encoder(item_num=item_num, max_seq_len=args.max_seq_len, item_dim=args.embedding_dim,
                                          num_attention_heads=args.num_attention_heads, dropout=args.drop_rate,
                                          n_layers=args.transformer_block, compute_dtype=self.compute_dtype, res32=resolve_res32(args))
-        # the vision twin (bce_vision/main-end2end/model/model.py): the MAE tower; Swin under this loss is not built
+        # the vision twin (bce_vision/main-end2end/model/model.py): the MAE and BEiT towers; Swin under this loss is not built
         self.vision = bool(self.use_modal and getattr(args, "CV_model_load", "None") not in ("None", None))
         if self.vision:
             cv = args.CV_model_load
-            if "swin" in cv or "resnet" in cv or "beit" in cv or not is_mae_name(cv):
-                raise NotImplementedError(f"BceModel: CV_model_load {cv!r}: only the MAE tower is built for the BCE loss (Swin runs under the "
-                                          "in-batch loss; ResNet / BEiT are not implemented)")
-            self.cv_encoder = MAE_Encoder(image_net=bert_model, item_dim=args.embedding_dim, compute_dtype=self.compute_dtype)
+            if "swin" in cv or "resnet" in cv or not ("beit" in cv or is_mae_name(cv)):
+                raise NotImplementedError(f"BceModel: CV_model_load {cv!r}: only the MAE and BEiT towers are built for the BCE loss (Swin "
+                                          "runs under the in-batch loss; ResNet is not implemented)")
+            if "beit" in cv:
+                self.cv_encoder = Vit_Encoder(image_net=bert_model, compute_dtype=self.compute_dtype, family="beit")
+            else:
+                self.cv_encoder = MAE_Encoder(image_net=bert_model, item_dim=args.embedding_dim, compute_dtype=self.compute_dtype)
         elif self.use_modal:
             self.bert_encoder = Bert_Encoder(args=args, bert_model=bert_model)
         # ID (+) modality fusion (bce_text/id_plus_mo-end2end/model/model.py:23-39): encoder AND fc AND id_embedding
@@ -75,7 +78,7 @@ class BceModel(nn.Module):
             return engine.NO_DROP, engine.NO_DROP, engine.NO_DROP
         self._drop_calls += 1
         base = (torch.initial_seed() * 0x9E3779B97F4A7C15 + self._drop_calls * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
-        d_item = engine.DropCfg(0.0, 0.0, base) if self.vision else engine.NO_DROP      # the MAE tower's patch-masking noise
+        d_item = engine.DropCfg(0.0, 0.0, base) if self.vision else engine.NO_DROP      # the MAE tower's patch-masking noise / the BEiT tower's DropPath streams
         return d_item, engine.NO_DROP, (engine.DropCfg(p, 0.0, base ^ 0x3C6EF372FE94F82B) if (self.fusion and p > 0) else engine.NO_DROP)
 
     def forward(self, *inputs, local_rank=None):

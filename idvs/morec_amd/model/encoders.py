@@ -12,6 +12,7 @@ from ..engine import NO_DROP, DropCfg
 from ..ops import FLT_MIN_MASK
 from .bert import HipBertModel
 from .swin import HipSwinForImageClassification
+from .beit import HipBeitForImageClassification, check_beit_config
 from .mae import HipViTMAEModel
 from ..mae_engine import MAE_SEED_EVAL, MAE_SEED_TRAIN, mae_keep
 from .modules import TransformerEncoder
@@ -206,23 +207,34 @@ class Bert_Encoder(nn.Module):
 
 class Vit_Encoder(nn.Module):
     """``V/model/encoders.py:24-31``: ``GELU(image_net(item_content)[0])`` with ``image_net`` a Swin classifier whose head
-    was replaced by ``Linear(num_features, embedding_dim)`` (``V/run.py:47-54``).  BEiT shares the class in the reference;
-    only Swin (the benchmarked tower, ``V/train_swin_tiny.py``) is implemented."""
+    was replaced by ``Linear(num_features, embedding_dim)`` (``V/run.py:47-54``).  BEiT shares the class, as in the reference
+    (``V/model/model.py:26-27``): a ``HipBeitForImageClassification`` container, a HF ``BeitForImageClassification`` or
+    ``family="beit"`` (the caller routes on the model's name) selects the BEiT tower (``beit_engine``)."""
 
-    def __init__(self, image_net, compute_dtype=None):
+    def __init__(self, image_net, compute_dtype=None, family=None):
         super().__init__()
-        self.image_net = image_net if isinstance(image_net, HipSwinForImageClassification) \
-            else HipSwinForImageClassification.from_hf(image_net)
+        if isinstance(image_net, (HipSwinForImageClassification, HipBeitForImageClassification)):
+            self.image_net = image_net
+        elif family == "beit" or getattr(getattr(image_net, "config", None), "model_type", None) == "beit":
+            self.image_net = HipBeitForImageClassification.from_hf(image_net)
+        else:
+            self.image_net = HipSwinForImageClassification.from_hf(image_net)
+        self.is_beit = isinstance(self.image_net, HipBeitForImageClassification)
         self.compute_dtype = compute_dtype or resolve_dtype()
 
-    def encode(self, item_content, drop: DropCfg = NO_DROP):
+    def encode(self, item_content, drop: DropCfg = NO_DROP, interpolate_pos_encoding: bool = False):
         named = [(n, p) for n, p in self.named_parameters()]
         names, params = zip(*named)
         cfg = (names, self.image_net.shape, self.compute_dtype, "image_net.", drop, self.training)
+        if self.is_beit:
+            if interpolate_pos_encoding:
+                raise NotImplementedError("BEiT tower: interpolate_pos_encoding (a bias table resampled to another grid) is not built")
+            check_beit_config(self.image_net.config)
+            return F_.BeitEncoderFn.apply(item_content, cfg, *params)
         return F_.SwinEncoderFn.apply(item_content, cfg, *params)
 
-    def forward(self, item_content):
-        return self.encode(item_content).float()
+    def forward(self, item_content, interpolate_pos_encoding: bool = False):
+        return self.encode(item_content, interpolate_pos_encoding=interpolate_pos_encoding).float()
 
 
 def is_mae_name(name) -> bool:

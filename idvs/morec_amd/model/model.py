@@ -42,10 +42,12 @@ class Model(nn.Module):
         if self.use_modal and self.vision:
             if "swin" in args.CV_model_load:
                 self.cv_encoder = Vit_Encoder(image_net=bert_model, compute_dtype=self.compute_dtype)
-            elif "resnet" not in args.CV_model_load and "beit" not in args.CV_model_load and is_mae_name(args.CV_model_load):
+            elif "beit" in args.CV_model_load:      # V/model/model.py:26-27: the same encoder class over a BEiT classifier
+                self.cv_encoder = Vit_Encoder(image_net=bert_model, compute_dtype=self.compute_dtype, family="beit")
+            elif "resnet" not in args.CV_model_load and is_mae_name(args.CV_model_load):
                 self.cv_encoder = MAE_Encoder(image_net=bert_model, item_dim=args.embedding_dim, compute_dtype=self.compute_dtype)
             else:
-                raise NotImplementedError("only the Swin and MAE towers of V/model/model.py:24-29 are implemented (ResNet / BEiT "
+                raise NotImplementedError("only the Swin, BEiT and MAE towers of V/model/model.py:24-29 are implemented (the ResNet "
                                           "launchers are outside the benchmarked path)")
         elif self.use_modal:
             self.bert_encoder = Bert_Encoder(args=args, bert_model=bert_model)
@@ -75,7 +77,7 @@ class Model(nn.Module):
         d_user = engine.DropCfg(p, p, base ^ 0x5555555555555555) if p > 0 else engine.NO_DROP
         d_item = engine.NO_DROP
         if self.use_modal and self.vision:
-            d_item = engine.DropCfg(0.0, 0.0, base)      # only the DropPath streams (Swin) / the patch-masking noise (MAE) are drawn from it
+            d_item = engine.DropCfg(0.0, 0.0, base)      # only the DropPath streams (Swin, BEiT) / the patch-masking noise (MAE) are drawn from it
         elif self.use_modal:
             c = self.bert_encoder.text_encoders["title"].bert_model.config
             ph, pa = float(getattr(c, "hidden_dropout_prob", 0.0)), float(getattr(c, "attention_probs_dropout_prob", 0.0))

@@ -1109,6 +1109,114 @@ def mae_assemble_bwd(dx, n_img, len_keep, d_cls=None):
     return de, d_cls
 
 
+# ---------------------------------------------------------------------------------------------------------
+# BEiT tower (csrc/beit.hip; attention with a position bias: csrc/attention_stream.hip)
+# ---------------------------------------------------------------------------------------------------------
+def beit_bias_pitch(T: int) -> int:
+    """Row pitch of the expanded position bias [heads, T, Tp]: T rounded up to the key-tile width (include/morec_hip.h)."""
+    return (T + 63) // 64 * 64
+
+
+def beit_relative_position_index(g: int) -> torch.Tensor:
+    """int64 [g*g + 1, g*g + 1]: ``BeitRelativePositionBias.generate_relative_position_index`` on the host -- patch pairs by their 2-D
+    offset, then the entries cls -> token, token -> cls, cls -> cls.  What ``beit_bias_expand`` gathers by."""
+    R = 2 * g - 1
+    nrd = R * R + 3
+    ys, xs = torch.meshgrid(torch.arange(g), torch.arange(g), indexing="ij")
+    ys, xs = ys.reshape(-1), xs.reshape(-1)
+    idx = torch.zeros((g * g + 1, g * g + 1), dtype=torch.int64)
+    idx[1:, 1:] = (ys[:, None] - ys[None, :] + g - 1) * R + (xs[:, None] - xs[None, :] + g - 1)
+    idx[0, :] = nrd - 3
+    idx[:, 0] = nrd - 2
+    idx[0, 0] = nrd - 1
+    return idx
+
+
+def beit_bias_expand(table, g):
+    """``relative_position_bias_table`` fp32 [(2g-1)^2 + 3, heads] -> the position bias of ``attn_bias_fwd``: fp32 [heads, T, Tp]."""
+    _dev(table)
+    heads, T = table.shape[1], g * g + 1
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.shape[0] == (2 * g - 1) ** 2 + 3
+    out = torch.empty((heads, T, beit_bias_pitch(T)), device=table.device, dtype=torch.float32)
+    check(_lib.lib().morec_beit_bias_expand(_p(table), _p(out), g, heads, _stream()), "morec_beit_bias_expand")
+    return out
+
+
+def beit_bias_reduce_(d_pos_bias, dtable, g):
+    """``dtable`` fp32 [(2g-1)^2 + 3, heads] += the sum of the ``d_pos_bias`` cells behind each entry (fixed order)."""
+    assert d_pos_bias.shape == (dtable.shape[1], g * g + 1, beit_bias_pitch(g * g + 1)) and dtable.is_contiguous()
+    check(_lib.lib().morec_beit_bias_reduce(_p(_dev(d_pos_bias)), _p(dtable), g, dtable.shape[1], _stream()), "morec_beit_bias_reduce")
+
+
+def attn_bias_fwd(desc, qkv, key_keep, pos_bias):
+    """``attn_fwd`` with ``+ pos_bias[h, i, j]`` on every score (``pos_bias``: fp32 [heads, T, Tp], ``beit_bias_expand``'s layout)."""
+    _dev(qkv), _dev(key_keep), _dev(pos_bias)
+    assert pos_bias.dtype == torch.float32 and tuple(pos_bias.shape) == (desc.n_heads, desc.T, beit_bias_pitch(desc.T)) and pos_bias.is_contiguous()
+    ctx = torch.empty((qkv.shape[0], qkv.shape[1] // 3), device=qkv.device, dtype=qkv.dtype)
+    check(_lib.lib().morec_attn_bias_fwd(C.byref(desc), _p(qkv), _p(key_keep), _p(pos_bias), _p(ctx), _stream()), "morec_attn_bias_fwd")
+    return ctx
+
+
+def attn_bias_bwd(desc, qkv, key_keep, pos_bias, dctx, dbias=None, need_dpos=True):
+    """(dqkv, d_pos_bias): ``attn_bwd`` of the biased scores.  ``dbias``: fp32 [3 H], accumulated into (column sums of dqkv).
+    ``d_pos_bias`` fp32 [heads, T, Tp] = the sum over the sequences of dS (the gradient at the score), or None with ``need_dpos=False``
+    (a frozen table: no extra launch)."""
+    _dev(dctx), _dev(pos_bias)
+    dqkv = torch.empty_like(qkv)
+    dpos = ws = None
+    nbytes = 0
+    if need_dpos:
+        dpos = torch.empty_like(pos_bias)
+        nbytes = int(_lib.lib().morec_attn_bias_ws_bytes(C.byref(desc)))
+        ws = torch.empty(nbytes // 4, device=qkv.device, dtype=torch.float32)
+    check(_lib.lib().morec_attn_bias_bwd(C.byref(desc), _p(qkv), _p(key_keep), _p(pos_bias), _p(dctx), _p(dqkv), _p(dbias), _p(dpos), _p(ws),
+                                         nbytes, _stream()), "morec_attn_bias_bwd")
+    return dqkv, dpos
+
+
+def layerscale_res_fwd(a, bias, lam, res, rowscale=None, rows_per_scale=0):
+    """``res + rowscale[row / rows_per_scale] * (lam * (a + bias))``: fp32 arithmetic, one rounding."""
+    _dev(a), _dev(res)
+    h = torch.empty_like(a)
+    check(_lib.lib().morec_layerscale_res_fwd(_p(a), _p(bias), _p(lam), _p(res), _p(rowscale), rows_per_scale, _p(h), a.shape[0], a.shape[1],
+                                              code(a.dtype), _stream()), "morec_layerscale_res_fwd")
+    return h
+
+
+def layerscale_res_bwd(dh, a, bias, lam, rowscale=None, rows_per_scale=0, dlam=None, dbias=None):
+    """da = dh * rowscale * lam; ``dlam`` += column sums of dh * rowscale * (a + bias); ``dbias`` += lam * column sums of dh * rowscale
+    (either may be None: frozen)."""
+    _dev(dh)
+    da = torch.empty_like(dh)
+    check(_lib.lib().morec_layerscale_res_bwd(_p(dh), _p(a), _p(bias), _p(lam), _p(rowscale), rows_per_scale, _p(da), _p(dlam), _p(dbias),
+                                              dh.shape[0], dh.shape[1], code(dh.dtype), _stream()), "morec_layerscale_res_bwd")
+    return da
+
+
+def beit_pool_fwd(x, n_img, T):
+    """[n_img, C]: the mean over the patch tokens (rows 1 .. T-1) of every image."""
+    assert x.shape[0] == n_img * T
+    out = torch.empty((n_img, x.shape[1]), device=x.device, dtype=x.dtype)
+    check(_lib.lib().morec_beit_pool_fwd(_p(_dev(x)), _p(out), n_img, T, x.shape[1], code(x.dtype), _stream()), "morec_beit_pool_fwd")
+    return out
+
+
+def beit_pool_bwd(dpool, n_img, T):
+    dx = torch.empty((n_img * T, dpool.shape[1]), device=dpool.device, dtype=dpool.dtype)
+    check(_lib.lib().morec_beit_pool_bwd(_p(_dev(dpool)), _p(dx), n_img, T, dpool.shape[1], code(dpool.dtype), _stream()), "morec_beit_pool_bwd")
+    return dx
+
+
+def beit_assemble_fwd(e, cls_token, n_img):
+    """[n_img * (1 + N), C]: row 0 of an image = cls_token, row 1 + j = e[i * N + j]."""
+    _dev(e), _dev(cls_token)
+    N, C_ = e.shape[0] // n_img, e.shape[1]
+    assert e.shape[0] == n_img * N and cls_token.numel() == C_ and cls_token.dtype == torch.float32
+    x = torch.empty((n_img * (1 + N), C_), device=e.device, dtype=e.dtype)
+    check(_lib.lib().morec_beit_assemble_fwd(_p(e), _p(cls_token), _p(x), n_img, N, C_, code(e.dtype), _stream()), "morec_beit_assemble_fwd")
+    return x
+
+
 def dropout_keep_mask(n, p, seed, device="cuda"):
     out = torch.empty(n, device=device, dtype=torch.uint8)
     check(_lib.lib().morec_dropout_keep_mask(_p(out), n, p, seed, _stream()), "morec_dropout_keep_mask")

@@ -67,8 +67,9 @@ def build_parser():
     p.add_argument("--num_words_body", type=int, default=50)
     p.add_argument("--news_attributes", type=str, default="title")
     # ============== vision variant (V/parameters.py:34-39) ==============
-    p.add_argument("--CV_model_load", type=str, default="None", help="swin_tiny | swin_small | swin_base, or mae_base | mae_large (a name with 'mae' "
-                   "or 'checkpoint': the MAE / ViT tower of V/model/model.py:28) (vision item tower)")
+    p.add_argument("--CV_model_load", type=str, default="None", help="swin_tiny | swin_small | swin_base, mae_base | mae_large (a name with 'mae' "
+                   "or 'checkpoint': the MAE / ViT tower of V/model/model.py:28), or beit_base | beit_large | beit_micro (a name with 'beit': "
+                   "V/model/model.py:26) (vision item tower)")
     p.add_argument("--mae_mask_ratio", type=float, default=None, help="MAE tower: share of the patches masked in a training forward "
                    "(default: the model's, 0.75)")
     p.add_argument("--mae_eval_mask_ratio", type=float, default=None, help="MAE tower: the same in evaluation mode (catalogue passes); default: "
@@ -171,6 +172,30 @@ def check_mae_args(args):
             why = f"--{name} must lie in [0, 1)"
     if why:
         raise SystemExit(f"--CV_model_load {args.CV_model_load} (MAE / ViT item tower): " + why)
+    return True
+
+
+def is_beit_run(args) -> bool:
+    """A run whose item tower is the BEiT tower: a modal tower with a ``--CV_model_load`` the reference routes to ``Vit_Encoder`` over
+    ``BeitForImageClassification`` (``'beit' in CV_model_load``, ``V/model/model.py:26``)."""
+    cv = str(getattr(args, "CV_model_load", "None"))
+    return "modal" in str(args.item_tower) and "beit" in cv and "swin" not in cv
+
+
+def check_beit_args(args):
+    """What the BEiT tower does not run with: exits with the reason (before anything touches a device).  True for a BEiT run."""
+    if not is_beit_run(args):
+        return False
+    why = None
+    if getattr(args, "fused_step", False):
+        why = ("--fused_step" + (" --pool_negatives" if getattr(args, "pool_negatives", False) else "") +
+               ": train_step.TrainStep covers the text, ID and Swin towers; the BEiT tower trains on the drop-in autograd path")
+    elif getattr(args, "graph", False):
+        why = "--graph replays the fused step (train_step.TrainStep), which the BEiT tower does not use"
+    elif getattr(args, "arch", "sasrec") == "dssm":
+        why = "--arch dssm: a vision item tower is not built for DSSM"
+    if why:
+        raise SystemExit(f"--CV_model_load {args.CV_model_load} (BEiT item tower): " + why)
     return True
 
 

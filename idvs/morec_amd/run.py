@@ -38,9 +38,11 @@ from .data_utils.utils import _unwrap
 from .model import BceModel, BertShape, DssmModel, HipBertModel, Model
 from .model.swin import HipSwinForImageClassification
 from .swin_engine import SwinShape
+from .model.beit import HipBeitForImageClassification
 from .model.mae import HipViTMAEModel
+from .beit_engine import BeitShape
 from .mae_engine import MaeShape
-from .parameters import (check_dssm_args, check_fusion_args, check_id_two_stage_args, check_mae_args, check_two_stage_args, is_mae_run,
+from .parameters import (check_beit_args, check_dssm_args, check_fusion_args, check_id_two_stage_args, check_mae_args, check_two_stage_args, is_beit_run, is_mae_run,
                          parse_args)
 from . import engine
 from .train_step import TrainStep
@@ -481,7 +483,13 @@ def build_text_tower(args, freeze=True):
 def build_vision_tower(args):
     """The image network of a vision run, keyed on ``--CV_model_load`` the way ``V/model/model.py:24-29`` is: a Swin classifier
     (``V/run.py:47-54``) or, for a name with 'mae' / 'checkpoint', the ``ViTMAEModel`` container (``--mae_mask_ratio`` /
-    ``--mae_eval_mask_ratio`` override the shape's masking)."""
+    ``--mae_eval_mask_ratio`` override the shape's masking), or, for a name with 'beit', the BEiT classifier container."""
+    if is_beit_run(args):
+        shape = BeitShape.named(args.CV_model_load)
+        if shape.image_size != args.CV_resize:
+            raise SystemExit(f"--CV_model_load {args.CV_model_load}: the BEiT tower takes {shape.image_size} px images (--CV_resize "
+                             f"{args.CV_resize}); interpolate_pos_encoding is not implemented")
+        return HipBeitForImageClassification(shape, args.embedding_dim)      # V/run.py:47-54
     if is_mae_run(args):
         shape = MaeShape.named(args.CV_model_load)
         if getattr(args, "mae_mask_ratio", None) is not None:
@@ -696,8 +704,8 @@ def train(args, use_modal, local_rank):
         bert = build_text_tower(args)
     bce = args.loss == "bce"
     fusion = check_fusion_args(args) if use_modal else None
-    if bce and (args.fused_step or (vision and not is_mae_run(args))):
-        raise SystemExit("--loss bce runs on the drop-in autograd path with the text / ID / MAE towers (bce_text/main-end2end, "
+    if bce and (args.fused_step or (vision and not (is_mae_run(args) or is_beit_run(args)))):
+        raise SystemExit("--loss bce runs on the drop-in autograd path with the text / ID / MAE / BEiT towers (bce_text/main-end2end, "
                          "bce_vision/main-end2end)")
     model = (BceModel(args, item_num, use_modal, bert) if bce else Model(args, item_num, use_modal, bert, pop)).to(local_rank)
     users = list(users_train.keys())
@@ -725,6 +733,8 @@ def train(args, use_modal, local_rank):
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
         if vision and is_mae_run(args):      # V/run.py:121-135 over the reference's own (transformers 4.20.1) MAE names, none of which
             tower = lambda n: "image_net" in n      # holds 'fc' or 'classifier' (the installed names' mlp.fc1 / mlp.fc2 are its *.dense)
+        elif vision and is_beit_run(args):      # the same rule over the reference's (4.20.1) BEiT names: 'classifier' is the only head;
+            tower = lambda n: "image_net" in n and "classifier" not in n      # the installed names' mlp.fc1 / mlp.fc2 are its *.dense
         elif vision:   # V/run.py:121-135
             tower = lambda n: "image_net" in n and not ("fc" in n or "classifier" in n)
         else:        # T/run.py:150-162
@@ -1015,7 +1025,7 @@ def two_stage_features(args, item_content, item_num, vision, local_rank, rank):
     t0 = time.time()
     if vision and is_mae_run(args):
         tower = MAE_Encoder(image_net=build_vision_tower(args), item_dim=args.embedding_dim, compute_dtype=resolve_dtype(args))
-    elif vision:
+    elif vision:      # Swin, or BEiT (the container decides)
         tower = Vit_Encoder(image_net=build_vision_tower(args), compute_dtype=resolve_dtype(args))
     else:
         tower = Bert_Encoder(args=args, bert_model=build_text_tower(args, freeze=False))
@@ -1131,6 +1141,7 @@ def train_two_stage(args, use_modal, local_rank, id_fusion=False):
 def main(argv=None):
     args = parse_args(argv)
     check_mae_args(args)
+    check_beit_args(args)
     two_stage = check_two_stage_args(args)
     id_two_stage = check_id_two_stage_args(args)
     dssm = check_dssm_args(args)

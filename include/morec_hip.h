@@ -445,6 +445,57 @@ int morec_mae_assemble_fwd(const void* e, const float* cls_token, const float* p
 int morec_mae_assemble_bwd(const void* dx, void* de, float* d_cls, int n_img, int len_keep, int C, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The BEiT item tower (HF modeling_beit.py): attention with a per-head additive position bias (csrc/attention_stream.hip, the BIAS
+ * instantiations of the streaming kernels) and the tower's small kernels (csrc/beit.hip).
+ *
+ * morec_attn_bias_fwd / _bwd: morec_attn_fwd / _bwd with
+ *     score = (q.k) * scale + (kept ? 0 : mask_value) + pos_bias[h][i][j]
+ * the mask added in the literal rounding order of the plain kernels, the bias after it in fp32.  The streaming kernels run for EVERY
+ * T <= 1024 (MOREC_ATTN_STREAM is not consulted): stream16 (matrix cores) for bf16 / fp16 with dh % 32 == 0 and dh <= 256, streamgen (fp32
+ * arithmetic) otherwise.  The descriptor is the plain one; causal != 0, p_drop > 0, cu_seqlens != NULL and T > 1024 return
+ * MOREC_E_UNSUPPORTED (no caller uses them), and the descriptor is judged before any pointer.
+ *
+ * pos_bias LAYOUT: fp32 [heads][T][Tp], Tp = 64 * ceil(T / 64): row i of head h holds the bias of query i against the keys 0 .. T-1,
+ * padded with zeros to the key-tile width; the same for every sequence; 16-byte aligned.  morec_beit_bias_expand produces it.  The
+ * cells j >= T are read (in bounds by the layout) but only ever meet a score that is already -inf.
+ *
+ * Backward: dqkv as morec_attn_bwd.  dqkv_bias (fp32 [3 H], may be NULL) += the column sums of dqkv, as morec_attn_bwd_dbias forms them
+ * off the matrix-core path.  d_pos_bias (fp32, pos_bias's layout, may be NULL = frozen table: nothing more is launched) is WRITTEN,
+ * pad cells as zero: d_pos_bias[h][i][j] = sum over the sequences of dS[n, h, i, j], dS = P o (dP - delta) -- the gradient at the score,
+ * `scale` not applied.  It needs ws of morec_attn_bias_ws_bytes(desc) bytes (16-byte aligned; too small or NULL: MOREC_E_ARG): the row
+ * statistics of the main backward ([n_seq][heads][3][T]) and 8 partial tables.  The sequences are cut into 8 chunks of
+ * ceil(n_seq / 8); a workgroup sums one (head, query block, key block) tile over the sequences of its chunk in index order, in fp32
+ * registers, and the chunks are added in chunk order: no atomics, one fixed order, two calls on the same inputs give the same bits.
+ * morec_attn_bias_ws_bytes returns 0 for a descriptor the entry points refuse. */
+size_t morec_attn_bias_ws_bytes(const morec_attn_desc* desc);
+int morec_attn_bias_fwd(const morec_attn_desc* desc, const void* qkv, const float* key_keep, const float* pos_bias, void* ctx, void* stream);
+int morec_attn_bias_bwd(const morec_attn_desc* desc, const void* qkv, const float* key_keep, const float* pos_bias, const void* dctx,
+                        void* dqkv, float* dqkv_bias, float* d_pos_bias, float* ws, size_t ws_bytes, void* stream);
+/* table fp32 [(2g-1)^2 + 3, heads] (relative_position_bias_table; g = patches per side, T = g^2 + 1 <= 1024) -> pos_bias in the layout
+ * above, with BeitRelativePositionBias.generate_relative_position_index: patch pairs by their 2-D offset, then the three entries
+ * cls -> token, token -> cls, cls -> cls.  Reduce: dtable += the sum of the d_pos_bias cells behind each entry; ONE thread owns an entry
+ * and adds its cells in a fixed order. */
+int morec_beit_bias_expand(const float* table, float* pos_bias, int g, int heads, void* stream);
+int morec_beit_bias_reduce(const float* d_pos_bias, float* dtable, int g, int heads, void* stream);
+/* Layer scale fused with the residual add: h[r, c] = res[r, c] + rowscale[r / rows_per_scale] * (lam[c] * (a[r, c] + bias[c])), formed
+ * in fp32 in exactly this order (HF: lambda * output, DropPath, residual) without contraction and rounded once.  rowscale may be NULL;
+ * with it M % rows_per_scale != 0 is MOREC_E_ARG.  N % 8 != 0 or a base pointer off 16 bytes: MOREC_E_ALIGN.
+ * Backward from dh: da = dh * rowscale * lam (storage type); dlam[c] += sum_r dh * rowscale * (a + bias); dbias[c] += lam[c] * sum_r
+ * dh * rowscale.  dlam / dbias may be NULL (frozen: only da is formed; a / bias may then be NULL too).  The column sums run per slab of
+ * 1024 rows in a fixed order and the slabs are added in slab order: no atomics.  Every output is written once. */
+int morec_layerscale_res_fwd(const void* a, const float* bias, const float* lam, const void* res, const float* rowscale, int rows_per_scale,
+                             void* h, long M, int N, int dtype, void* stream);
+int morec_layerscale_res_bwd(const void* dh, const void* a, const float* bias, const float* lam, const float* rowscale, int rows_per_scale,
+                             void* da, float* dlam, float* dbias, long M, int N, int dtype, void* stream);
+/* The mean-pool head: out[n_img, C] = the mean over rows 1 .. T-1 of every image of x[n_img, T, C] ([CLS], row 0, is not part of it);
+ * backward: dx rows 1 .. T-1 = dpool / (T - 1), row 0 = 0. */
+int morec_beit_pool_fwd(const void* x, void* out, int n_img, int T, int C, int dtype, void* stream);
+int morec_beit_pool_bwd(const void* dpool, void* dx, int n_img, int T, int C, int dtype, void* stream);
+/* x[n_img, 1 + N, C]: x[i, 0] = cls_token (fp32 [C], rounded to the storage type), x[i, 1 + j] = e[i * N + j] (row copy; BEiT has no
+ * absolute positions).  The backward is morec_mae_assemble_bwd: the row copy and d_cls = the sum over images of row 0 in index order. */
+int morec_beit_assemble_fwd(const void* e, const float* cls_token, void* x, int n_img, int N, int C, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * BCE variant, one sampled negative per position (bce_text/main-end2end/model/model.py:30-51).
  * E [B, S+1, 2, D] item vectors (pos at [:, :, 0], neg at [:, :, 1]), P [B, S, D] user states, row_valid u8 [B*S].
  * scores fp32 [2][B*S] (pos | neg) are saved for the backward; loss_sum[0] += sum_valid softplus(-pos) + softplus(neg).
