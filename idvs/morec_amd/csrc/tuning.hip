@@ -13,10 +13,11 @@ enum Handling {
     TAIL_BIAS,   // 0..16
     MFMA,        // 0 | 16 | 32; morec_tuning_set refuses anything else, the environment falls back to 0
     AT_LEAST_1,
+    TILE,        // 0 | 128 | 129 | 256 | 1024 | 2128; morec_tuning_set refuses anything else, the environment passes its integer on as given
+    EPI,         // morec_tuning_set: 0 | 1 | 2, anything else refused; environment: 'w...' = 1, anything else = 0
     // environment-only spellings
     NOT_CHAR_0,  // 0 if the variable starts with '0', else 1
     IS_CHAR_1,   // 1 if the variable starts with '1', else 0
-    EPI,         // 'w...' = 1, anything else = 0
 };
 struct Row {
     const char* key;      // morec_tuning_set key, or null: environment only
@@ -46,8 +47,8 @@ const Row ROWS[] = {
     {"deterministic", "MOREC_DETERMINISTIC", &Tuning::deterministic, 0, FLAG},
     {"fold_defer", "MOREC_FOLD_DEFER", &Tuning::fold_defer, 1, FLAG},
     {"attn_stream", "MOREC_ATTN_STREAM", &Tuning::attn_stream, 0, RAW},
-    {nullptr, "MOREC_GEMM_TILE", &Tuning::gemm_tile, 0, RAW},
-    {nullptr, "MOREC_GEMM_EPI", &Tuning::gemm_epi, 2, EPI},
+    {"gemm_tile", "MOREC_GEMM_TILE", &Tuning::gemm_tile, 0, TILE},
+    {"gemm_epi", "MOREC_GEMM_EPI", &Tuning::gemm_epi, 2, EPI},
     {nullptr, "MOREC_GEMM2W_STAGGER", &Tuning::gemm2w_stagger, 0, RAW},
     {nullptr, "MOREC_TN8P_SKIP", &Tuning::tn8p_skip, 1, FLAG},
     {nullptr, "MOREC_ATTN_MFMA64", &Tuning::attn_mfma64, 1, NOT_CHAR_0},
@@ -66,6 +67,16 @@ int handled(Handling how, int v) {
         case MFMA: return (v == 16 || v == 32) ? v : 0;
         case AT_LEAST_1: return v < 1 ? 1 : v;
         default: return v;
+    }
+}
+
+// morec_tuning_set: the kinds that refuse a value instead of mapping it (everything else goes through handled())
+bool accepted(Handling how, int v) {
+    switch (how) {
+        case MFMA: return v == 0 || v == 16 || v == 32;
+        case TILE: return v == 0 || v == 128 || v == 129 || v == 256 || v == 1024 || v == 2128;
+        case EPI: return v >= 0 && v <= 2;
+        default: return true;
     }
 }
 
@@ -92,7 +103,7 @@ extern "C" int morec_tuning_set(const char* key, int value) {
     if (!key) return MOREC_E_ARG;
     for (const Row& r : ROWS)
         if (r.key && !strcmp(key, r.key)) {
-            if (r.how == MFMA && value != 0 && value != 16 && value != 32) return MOREC_E_UNSUPPORTED;
+            if (!accepted(r.how, value)) return MOREC_E_UNSUPPORTED;
             table().*r.field = handled(r.how, value);
             return MOREC_OK;
         }

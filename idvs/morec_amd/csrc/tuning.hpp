@@ -20,9 +20,10 @@ struct Tuning {
     int deterministic;
     int fold_defer;            // deterministic mode: morec_fold_defer_begin opens a scope (0: it does not, every fold launches in place)
     int attn_stream;           // the streaming attention kernels (attention_stream.hip): 0 = for T > 256 only, 1 = never (T > 256 is unsupported), 2 = for every T > 64
+    // the two-buffer GEMMs (gemm_plan rule 6): tuning and test overrides
+    int gemm_tile;             // "gemm_tile" / MOREC_GEMM_TILE: 0 = automatic, 128 / 129 / 256 / 1024 / 2128 = one two-buffer tile shape everywhere
+    int gemm_epi;              // "gemm_epi" / MOREC_GEMM_EPI: 2 = automatic, 1 = per-wave epilogue (w...), 0 = block epilogue (anything else)
     // environment only
-    int gemm_tile;             // MOREC_GEMM_TILE: 0 = automatic, 128 / 129 / 256 / 1024 / 2128 = one two-buffer tile shape everywhere
-    int gemm_epi;              // MOREC_GEMM_EPI: 2 = automatic, 1 = per-wave epilogue (w...), 0 = block epilogue (anything else)
     int gemm2w_stagger;        // MOREC_GEMM2W_STAGGER: first-round stagger experiment of gemm2w, 0 = off
     int tn8p_skip;             // MOREC_TN8P_SKIP=0: never the block-skipping gemm_tn8p variant
     int attn_mfma64;           // MOREC_ATTN_MFMA64=0: the VALU kernels for 32 < T <= 64

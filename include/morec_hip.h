@@ -113,16 +113,21 @@ int morec_version(void);
  *   "attn_stream"        the streaming attention kernels (attention_stream.hip): 0 = for T > 256 only (every T <= 256 call     MOREC_ATTN_STREAM         0
  *                        reaches the kernel it reaches without them) | 1 = never: T > 256 is MOREC_E_UNSUPPORTED | 2 = for every T > 64
  *                        (tests and measurements: the tile edges with small inputs, the strip kernels' range on the matrix cores)
+ *   "gemm_tile"          one tile shape for every two-buffer GEMM (csrc/gemm_plan.hpp, rule 6): 0 automatic |       MOREC_GEMM_TILE           0
+ *                        129 = 128 x 128, 8 waves | 128 = 128 x 128, 4 waves | 1024 = 256 x 256, 16 waves | 256 = 256 x 256, 8 waves |
+ *                        2128 = 256 x 128, 8 waves, 64-byte K stages; other values are refused with MOREC_E_UNSUPPORTED (the environment
+ *                        variable is taken as given).  A tuning and test aid: it does not change which products reach these kernels;
+ *   "gemm_epi"           epilogue form of the two-buffer GEMMs: 0 block staging | 1 per-wave slices | 2 automatic    MOREC_GEMM_EPI            2
+ *                        (wave when N <= 1024 or there is a second output); other values are refused with MOREC_E_UNSUPPORTED.
+ *                        The environment variable spells them w... = 1, anything else = 0, unset = automatic
  * Environment only:
- *   MOREC_GEMM_TILE      one tile shape for every two-buffer GEMM: 128 | 129 | 256 | 1024 | 2128 (csrc/gemm_plan.hpp)          0 = automatic
- *   MOREC_GEMM_EPI       w = per-wave epilogue, anything else = block epilogue, in the two-buffer GEMMs                      unset = automatic
  *   MOREC_GEMM2W_STAGGER first-round stagger experiment of gemm2w                                                           0
  *   MOREC_TN8P_SKIP      0 = never the block-skipping variant of gemm_tn's eight-phase kernel                                1
  *   MOREC_ATTN_MFMA64, MOREC_ATTN_F32_MFMA   0 = the VALU attention kernels for 32 < T <= 64 / for fp32                      1
  *   MOREC_SWIN_WPW_MIN   fewest windows per workgroup of the window-attention backward (>= 1)                                8
  *   MOREC_SWIN_BWD_WIDE  0 = the narrow window-attention backward                                                            1
  *   MOREC_QUIET          1 = no once-per-process notes on stderr                                                             0
- * Returns MOREC_E_UNSUPPORTED for an unknown key or a value "gemm8p_mfma" does not take.  No reference counterpart (the reference has no kernels,
+ * Returns MOREC_E_UNSUPPORTED for an unknown key or a value "gemm8p_mfma", "gemm_tile" or "gemm_epi" does not take.  No reference counterpart (the reference has no kernels,
  * SURVEY.md §2). */
 int morec_tuning_set(const char* key, int value);
 /* Deterministic mode: make the partial-sum scratch of `stream` hold at least n_floats (call outside graph capture; under capture the
