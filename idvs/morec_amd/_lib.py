@@ -37,6 +37,11 @@ class GemmPlanInfo(C.Structure):      # morec_gemm_plan_info
                 ("colsum_fused", C.c_int), ("family_name", C.c_char_p)]
 
 
+class GemmTnPlanInfo(C.Structure):    # morec_gemm_tn_plan_info
+    _fields_ = [("kernel", C.c_int), ("mchunk", C.c_int), ("zs", C.c_int), ("path", C.c_int), ("fold", C.c_int),
+                ("kernel_name", C.c_char_p), ("path_name", C.c_char_p)]
+
+
 class AttnDesc(C.Structure):
     _fields_ = [("n_seq", C.c_int), ("T", C.c_int), ("n_heads", C.c_int), ("dh", C.c_int), ("causal", C.c_int),
                 ("scale", C.c_float), ("mask_value", C.c_float), ("dtype", C.c_int), ("p_drop", C.c_float),
@@ -91,6 +96,7 @@ _SIGS = {
     "morec_gemm_plan": (C.c_int, [C.POINTER(GemmDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GemmPlanInfo)]),
     "morec_gemm_tn": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "morec_gemm_tn_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "morec_gemm_tn_plan": (C.c_int, [C.c_int] * 10 + [C.POINTER(GemmTnPlanInfo)]),
     "morec_mlp_dact_recompute_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "morec_mlp_dact_recompute_workspace_bytes": (C.c_size_t, [C.c_int]),
     "morec_mlp_dact_recompute": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

@@ -12,12 +12,15 @@
 #include "gemm_core.hpp"
 #include "gemm_args.hpp"
 
-int gemm_tn8p_try_launch(const bf16* DY, const bf16* X, float* out, size_t slab_stride, int M, int N, int K, int ldy, int ldx, int ldo,
-                         int mchunk, int zs, int dtype, hipStream_t s);
+#include "gemm_tn_plan.hpp"
+
+int gemm_tn8p_launch(const TnPlan& p, const bf16* DY, const bf16* X, float* out, size_t slab_stride, int M, int N, int K, int ldy, int ldx,
+                     int ldo, int dtype, hipStream_t s);
 
 namespace {
 constexpr int TT = 64;                 // tokens per stage
 constexpr int TC = 256;                // columns per operand tile
+static_assert(TT == tnplan::TT && TC == tnplan::TC, "gemm_tn_plan.hpp");
 constexpr int ROWB = TC * 2;           // 512 bytes per staged row
 constexpr int OPB = TT * ROWB;         // 32 KiB per operand per stage
 constexpr int STAGE = 2 * OPB;
@@ -205,31 +208,23 @@ extern "C" size_t morec_gemm_tn_workspace_bytes(int N, int K, int split_m) {
 // c_dtype = MOREC_BF16: only with slabs (split_m > 1 + workspace) and accumulate == 0 -- the fold writes the rounded sum.
 int gemm_tn_launch(const void* DY, const void* X, void* C, int c_dtype, int M, int N, int K, int ldy, int ldx, int ldc, int dtype, int split_m,
                    int accumulate, float* workspace, void* stream) {
-    if (!DY || !X || !C || M <= 0 || N <= 0 || K <= 0) return MOREC_E_ARG;
-    if (!is_h16(dtype)) return MOREC_E_UNSUPPORTED;   // the exact-fp32 path uses transposed copies + morec_gemm_nt
-    if (c_dtype != MOREC_F32 && c_dtype != dtype) return MOREC_E_DTYPE;
-    if (N % 8 || K % 8 || ldy % 8 || ldx % 8 || ldc % 4 || !aligned16(DY) || !aligned16(X) || !aligned16(C)) return MOREC_E_ALIGN;
-    if (split_m > 1 && !accumulate && !workspace) return MOREC_E_ARG;      // the atomic path needs a caller-zeroed C
+    if (!DY || !X || !C) return MOREC_E_ARG;
+    // every decision -- validation, chunking, kernel, store path -- is gemm_tn_plan's (gemm_tn_plan.hpp); here: pointers and launches
+    const TnPlan p = gemm_tn_plan(M, N, K, ldy, ldx, ldc, dtype, c_dtype, split_m, accumulate, workspace != nullptr,
+                                  aligned16(DY) && aligned16(X) && aligned16(C), aligned16(workspace), tuning());
+    if (p.kernel == TN_UNSUPPORTED) return p.error;
     TnArgs a;
     a.DY = reinterpret_cast<const bf16*>(DY); a.X = reinterpret_cast<const bf16*>(X); a.C = reinterpret_cast<float*>(C);
     a.M = M; a.N = N; a.K = K; a.ldy = ldy; a.ldx = ldx; a.ldc = ldc; a.atomic = accumulate ? 1 : 0;
-    const int split = split_m < 1 ? 1 : split_m;
-    int mchunk = (M + split - 1) / split;
-    mchunk = ((mchunk + TT - 1) / TT) * TT;
-    a.mchunk = mchunk;
-    const int zs = (M + mchunk - 1) / mchunk;
-    a.tiles_n = (N + TC - 1) / TC; a.tiles_k = (K + TC - 1) / TC;
-    a.slabs = (zs > 1 && workspace) ? workspace : nullptr;
-    if (a.slabs && (K % 4 || !aligned16(workspace))) return MOREC_E_ALIGN;
-    if (c_dtype != MOREC_F32 && (!a.slabs || accumulate)) return MOREC_E_UNSUPPORTED;
-    if (zs > 1 && !a.slabs && !accumulate) return MOREC_E_ARG;
-    int r8 = MOREC_E_UNSUPPORTED;      // = not eligible
-    if (a.slabs)                    // split-m partials -> slabs: the eight-phase kernel (gemm_tn8p.hip) when the launch is large enough
-        r8 = gemm_tn8p_try_launch(a.DY, a.X, a.slabs, (size_t)N * K, M, N, K, ldy, ldx, K, mchunk, zs, dtype, reinterpret_cast<hipStream_t>(stream));
-    else if (zs == 1 && !accumulate)
-        r8 = gemm_tn8p_try_launch(a.DY, a.X, a.C, 0, M, N, K, ldy, ldx, ldc, mchunk, 1, dtype, reinterpret_cast<hipStream_t>(stream));
-    if (r8 != MOREC_E_UNSUPPORTED && r8 != MOREC_OK) return r8;
-    if (r8 == MOREC_E_UNSUPPORTED) {
+    a.mchunk = p.mchunk;
+    const int zs = p.zs;
+    a.tiles_n = p.tiles_n; a.tiles_k = p.tiles_k;
+    a.slabs = p.path == TN_PATH_SLABS ? workspace : nullptr;
+    if (p.kernel != TN_TWO_BUFFER) {      // the eight-phase kernel (gemm_tn8p.hip): split-m partials -> slabs, or one chunk that overwrites C
+        const int r8 = a.slabs ? gemm_tn8p_launch(p, a.DY, a.X, a.slabs, (size_t)N * K, M, N, K, ldy, ldx, K, dtype, reinterpret_cast<hipStream_t>(stream))
+                               : gemm_tn8p_launch(p, a.DY, a.X, a.C, 0, M, N, K, ldy, ldx, ldc, dtype, reinterpret_cast<hipStream_t>(stream));
+        if (r8 != MOREC_OK) return r8;
+    } else {
         by_h16(dtype, [&](auto* t) {
             using T = MOREC_TAG_T(t);
             static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TN);   // thread-safe one-time set-up
@@ -258,4 +253,17 @@ int gemm_tn_launch(const void* DY, const void* X, void* C, int c_dtype, int M, i
 extern "C" int morec_gemm_tn(const void* DY, const void* X, float* C, int M, int N, int K, int ldy, int ldx, int ldc,
                              int dtype, int split_m, int accumulate, float* workspace, void* stream) {
     return gemm_tn_launch(DY, X, C, MOREC_F32, M, N, K, ldy, ldx, ldc, dtype, split_m, accumulate, workspace, stream);
+}
+
+// The planner's answer for a call of morec_gemm_tn, without operands and without a device (pointers count as aligned).
+extern "C" int morec_gemm_tn_plan(int M, int N, int K, int ldy, int ldx, int ldc, int dtype, int split_m, int accumulate, int has_workspace,
+                                  morec_gemm_tn_plan_info* out) {
+    if (!out) return MOREC_E_ARG;
+    static const char* const kernels[] = {"unsupported", "two_buffer", "eight_p", "eight_p_skip"};
+    static const char* const paths[] = {"none", "store", "rmw", "atomic", "slabs"};
+    *out = morec_gemm_tn_plan_info{MOREC_TN_UNSUPPORTED, 0, 0, MOREC_TN_PATH_NONE, 0, kernels[0], paths[0]};
+    const TnPlan p = gemm_tn_plan(M, N, K, ldy, ldx, ldc, dtype, MOREC_F32, split_m, accumulate, has_workspace != 0, true, true, tuning());
+    if (p.kernel == TN_UNSUPPORTED) return p.error;
+    *out = morec_gemm_tn_plan_info{p.kernel, p.mchunk, p.zs, p.path, p.fold, kernels[p.kernel], paths[p.path]};
+    return MOREC_OK;
 }

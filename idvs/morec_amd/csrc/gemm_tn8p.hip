@@ -19,7 +19,7 @@
 // Tokens past M must contribute ZERO (they are summed): their lanes carry an out-of-range buffer offset.
 #include "gemm_core.hpp"
 #include "gemm_args.hpp"
-
+#include "gemm_tn_plan.hpp"
 
 namespace {
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
@@ -302,36 +302,24 @@ __global__ __launch_bounds__(THREADS) void gemm_tn8p_kernel(TnArgs8 p) {
 }
 }  // namespace
 
-// Runs the launch on the eight-phase kernel when it is eligible: returns MOREC_OK / a launch error, or MOREC_E_UNSUPPORTED
-// (not eligible: the caller runs the two-buffer kernel, as with morec_attn_mfma_launch).
+static_assert(TT == tnplan::TT, "gemm_tn_plan.hpp");
+
+// Launches what gemm_tn_plan (gemm_tn_plan.hpp) chose -- whether this kernel is eligible, its chunking and the SKIP variant are
+// decided there: returns MOREC_OK / a launch error.
 // `out` = slab workspace ([zs][N][K], fp32) when zs > 1, else C (plain stores: accumulate must be 0).
-int gemm_tn8p_try_launch(const bf16* DY, const bf16* X, float* out, size_t slab_stride, int M, int N, int K, int ldy, int ldx, int ldo,
-                         int mchunk, int zs, int dtype, hipStream_t s) {
-    const int mode = tuning().gemm8p;
-    if (mode == 1) return MOREC_E_UNSUPPORTED;
-    if (N % 8 || K % 8 || ldo % 4) return MOREC_E_UNSUPPORTED;
-    if (mchunk % TT || mchunk < 2 * TT) return MOREC_E_UNSUPPORTED;
-    if (M - (zs - 1) * (long)mchunk < 2 * TT && zs > 1) return MOREC_E_UNSUPPORTED;     // the last chunk needs two stages as well
-    if (zs == 1 && M < 2 * TT) return MOREC_E_UNSUPPORTED;
-    const int tiles_n = (N + 255) / 256, tiles_k = (K + 255) / 256;
-    if (mode != 2) {
-        // automatic: enough work per workgroup.  (No tile-fill rule: on every Swin-T / BERT weight-gradient shape measured --
-        // down to 96 x 96 outputs, 86 % of the tile outside the matrix -- this kernel is at least as fast as the two-buffer one,
-        // which is HBM-bound there as well: profiles/r02_swin_gemm_shapes_modes.txt.)
-        if (mchunk < 8 * TT) return MOREC_E_UNSUPPORTED;
-    }
-    if ((long)M * ldy * 2 >= 0x7fffffffL || (long)M * ldx * 2 >= 0x7fffffffL) return MOREC_E_UNSUPPORTED;   // 32-bit stage offsets
+int gemm_tn8p_launch(const TnPlan& p, const bf16* DY, const bf16* X, float* out, size_t slab_stride, int M, int N, int K, int ldy, int ldx,
+                     int ldo, int dtype, hipStream_t s) {
+    if (p.kernel != TN_EIGHT_P && p.kernel != TN_EIGHT_P_SKIP) return MOREC_E_UNSUPPORTED;
+    const int tiles_n = p.tiles_n, tiles_k = p.tiles_k, zs = p.zs;
     TnArgs8 a;
-    a.DY = DY; a.X = X; a.out = out; a.M = M; a.N = N; a.K = K; a.ldy = ldy; a.ldx = ldx; a.ldo = ldo; a.mchunk = mchunk;
+    a.DY = DY; a.X = X; a.out = out; a.M = M; a.N = N; a.K = K; a.ldy = ldy; a.ldx = ldx; a.ldo = ldo; a.mchunk = p.mchunk;
     a.tiles_n = tiles_n; a.tiles_k = tiles_k; a.zs = zs; a.slab_stride = slab_stride;
     if (!by_h16(dtype, [&](auto* t) {
             using T = MOREC_TAG_T(t);
             static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn8p_kernel<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);   // thread-safe one-time set-up
             static const hipError_t attr_rc2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn8p_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
             (void)attr_rc; (void)attr_rc2;
-            // a 32-wide block row or column of some tile lies outside the matrix: the variant that skips those blocks' MFMAs
-            // (MOREC_TN8P_SKIP=0: never, an A/B aid)
-            if (tuning().tn8p_skip && ((N % 256 != 0 && N % 256 <= 224) || (K % 256 != 0 && K % 256 <= 224)))
+            if (p.kernel == TN_EIGHT_P_SKIP)      // a 32-wide block row or column of some tile lies outside the matrix
                 hipLaunchKernelGGL((gemm_tn8p_kernel<T, true>), dim3(tiles_n * tiles_k * zs), dim3(THREADS), LDS_TOTAL, s, a);
             else
                 hipLaunchKernelGGL((gemm_tn8p_kernel<T, false>), dim3(tiles_n * tiles_k * zs), dim3(THREADS), LDS_TOTAL, s, a);

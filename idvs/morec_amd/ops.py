@@ -302,6 +302,17 @@ def gemm_tn_(dy, x, out, split_m=1, accumulate=True, slabs=True, stream=None):
     return out
 
 
+def gemm_tn_plan(M, N, K, dtype=torch.bfloat16, *, split_m=1, accumulate=True, workspace=True, ldy=None, ldx=None, ldc=None):
+    """What ``morec_gemm_tn`` would launch for these arguments (``morec_gemm_tn_plan``, no device needed): a dict of kernel
+    (``two_buffer`` / ``eight_p`` / ``eight_p_skip``), ``mchunk``, ``zs``, path (``store`` / ``rmw`` / ``atomic`` / ``slabs``) and whether
+    the slab fold follows.  ``workspace``: whether one would be passed (``gemm_tn_`` passes one when ``slabs`` and ``split_m`` > 1).
+    Raises, like the launch, on a refused call."""
+    info = _lib.GemmTnPlanInfo()
+    check(_lib.lib().morec_gemm_tn_plan(M, N, K, ldy or N, ldx or K, ldc or K, code(dtype), split_m, int(accumulate), int(bool(workspace)),
+                                        C.byref(info)), "morec_gemm_tn_plan")
+    return {"kernel": info.kernel_name.decode(), "mchunk": info.mchunk, "zs": info.zs, "path": info.path_name.decode(), "fold": bool(info.fold)}
+
+
 def transpose(x, out=None, out_dtype=None, ld_out=None):
     """[R, C] -> [C, ld_out>=R] (pad columns, if any, are zero)."""
     _dev(x)

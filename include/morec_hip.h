@@ -246,6 +246,36 @@ int morec_gemm_tn(const void* DY, const void* X, float* C, int M, int N, int K, 
 /* workspace (optional, fp32): morec_gemm_tn_workspace_bytes(N, K, split_m).  With it the split-m partial tiles are written
  * as plain slabs and summed by a second kernel (deterministic, ~4x cheaper than the atomics); without it fp32 atomicAdd. */
 size_t morec_gemm_tn_workspace_bytes(int N, int K, int split_m);
+/* What morec_gemm_tn would launch for these arguments, asked of the same function the launch uses (csrc/gemm_tn_plan.hpp) with the knobs
+ * as they stand ("gemm8p", MOREC_TN8P_SKIP).  has_workspace: whether a workspace would be passed; pointers are assumed 16-byte aligned
+ * (the launch checks its own).  Touches no device.  Returns what the launch would return before launching: MOREC_OK, or the MOREC_E_* of a
+ * refused call with kernel MOREC_TN_UNSUPPORTED.
+ *   mchunk = ceil(M / max(split_m, 1)) rounded up to 64 tokens; zs = ceil(M / mchunk) chunks are launched (<= split_m);
+ *   path: store (one chunk, overwrite) | rmw (one chunk, accumulate) | atomic (several chunks, no workspace) | slabs (several chunks,
+ *   workspace: fold != 0, a second kernel sums the slabs into C);
+ *   kernel: the eight-phase kernel takes the store and slabs paths when every chunk, the last too, has at least 128 tokens -- and,
+ *   unless "gemm8p" = 2, mchunk >= 512; "gemm8p" = 1: never.  eight_p_skip: N % 256 or K % 256 in 8 ... 224 (blocks of some tile lie
+ *   outside the matrix and cost no MFMA).
+ * No reference counterpart (the reference has no kernels to select). */
+#define MOREC_TN_UNSUPPORTED 0
+#define MOREC_TN_TWO_BUFFER 1
+#define MOREC_TN_EIGHT_P 2
+#define MOREC_TN_EIGHT_P_SKIP 3
+#define MOREC_TN_PATH_NONE 0
+#define MOREC_TN_PATH_STORE 1
+#define MOREC_TN_PATH_RMW 2
+#define MOREC_TN_PATH_ATOMIC 3
+#define MOREC_TN_PATH_SLABS 4
+typedef struct {
+    int kernel;        /* MOREC_TN_* */
+    int mchunk, zs;
+    int path;          /* MOREC_TN_PATH_* */
+    int fold;          /* the slab fold follows the GEMM */
+    const char* kernel_name; /* "two_buffer", "eight_p", "eight_p_skip", "unsupported" (static storage) */
+    const char* path_name;   /* "store", "rmw", "atomic", "slabs", "none" */
+} morec_gemm_tn_plan_info;
+int morec_gemm_tn_plan(int M, int N, int K, int ldy, int ldx, int ldc, int dtype, int split_m, int accumulate, int has_workspace,
+                       morec_gemm_tn_plan_info* out);
 
 /* out[c, r] = in[r, c]; in is [R, C] with pitch ld_in, out is [C, R] with pitch ld_out.
  * in_dtype/out_dtype select a fused conversion (f32 -> bf16 weight shadows). */
