@@ -6,7 +6,8 @@
 #include "common.hpp"
 #include "pos_grad.hpp"
 
-template <typename T, int VPL>
+// PID: the position row of token `row` is pos_ids[row] (the pad-relative rule, morec_roberta_pos_ids) instead of row % Tlen.
+template <typename T, int VPL, bool PID = false>
 __global__ __launch_bounds__(256) void bert_embed_fwd_kernel(const int32_t* __restrict__ ids,
                                                              const float* __restrict__ word,
                                                              const float* __restrict__ pos,
@@ -15,7 +16,8 @@ __global__ __launch_bounds__(256) void bert_embed_fwd_kernel(const int32_t* __re
                                                              const float* __restrict__ beta, float eps,
                                                              T* __restrict__ z_out, T* __restrict__ y,
                                                              float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                             int M, int Tlen, int H, DropRng dout) {
+                                                             int M, int Tlen, int H, DropRng dout,
+                                                             const int32_t* __restrict__ pos_ids = nullptr) {
     dout = drop_resolve(dout);
     constexpr int EV = vio<T>::EV;
     const int lane = threadIdx.x & 63;
@@ -23,7 +25,7 @@ __global__ __launch_bounds__(256) void bert_embed_fwd_kernel(const int32_t* __re
     if (row >= M) return;
     const size_t base = (size_t)row * H;
     const float* w = word + (size_t)ids[row] * H;
-    const float* p = pos + (size_t)(row % Tlen) * H;
+    const float* p = pos + (size_t)(PID ? pos_ids[row] : row % Tlen) * H;
     float v[VPL][EV];
     float sum = 0.f;
 #pragma unroll
@@ -89,21 +91,23 @@ __global__ __launch_bounds__(256) void bert_embed_fwd_kernel(const int32_t* __re
     }
 }
 
-extern "C" int morec_bert_embed_fwd(const int32_t* ids, const float* word, const float* pos, const float* type0,
-                                    const float* gamma, const float* beta, float eps, void* z_out, void* y,
-                                    float* mean, float* rstd, int M, int T, int H, int dtype, float p_out,
-                                    uint64_t seed_out, void* stream) {
+template <bool PID>
+static int bert_embed_fwd_launch(const int32_t* ids, const int32_t* pos_ids, const float* word, const float* pos, const float* type0,
+                                 const float* gamma, const float* beta, float eps, void* z_out, void* y,
+                                 float* mean, float* rstd, int M, int T, int H, int dtype, float p_out,
+                                 uint64_t seed_out, void* stream) {
     if (p_out < 0.f || p_out >= 1.f) return MOREC_E_ARG;
     const DropRng dout = make_drop(p_out, seed_out);
     if (!ids || !word || !pos || !type0 || !gamma || !beta || !y || M <= 0 || T <= 0 || H <= 0) return MOREC_E_ARG;
+    if (PID && !pos_ids) return MOREC_E_ARG;
     const int ev = dtype == MOREC_F32 ? 4 : 8;
     if (H % ev) return MOREC_E_ALIGN;
     const int vpl = (H + 64 * ev - 1) / (64 * ev);
     dim3 grid((M + 3) / 4), block(256);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
 #define EMB(TT, V)                                                                                                  \
-    hipLaunchKernelGGL((bert_embed_fwd_kernel<TT, V>), grid, block, 0, s, ids, word, pos, type0, gamma, beta, eps, \
-                       (TT*)z_out, (TT*)y, mean, rstd, M, T, H, dout)
+    hipLaunchKernelGGL((bert_embed_fwd_kernel<TT, V, PID>), grid, block, 0, s, ids, word, pos, type0, gamma, beta, eps, \
+                       (TT*)z_out, (TT*)y, mean, rstd, M, T, H, dout, pos_ids)
 #define EMB_DISPATCH(TT)                      \
     do {                                      \
         if (vpl <= 1) EMB(TT, 1);             \
@@ -119,6 +123,66 @@ extern "C" int morec_bert_embed_fwd(const int32_t* ids, const float* word, const
     else return MOREC_E_DTYPE;
 #undef EMB
 #undef EMB_DISPATCH
+    MOREC_CHECK_LAUNCH();
+    return MOREC_OK;
+}
+
+extern "C" int morec_bert_embed_fwd(const int32_t* ids, const float* word, const float* pos, const float* type0,
+                                    const float* gamma, const float* beta, float eps, void* z_out, void* y,
+                                    float* mean, float* rstd, int M, int T, int H, int dtype, float p_out,
+                                    uint64_t seed_out, void* stream) {
+    return bert_embed_fwd_launch<false>(ids, nullptr, word, pos, type0, gamma, beta, eps, z_out, y, mean, rstd, M, T, H, dtype, p_out,
+                                        seed_out, stream);
+}
+
+extern "C" int morec_bert_embed_fwd_pos(const int32_t* ids, const int32_t* pos_ids, const float* word, const float* pos,
+                                        const float* type0, const float* gamma, const float* beta, float eps, void* z_out, void* y,
+                                        float* mean, float* rstd, int M, int T, int H, int dtype, float p_out,
+                                        uint64_t seed_out, void* stream) {
+    return bert_embed_fwd_launch<true>(ids, pos_ids, word, pos, type0, gamma, beta, eps, z_out, y, mean, rstd, M, T, H, dtype, p_out,
+                                       seed_out, stream);
+}
+
+// Pad-relative position ids (HF create_position_ids_from_input_ids): the k-th non-pad token of a sequence (k from 0) has id
+// pad + 1 + k, a pad token has id pad.  One wave per sequence: T is walked 64 lanes at a time, each trip a ballot of id != pad, the
+// popcount of the lanes below and a running base -- once to count the sequence's non-pad tokens (the pad slots of `perm` start
+// there), once to write.  perm[n*T + k] = position of the k-th non-pad token for k < cnt[n], then the pad positions in order.
+__global__ __launch_bounds__(256) void roberta_pos_ids_kernel(const int32_t* __restrict__ ids, int pad_id, int n_seq, int Tlen,
+                                                              int32_t* __restrict__ pos_ids, int32_t* __restrict__ perm,
+                                                              int32_t* __restrict__ cnt) {
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (n >= n_seq) return;      // (wave-uniform)
+    const int32_t* row = ids + (size_t)n * Tlen;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int total = 0;
+    for (int t0 = 0; t0 < Tlen; t0 += 64) {
+        const int t = t0 + lane;
+        total += __popcll(__ballot(t < Tlen && row[t] != pad_id));
+    }
+    int base = 0;
+    for (int t0 = 0; t0 < Tlen; t0 += 64) {
+        const int t = t0 + lane;
+        const bool in = t < Tlen;
+        const bool real = in && row[t] != pad_id;
+        const unsigned long long m = __ballot(real);
+        const int k = base + __popcll(m & below);      // non-pad tokens in front of position t
+        if (in) {
+            pos_ids[(size_t)n * Tlen + t] = real ? pad_id + 1 + k : pad_id;
+            perm[(size_t)n * Tlen + (real ? k : total + (t - k))] = t;
+        }
+        base += __popcll(m);
+    }
+    if (lane == 0) cnt[n] = total;
+}
+
+extern "C" int morec_roberta_pos_ids(const int32_t* ids, int pad_id, int n_seq, int T, int n_pos, int32_t* pos_ids_out,
+                                     int32_t* perm_out, int32_t* cnt_out, void* stream) {
+    if (!ids || !pos_ids_out || !perm_out || !cnt_out || n_seq <= 0 || T <= 0 || pad_id < 0) return MOREC_E_ARG;
+    if ((long long)pad_id + T >= (long long)n_pos) return MOREC_E_ARG;      // the largest id written is pad_id + T: it must be a table row
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(roberta_pos_ids_kernel, dim3((n_seq + 3) / 4), dim3(256), 0, s, ids, pad_id, n_seq, T, pos_ids_out, perm_out,
+                       cnt_out);
     MOREC_CHECK_LAUNCH();
     return MOREC_OK;
 }
@@ -339,10 +403,10 @@ __global__ __launch_bounds__(256) void pos_type_grad_scalar_kernel(const T* __re
     }
 }
 
-extern "C" int morec_bert_embed_bwd(const int32_t* ids, const void* dz, float* dword, float* dpos, float* dtype0,
-                                    int pad_id, int M, int T, int H, int dtype, const int32_t* order, void* stream) {
-    if (!ids || !dz || !dword || !dpos || M <= 0 || T <= 0 || H <= 0 || M % T) return MOREC_E_ARG;
-    if (H % 4) return MOREC_E_ALIGN;
+// perm != nullptr: the pad-relative position rule (morec_roberta_embed_bwd) -- dpos then points at the row of slot 0
+static int bert_embed_bwd_launch(const int32_t* ids, const void* dz, float* dword, float* dpos, float* dtype0,
+                                 int pad_id, int M, int T, int H, int dtype, const int32_t* order, const int32_t* perm,
+                                 const int32_t* cnt, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int spb = 64;
     dim3 g1((M + 3) / 4), g2(T, (M / T + spb - 1) / spb);
@@ -372,13 +436,33 @@ extern "C" int morec_bert_embed_bwd(const int32_t* ids, const void* dz, float* d
                 if (part) hipLaunchKernelGGL((word_scatter_fold_kernel<4>), g3, dim3(256), 0, s, ids, order, (const float*)part, dword, pad_id, M, H, rpw);
             }
             else hipLaunchKernelGGL((word_scatter_kernel<T>), g1, dim3(256), 0, s, ids, (const T*)dz, dword, pad_id, M, H);
-            if (vec) rc_pos = pos_type_grad_launch<T>((const T*)dz, dpos, dtype0, M / T_, T_, H, s);
+            if (perm) rc_pos = pos_type_grad_launch<T, true>((const T*)dz, dpos, dtype0, M / T_, T_, H, s, perm, cnt);
+            else if (vec) rc_pos = pos_type_grad_launch<T>((const T*)dz, dpos, dtype0, M / T_, T_, H, s);
             else hipLaunchKernelGGL((pos_type_grad_scalar_kernel<T>), g2, dim3(256), 0, s, (const T*)dz, dpos, dtype0, M / T_, T_, H, spb);
         }))
         return MOREC_E_DTYPE;
     if (rc_pos < 0) return (int)hipErrorOutOfMemory;      // deterministic scratch unavailable (e.g. it would have to grow under graph capture)
     MOREC_CHECK_LAUNCH();
     return MOREC_OK;
+}
+
+extern "C" int morec_bert_embed_bwd(const int32_t* ids, const void* dz, float* dword, float* dpos, float* dtype0,
+                                    int pad_id, int M, int T, int H, int dtype, const int32_t* order, void* stream) {
+    if (!ids || !dz || !dword || !dpos || M <= 0 || T <= 0 || H <= 0 || M % T) return MOREC_E_ARG;
+    if (H % 4) return MOREC_E_ALIGN;
+    return bert_embed_bwd_launch(ids, dz, dword, dpos, dtype0, pad_id, M, T, H, dtype, order, nullptr, nullptr, stream);
+}
+
+extern "C" int morec_roberta_embed_bwd(const int32_t* ids, const void* dz, float* dword, float* dpos, float* dtype0,
+                                       int pad_id, int M, int T, int H, int dtype, const int32_t* order, const int32_t* perm,
+                                       const int32_t* cnt, int pos_pad, int n_pos, void* stream) {
+    if (!ids || !dz || !dword || !dpos || !perm || !cnt || M <= 0 || T <= 0 || H <= 0 || M % T) return MOREC_E_ARG;
+    if (pos_pad < 0 || (long long)pos_pad + T >= (long long)n_pos) return MOREC_E_ARG;      // slots write rows pos_pad + 1 .. pos_pad + T
+    if (dtype != MOREC_F32 && dtype != MOREC_BF16 && dtype != MOREC_F16) return MOREC_E_DTYPE;
+    const int ev = dtype == MOREC_F32 ? 4 : 8;
+    if (H % ev || H / ev > 256) return MOREC_E_UNSUPPORTED;      // the vector layout only: no scalar kernel for this rule
+    return bert_embed_bwd_launch(ids, dz, dword, dpos + (size_t)(pos_pad + 1) * H, dtype0, pad_id, M, T, H, dtype, order, perm, cnt,
+                                 stream);
 }
 
 template <typename T>

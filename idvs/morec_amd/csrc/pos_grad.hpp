@@ -9,10 +9,16 @@
 // sum stays in registers over all positions: one atomic per column per block).  The first version read two bytes per lane per
 // dependent trip and sent every block's type-row sums to the same H addresses: 118 us for 124 MB.  Few sequences (the recommender's
 // [B, S] rows): the positions are spread over blockIdx.y so that the launch still has a few hundred blocks.
-template <typename T>
+//
+// PERM (the pad-relative position rule, morec_roberta_embed_bwd): slot k of sequence n reads row n*T + perm[n*T + k] instead of row
+// n*T + k, and enters the slot's sum only while k < cnt[n] (the sequence's non-pad tokens, in order); the type-row sum takes every row
+// (perm is a permutation of the sequence's positions).  The slot indices of the next two fetches are read one position ahead of the
+// rows they address, so the perm -> row chain is not on the walk's critical path.
+template <typename T, bool PERM = false>
 __global__ __launch_bounds__(256) void pos_type_grad_kernel(const T* __restrict__ dz, float* __restrict__ dpos,
                                                             float* __restrict__ dtype0, int nseq, int Tlen, int H,
-                                                            int t_per_block, int det = 0) {
+                                                            int t_per_block, int det = 0, const int32_t* __restrict__ perm = nullptr,
+                                                            const int32_t* __restrict__ cnt = nullptr) {
     constexpr int EV = vio<T>::EV, R = 4;
     extern __shared__ __attribute__((aligned(16))) float sm_pt[];      // [groups][H]
     const int nv = H / EV;                                   // <= 256, H % EV == 0 (launcher)
@@ -27,9 +33,25 @@ __global__ __launch_bounds__(256) void pos_type_grad_kernel(const T* __restrict_
     const size_t ustride = (size_t)groups * Tlen * H;
     const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
     uint4 ra[R], rb[R];
+    // PERM: pn[u] = the row-in-sequence of the NEXT fetch (slots are fetched in order t0, t0 + 1, ...), cn[u] = the sequence's non-pad count
+    int pn[R], cn[R];
+    const int32_t* pbase = nullptr;
+    if constexpr (PERM) {
+        pbase = perm + (size_t)(n_ok ? s0 + grp : 0) * Tlen;
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            pn[u] = (u < n_ok && t0 < t1) ? pbase[(size_t)u * groups * Tlen + t0] : 0;
+            cn[u] = u < n_ok ? cnt[s0 + grp + u * groups] : 0;
+        }
+    }
 #define PT_FETCH(r, t)                                                                                              \
-    _Pragma("unroll") for (int u = 0; u < R; ++u)                                                                    \
-        r[u] = (u < n_ok && (t) < t1) ? vio<T>::load_raw(base + u * ustride + (size_t)(t) * H) : zero4
+    _Pragma("unroll") for (int u = 0; u < R; ++u) {                                                                  \
+        if constexpr (PERM) {                                                                                        \
+            r[u] = (u < n_ok && (t) < t1) ? vio<T>::load_raw(base + u * ustride + (size_t)pn[u] * H) : zero4;        \
+            pn[u] = (u < n_ok && (t) + 1 < t1) ? pbase[(size_t)u * groups * Tlen + (t) + 1] : 0;                     \
+        } else                                                                                                       \
+            r[u] = (u < n_ok && (t) < t1) ? vio<T>::load_raw(base + u * ustride + (size_t)(t) * H) : zero4;          \
+    }
     float ty[EV];
 #pragma unroll
     for (int k = 0; k < EV; ++k) ty[k] = 0.f;
@@ -52,10 +74,20 @@ __global__ __launch_bounds__(256) void pos_type_grad_kernel(const T* __restrict_
         _Pragma("unroll") for (int u = 0; u < R; ++u) {                                       \
             float e[EV];                                                                      \
             vio<T>::unpack(r[u], e);                                                          \
-            _Pragma("unroll") for (int k = 0; k < EV; ++k) acc[k] += e[k];                    \
+            if constexpr (PERM) {                                                             \
+                const bool real = (t) < cn[u];                                                \
+                _Pragma("unroll") for (int k = 0; k < EV; ++k) {                              \
+                    ty[k] += e[k];                                                            \
+                    acc[k] += real ? e[k] : 0.f;                                              \
+                }                                                                             \
+            } else {                                                                          \
+                _Pragma("unroll") for (int k = 0; k < EV; ++k) acc[k] += e[k];                \
+            }                                                                                 \
         }                                                                                     \
         PT_FETCH(r, (t) + 2);                                                                 \
-        _Pragma("unroll") for (int k = 0; k < EV; ++k) ty[k] += acc[k];                       \
+        if constexpr (!PERM) {                                                                \
+            _Pragma("unroll") for (int k = 0; k < EV; ++k) ty[k] += acc[k];                   \
+        }                                                                                     \
         fold(acc, dpos + ((size_t)(det ? blockIdx.x * Tlen : 0) + (t)) * H);                  \
     }
     PT_FETCH(ra, t0);
@@ -71,8 +103,10 @@ __global__ __launch_bounds__(256) void pos_type_grad_kernel(const T* __restrict_
 
 // 0: the row width does not fit the one-vector-per-thread layout (the callers keep a scalar kernel for that); 1: launched; -1: the
 // deterministic mode's scratch is not available (callers return an error: never a silent fall-back to the atomic kernel)
-template <typename T>
-inline int pos_type_grad_launch(const T* dz, float* dpos, float* dtype0, int nseq, int Tlen, int H, hipStream_t s) {
+// PERM: dpos points at the row of slot 0 (position row pos_pad + 1); perm / cnt as morec_roberta_pos_ids writes them.
+template <typename T, bool PERM = false>
+inline int pos_type_grad_launch(const T* dz, float* dpos, float* dtype0, int nseq, int Tlen, int H, hipStream_t s,
+                                const int32_t* perm = nullptr, const int32_t* cnt = nullptr) {
     constexpr int EV = vio<T>::EV;
     if (H % EV || H / EV > 256) return 0;
     const int grp = 256 / (H / EV);
@@ -85,13 +119,13 @@ inline int pos_type_grad_launch(const T* dz, float* dpos, float* dtype0, int nse
         const size_t n_pos = (size_t)seq_blocks * Tlen * H, n_ty = dtype0 ? (size_t)seq_blocks * ty_blocks * H : 0;
         float* part = morec_det_scratch(s, n_pos + n_ty);
         if (!part) return -1;
-        hipLaunchKernelGGL((pos_type_grad_kernel<T>), dim3(seq_blocks, ty_blocks), dim3(256), (size_t)grp * H * sizeof(float), s, dz,
-                           part, dtype0 ? part + n_pos : nullptr, nseq, Tlen, H, tpb, 1);
+        hipLaunchKernelGGL((pos_type_grad_kernel<T, PERM>), dim3(seq_blocks, ty_blocks), dim3(256), (size_t)grp * H * sizeof(float), s, dz,
+                           part, dtype0 ? part + n_pos : nullptr, nseq, Tlen, H, tpb, 1, perm, cnt);
         (void)morec_det_fold_add(part, dpos, seq_blocks, (size_t)Tlen * H, (size_t)Tlen * H, s);
         if (dtype0) (void)morec_det_fold_add(part + n_pos, dtype0, seq_blocks * ty_blocks, (size_t)H, (size_t)H, s);
         return 1;
     }
-    hipLaunchKernelGGL((pos_type_grad_kernel<T>), dim3(seq_blocks, ty_blocks), dim3(256), (size_t)grp * H * sizeof(float), s, dz,
-                       dpos, dtype0, nseq, Tlen, H, tpb);
+    hipLaunchKernelGGL((pos_type_grad_kernel<T, PERM>), dim3(seq_blocks, ty_blocks), dim3(256), (size_t)grp * H * sizeof(float), s, dz,
+                       dpos, dtype0, nseq, Tlen, H, tpb, 0, perm, cnt);
     return 1;
 }

@@ -31,7 +31,7 @@ def _text_features_fn(enc: Bert_Encoder):
         for name in enc.newsname:      # one pass of the shared encoder per attribute, averaged (model/encoders.py:127-137)
             text = torch.narrow(news, 1, enc.attributes2start[name], enc.attributes2length[name]).contiguous()
             cls, _ = engine.bert_forward(p, prep, text, c.num_attention_heads, te.compute_dtype, False, c.layer_norm_eps, te.mask_value, "",
-                                         res32=te.res32, features_only=True)
+                                         res32=te.res32, features_only=True, **engine.bert_position_rule(c))
             vecs.append(cls.float())
         return vecs[0] if len(vecs) == 1 else torch.mean(torch.stack(vecs, dim=1), dim=1)
     return run

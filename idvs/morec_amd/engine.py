@@ -528,12 +528,25 @@ def bert_needs_grad_buffer(name: str, grad_from: int, prefix: str = TE) -> bool:
     return True
 
 
+def bert_position_rule(config) -> dict:
+    """The ``position_rule`` / ``pad_id`` keywords of ``bert_forward`` for a tower's ``config`` (``HipBertModel.config`` or a HuggingFace
+    one): RoBERTa counts its position rows from the pad token id, BERT from 0."""
+    rule = getattr(config, "position_rule", None)
+    if rule is None:
+        rule = "pad_relative" if getattr(config, "model_type", "bert") == "roberta" else "absolute"
+    return dict(position_rule=rule, pad_id=int(config.pad_token_id) if rule == "pad_relative" else 0)
+
+
 def bert_forward(p: dict, prep, text: torch.Tensor, heads: int, dtype, need_grad: bool, eps: float = 1e-12,
                  mask_value: float = ops.FLT_MIN_MASK, prefix: str = TE, drop: DropCfg = NO_DROP, unpad: bool | None = None,
-                 grad_from: int = -1, packing=None, on_use=None, res32: bool = False, features_only: bool = False):
+                 grad_from: int = -1, packing=None, on_use=None, res32: bool = False, features_only: bool = False,
+                 position_rule: str = "absolute", pad_id: int = 0):
     """text int64 [Nc, 2T] = [input_ids | attention_mask] (T/model/encoders.py:63-67) -> item vectors [Nc, D].
     ``features_only``: return ``(cls [Nc, H], None)``, the [CLS] rows in front of ``fc`` -- what the two-stage packages' ``Text_Encoder``
     returns (stage 1 of two-stage training, ``data_utils.two_stage``).
+    ``position_rule="pad_relative"`` (RoBERTa, with ``pad_id`` the tower's pad token): the k-th token of a title that is not ``pad_id``
+    reads position row ``pad_id + 1 + k``, a ``pad_id`` token row ``pad_id`` (HF ``create_position_ids_from_input_ids``: from the ids
+    alone, whatever the attention mask says); the ids are computed here, once per call, in the padded layout.
 
     ``unpad``: run the encoder layers on the REAL tokens only (packed rows + ``cu_seqlens``) instead of all T positions of
     every title.  Exact for what the path consumes (``hidden[:, 0]``, encoders.py:69): [PAD] keys carry the additive
@@ -557,10 +570,21 @@ def bert_forward(p: dict, prep, text: torch.Tensor, heads: int, dtype, need_grad
     type0 = p[bm + "embeddings.token_type_embeddings.weight"][0].contiguous()
     # (res32: the embedding stage runs in fp32 -- embeddings and their LayerNorm are not autocast operators -- and the first GEMM's operand
     # is its rounded copy)
-    x, z_e, mean_e, rstd_e = ops.bert_embed_fwd(ids32, p[bm + "embeddings.word_embeddings.weight"],
-                                                p[bm + "embeddings.position_embeddings.weight"], type0,
-                                                p[bm + "embeddings.LayerNorm.weight"], p[bm + "embeddings.LayerNorm.bias"],
-                                                eps, T, torch.float32 if res32 else dtype, p_out=drop.p_hidden, seed_out=drop.site(0))
+    pos_rule = None      # pad-relative rule: (perm, cnt, pad_id), what the backward's position scatter walks
+    if position_rule == "pad_relative":
+        pos_w = p[bm + "embeddings.position_embeddings.weight"]
+        pos_ids, perm, cnt = ops.roberta_pos_ids(ids32, pad_id, T, pos_w.shape[0])
+        pos_rule = (perm, cnt, pad_id)
+        x, z_e, mean_e, rstd_e = ops.bert_embed_fwd_pos(ids32, pos_ids, p[bm + "embeddings.word_embeddings.weight"], pos_w, type0,
+                                                        p[bm + "embeddings.LayerNorm.weight"], p[bm + "embeddings.LayerNorm.bias"],
+                                                        eps, T, torch.float32 if res32 else dtype, p_out=drop.p_hidden, seed_out=drop.site(0))
+    elif position_rule != "absolute":
+        raise ValueError(f"unknown position_rule {position_rule!r}")
+    else:
+        x, z_e, mean_e, rstd_e = ops.bert_embed_fwd(ids32, p[bm + "embeddings.word_embeddings.weight"],
+                                                    p[bm + "embeddings.position_embeddings.weight"], type0,
+                                                    p[bm + "embeddings.LayerNorm.weight"], p[bm + "embeddings.LayerNorm.bias"],
+                                                    eps, T, torch.float32 if res32 else dtype, p_out=drop.p_hidden, seed_out=drop.site(0))
     xr = None
     if res32:
         xr, x = x, ops.cast(x, dtype)
@@ -612,16 +636,16 @@ def bert_forward(p: dict, prep, text: torch.Tensor, heads: int, dtype, need_grad
     D = prep["fc"].w.shape[0]
     pre = torch.empty((Nc, D), device=cls.device, dtype=dtype) if need_grad else None
     item = ops.gemm_nt(cls, prep["fc"].w, bias=p[prefix + "fc.bias"], act=ACT_GELU, aux_out=pre)
-    saved = (cfg, ids32, z_e, mean_e, rstd_e, saved_layers, cls, pre, Nc, T, H, drop, tok_idx, grad_from, order, inv) if need_grad else None
+    saved = (cfg, ids32, z_e, mean_e, rstd_e, saved_layers, cls, pre, Nc, T, H, drop, tok_idx, grad_from, order, inv, pos_rule) if need_grad else None
     return item, saved
 
 
 def bert_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefix: str = TE, pad_id: int = 0, on_ready=None):
     """``on_ready(key)`` (optional) is called as soon as a set of gradients is final -- ``"head"`` once everything outside
     ``bert_model`` is, ``("layer", l)`` after layer ``l`` -- so a data-parallel driver can start reducing them while the
-    rest of the backward pass still runs."""
+    rest of the backward pass still runs.  A forward under the pad-relative position rule carries its own pad id (``pad_id`` is BERT's)."""
     bm = prefix + "bert_model."
-    cfg, ids32, z_e, mean_e, rstd_e, saved_layers, cls, pre, Nc, T, H, drop, tok_idx, grad_from, order, inv = saved
+    cfg, ids32, z_e, mean_e, rstd_e, saved_layers, cls, pre, Nc, T, H, drop, tok_idx, grad_from, order, inv, pos_rule = saved
     n_layers = len(prep["layers"])
     dv = ops.act_bwd(d_item.contiguous(), pre, ACT_GELU)
     ops.colsum_(dv, grads[prefix + "fc.bias"])
@@ -680,6 +704,12 @@ def bert_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefi
                                 p_out=drop.p_hidden, seed_out=drop.site(0), sub16=False)
     if order is None:      # integer bookkeeping: rows in token-id order for the run-length scatter (the collate can supply it: token_packing_host)
         order = torch.argsort(ids32, stable=ops.DETERMINISTIC).to(torch.int32)      # (stable: the fixed summation order of word_scatter_runs_kernel)
+    if pos_rule is not None:
+        perm, cnt, rpad = pos_rule
+        ops.roberta_embed_bwd_(ids32, dz_e, grads[bm + "embeddings.word_embeddings.weight"],
+                               grads[bm + "embeddings.position_embeddings.weight"],
+                               grads[bm + "embeddings.token_type_embeddings.weight"][0], rpad, T, perm, cnt, rpad, order)
+        return
     ops.bert_embed_bwd_(ids32, dz_e, grads[bm + "embeddings.word_embeddings.weight"],
                         grads[bm + "embeddings.position_embeddings.weight"],
                         grads[bm + "embeddings.token_type_embeddings.weight"][0], pad_id, T, order)

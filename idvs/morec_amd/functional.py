@@ -56,12 +56,14 @@ class BertEncoderFn(torch.autograd.Function):
     def forward(ctx, text, cfg, *params):
         names, heads, n_layers, dtype, prefix, eps, mask_value, drop = cfg[:8]
         res32 = bool(cfg[8]) if len(cfg) > 8 else False
+        pos_kw = dict(cfg[9]) if len(cfg) > 9 else {}      # position_rule / pad_id (``engine.bert_position_rule``); BERT's when absent
         p = dict(zip(names, params))
         need = any(ctx.needs_input_grad)
         prep = engine.bert_prepare(p, n_layers, dtype, prefix)
         # the backward stops at the lowest trainable point of the tower (T/run.py:73-75 freezes a prefix by parameter index)
         grad_from = engine.bert_grad_from([n for n, nd in zip(names, ctx.needs_input_grad[2:]) if nd], n_layers, prefix)
-        item, saved = engine.bert_forward(p, prep, text, heads, dtype, need, eps, mask_value, prefix, drop, grad_from=grad_from, res32=res32)
+        item, saved = engine.bert_forward(p, prep, text, heads, dtype, need, eps, mask_value, prefix, drop, grad_from=grad_from, res32=res32,
+                                          **pos_kw)
         ctx.stuff = (p, prep, saved, names, prefix, grad_from)
         ctx.needs = ctx.needs_input_grad
         ctx.fp32_gemm = ops.FP32_GEMM

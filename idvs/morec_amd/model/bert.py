@@ -54,6 +54,12 @@ class _Encoder(nn.Module):
 class _Embeddings(nn.Module):
     def __init__(self, c: BertShape):
         super().__init__()
+        if c.position_rule == "pad_relative":      # HF RobertaEmbeddings: the position table is registered last, both tables have padding_idx
+            self.word_embeddings = nn.Embedding(c.vocab_size, c.hidden_size, padding_idx=c.pad_token_id)
+            self.token_type_embeddings = nn.Embedding(c.type_vocab_size, c.hidden_size)
+            self.LayerNorm = nn.LayerNorm(c.hidden_size, eps=c.layer_norm_eps)
+            self.position_embeddings = nn.Embedding(c.max_position_embeddings, c.hidden_size, padding_idx=c.pad_token_id)
+            return
         self.word_embeddings = nn.Embedding(c.vocab_size, c.hidden_size, padding_idx=0)
         self.position_embeddings = nn.Embedding(c.max_position_embeddings, c.hidden_size)
         self.token_type_embeddings = nn.Embedding(c.type_vocab_size, c.hidden_size)
@@ -77,7 +83,8 @@ class HipBertModel(nn.Module):
                                             num_attention_heads=shape.num_attention_heads,
                                             intermediate_size=shape.intermediate_size, vocab_size=shape.vocab_size,
                                             max_position_embeddings=shape.max_position_embeddings,
-                                            layer_norm_eps=shape.layer_norm_eps, pad_token_id=0)
+                                            layer_norm_eps=shape.layer_norm_eps, pad_token_id=shape.pad_token_id,
+                                            type_vocab_size=shape.type_vocab_size, position_rule=shape.position_rule)
         self.embeddings = _Embeddings(shape)
         self.encoder = _Encoder(shape.num_hidden_layers, shape.hidden_size, shape.intermediate_size, shape.layer_norm_eps)
         self.pooler = _Pooler(shape.hidden_size)   # present for state_dict compatibility; never evaluated (its
@@ -94,12 +101,15 @@ class HipBertModel(nn.Module):
 
     @staticmethod
     def from_hf(hf_model) -> "HipBertModel":
-        """Adopt a HuggingFace ``BertModel`` (what ``T/run.py:53`` constructs): same keys, weights copied."""
+        """Adopt a HuggingFace ``BertModel`` (what ``T/run.py:53`` constructs) or ``RobertaModel`` (``config.model_type ==
+        "roberta"``): same keys in the same order, weights copied."""
         c = hf_model.config
+        roberta = getattr(c, "model_type", "bert") == "roberta"
         shape = BertShape(vocab_size=c.vocab_size, hidden_size=c.hidden_size, num_hidden_layers=c.num_hidden_layers,
                           num_attention_heads=c.num_attention_heads, intermediate_size=c.intermediate_size,
                           max_position_embeddings=c.max_position_embeddings, type_vocab_size=c.type_vocab_size,
-                          layer_norm_eps=c.layer_norm_eps)
+                          layer_norm_eps=c.layer_norm_eps, pad_token_id=c.pad_token_id if roberta else 0,
+                          position_rule="pad_relative" if roberta else "absolute")
         m = HipBertModel(shape, hidden_dropout_prob=getattr(c, "hidden_dropout_prob", 0.1),
                          attention_probs_dropout_prob=getattr(c, "attention_probs_dropout_prob", 0.1))
         missing, unexpected = m.load_state_dict(hf_model.state_dict(), strict=False)

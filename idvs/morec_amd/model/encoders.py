@@ -8,7 +8,7 @@ import torch.nn as nn
 from torch.nn.init import constant_, xavier_normal_
 
 from .. import functional as F_
-from ..engine import NO_DROP, DropCfg
+from ..engine import NO_DROP, DropCfg, bert_position_rule
 from ..ops import FLT_MIN_MASK
 from .bert import HipBertModel
 from .swin import HipSwinForImageClassification
@@ -168,7 +168,7 @@ class Text_Encoder(nn.Module):
         named = [(n, p) for n, p in self.named_parameters() if ".pooler." not in n]
         names, params = zip(*named)
         cfg = (names, c.num_attention_heads, c.num_hidden_layers, self.compute_dtype, "", c.layer_norm_eps, self.mask_value,
-               drop, self.res32)
+               drop, self.res32, tuple(bert_position_rule(c).items()))
         return F_.BertEncoderFn.apply(text, cfg, *params)
 
     def forward(self, text):

@@ -25,10 +25,26 @@ class BertShape:
     max_position_embeddings: int = 512
     type_vocab_size: int = 2
     layer_norm_eps: float = 1e-12
+    pad_token_id: int = 0
+    position_rule: str = "absolute"      # "absolute": position t reads row t (BERT); "pad_relative": RoBERTa, rows counted from the pad id
 
     @staticmethod
     def named(name: str) -> "BertShape":
-        """Shapes selected the way ``T/run.py:55-72`` keys on ``bert_model_load``."""
+        """Shapes selected the way ``T/run.py:55-72`` keys on ``bert_model_load``; a name containing ``roberta`` selects the RoBERTa
+        tower (the reference's ``'roberta' in args.bert_model_load`` branch) before the size keys are looked at."""
+        if "roberta" in name:
+            common = dict(vocab_size=50265, max_position_embeddings=514, type_vocab_size=1, layer_norm_eps=1e-5, pad_token_id=1,
+                          position_rule="pad_relative")
+            rtable = {
+                "micro": dict(vocab_size=512, hidden_size=64, num_hidden_layers=2, num_attention_heads=2, intermediate_size=256,
+                              max_position_embeddings=66),
+                "large": dict(hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, intermediate_size=4096),
+                "base": dict(),
+            }
+            for key, kw in rtable.items():
+                if key in name:
+                    return BertShape(**{**common, **kw})
+            raise ValueError(f"unknown bert_model_load {name!r}")
         table = {
             "tiny": dict(hidden_size=128, num_hidden_layers=2, num_attention_heads=2, intermediate_size=512),
             "mini": dict(hidden_size=256, num_hidden_layers=4, num_attention_heads=4, intermediate_size=1024),
@@ -70,10 +86,16 @@ def bert_param_shapes(cfg: BertShape, prefix: str = BM, pooler: bool = True) -> 
     H, I = cfg.hidden_size, cfg.intermediate_size
     out = OrderedDict()
     out[prefix + "embeddings.word_embeddings.weight"] = (cfg.vocab_size, H)
-    out[prefix + "embeddings.position_embeddings.weight"] = (cfg.max_position_embeddings, H)
-    out[prefix + "embeddings.token_type_embeddings.weight"] = (cfg.type_vocab_size, H)
-    out[prefix + "embeddings.LayerNorm.weight"] = (H,)
-    out[prefix + "embeddings.LayerNorm.bias"] = (H,)
+    if cfg.position_rule == "pad_relative":      # RobertaEmbeddings registers the position table last (tests/golden/g29_roberta_keys.json)
+        out[prefix + "embeddings.token_type_embeddings.weight"] = (cfg.type_vocab_size, H)
+        out[prefix + "embeddings.LayerNorm.weight"] = (H,)
+        out[prefix + "embeddings.LayerNorm.bias"] = (H,)
+        out[prefix + "embeddings.position_embeddings.weight"] = (cfg.max_position_embeddings, H)
+    else:
+        out[prefix + "embeddings.position_embeddings.weight"] = (cfg.max_position_embeddings, H)
+        out[prefix + "embeddings.token_type_embeddings.weight"] = (cfg.type_vocab_size, H)
+        out[prefix + "embeddings.LayerNorm.weight"] = (H,)
+        out[prefix + "embeddings.LayerNorm.bias"] = (H,)
     for l in range(cfg.num_hidden_layers):
         L = prefix + f"encoder.layer.{l}."
         for n in ("query", "key", "value"):

@@ -557,6 +557,40 @@ def bert_embed_bwd_(ids32, dz, dword, dpos, dtype0, pad_id, T, order=None):
                                           code(dz.dtype), _p(order), _stream()), "morec_bert_embed_bwd")
 
 
+def roberta_pos_ids(ids32, pad_id, T, n_pos):
+    """Pad-relative position ids of ``ids32`` (int32 [n_seq * T]): ``(pos_ids, perm, cnt)`` int32 device tensors (``morec_roberta_pos_ids``)."""
+    _dev(ids32)
+    M = ids32.numel()
+    n_seq = M // T if T > 0 else 0
+    pos_ids = torch.empty(M, device=ids32.device, dtype=torch.int32)
+    perm = torch.empty(M, device=ids32.device, dtype=torch.int32)
+    cnt = torch.empty(max(n_seq, 1), device=ids32.device, dtype=torch.int32)
+    check(_lib.lib().morec_roberta_pos_ids(_p(ids32), pad_id, n_seq, T, n_pos, _p(pos_ids), _p(perm), _p(cnt), _stream()),
+          "morec_roberta_pos_ids")
+    return pos_ids, perm, cnt
+
+
+def bert_embed_fwd_pos(ids32, pos_ids, word, pos, type0, gamma, beta, eps, T, dtype, p_out=0.0, seed_out=0):
+    """``bert_embed_fwd`` with the position row of every token given by ``pos_ids`` (int32 [M])."""
+    M = ids32.numel()
+    H = word.shape[1]
+    z = torch.empty((M, H), device=word.device, dtype=dtype)
+    y = torch.empty_like(z)
+    mean = torch.empty(M, device=word.device, dtype=torch.float32)
+    rstd = torch.empty(M, device=word.device, dtype=torch.float32)
+    check(_lib.lib().morec_bert_embed_fwd_pos(_p(ids32), _p(pos_ids), _p(word), _p(pos), _p(type0), _p(gamma), _p(beta), eps, _p(z),
+                                              _p(y), _p(mean), _p(rstd), M, T, H, code(dtype), p_out, seed_out, _stream()),
+          "morec_bert_embed_fwd_pos")
+    return y, z, mean, rstd
+
+
+def roberta_embed_bwd_(ids32, dz, dword, dpos, dtype0, pad_id, T, perm, cnt, pos_pad, order=None):
+    """``bert_embed_bwd_`` under the pad-relative position rule: ``perm`` / ``cnt`` from ``roberta_pos_ids``; ``dpos`` is the whole table's gradient."""
+    M, H = dz.shape
+    check(_lib.lib().morec_roberta_embed_bwd(_p(ids32), _p(dz), _p(dword), _p(dpos), _p(dtype0), pad_id, M, T, H, code(dz.dtype),
+                                             _p(order), _p(perm), _p(cnt), pos_pad, dpos.shape[0], _stream()), "morec_roberta_embed_bwd")
+
+
 def gather_rows(table, idx32, dtype):
     R, D = idx32.numel(), table.shape[1]
     out = torch.empty((R, D), device=table.device, dtype=dtype)

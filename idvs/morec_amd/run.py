@@ -59,11 +59,19 @@ def setup_seed(seed):   # T/run.py:307-314
     random.seed(seed)
 
 
-def synthetic_dataset(n_users, n_items, S, T, seed=12345, full_len=False, extra_T=()):
+def synthetic_vocab(args, text):
+    """Token ids of a ``--synthetic`` text catalogue must be rows of the tower's word table: its vocabulary size (30522 otherwise)."""
+    return BertShape.named(args.bert_model_load).vocab_size if text else 30522
+
+
+def synthetic_dataset(n_users, n_items, S, T, seed=12345, full_len=False, extra_T=(), vocab=30522):
     """MIND-shaped synthetic data in the structures ``read_behaviors`` / ``get_doc_input_bert`` return.
     ``full_len``: every user has raw history S + 3 (train sequence of S + 1 items: the throughput shape of bench.py).
     ``extra_T``: token counts of further text attributes (abstract, body: ``--news_attributes title,abstract``); their [ids | mask]
-    blocks follow the title's in the item rows, as ``get_doc_input_bert`` + ``T/run.py:86-90`` lay them out."""
+    blocks follow the title's in the item rows, as ``get_doc_input_bert`` + ``T/run.py:86-90`` lay them out.
+    ``vocab``: token ids stay below it (a micro tower has 512 word rows; 1000 .. 30521 as before for the full vocabularies)."""
+    assert vocab > 102, "the synthetic titles use the ids 101 / 102"
+    lo_tok = 1000 if vocab > 2000 else 103
     rng = np.random.default_rng(seed)
     w = 1.0 / np.arange(1, n_items + 1)
     w /= w.sum()
@@ -80,7 +88,7 @@ def synthetic_dataset(n_users, n_items, S, T, seed=12345, full_len=False, extra_
     pop = np.append([1], counts[1:] / counts[1:].sum())
     content = np.zeros((n_items + 1, 2 * T), dtype=np.int64)
     tl = rng.integers(8, T + 1, n_items)
-    toks = rng.integers(1000, 30522, (n_items, T))
+    toks = rng.integers(lo_tok, vocab, (n_items, T))
     valid = np.arange(T)[None, :] < tl[:, None]
     toks = np.where(valid, toks, 0)
     toks[:, 0] = 101
@@ -89,7 +97,7 @@ def synthetic_dataset(n_users, n_items, S, T, seed=12345, full_len=False, extra_
     for Tx in extra_T:
         blk = np.zeros((n_items + 1, 2 * Tx), dtype=np.int64)
         tl = rng.integers(8, Tx + 1, n_items)
-        toks = rng.integers(1000, 30522, (n_items, Tx))
+        toks = rng.integers(lo_tok, vocab, (n_items, Tx))
         valid = np.arange(Tx)[None, :] < tl[:, None]
         toks = np.where(valid, toks, 0)
         toks[:, 0] = 101
@@ -323,10 +331,11 @@ def write_synthetic_special(args, item_num, vision, n_users=48, n_new=12, seed=2
     write(getattr(args, "new_items", "None"), ["%s\n" % name(item_num + 1 + k) for k in range(n_new)])
 
 
-def synthetic_new_item_docs(args, item_num, n_new=12, seed=1357):
+def synthetic_new_item_docs(args, item_num, n_new=12, seed=1357, vocab=30522):
     """Text content of the synthetic new items (ids item_num + 1 ..) in ``read_news_bert``'s form: per item, one tokenizer output
     (``input_ids`` / ``attention_mask`` lists) per attribute, ``[]`` for an attribute not in ``--news_attributes``."""
     rng = np.random.default_rng(seed)
+    lo_tok = 1000 if vocab > 2000 else 103
     docs = {}
     for k in range(n_new):
         enc = []
@@ -335,7 +344,7 @@ def synthetic_new_item_docs(args, item_num, n_new=12, seed=1357):
                 enc.append([])
                 continue
             L = int(rng.integers(3, T + 1))
-            ids = [101] + [int(v) for v in rng.integers(1000, 30522, L - 2)] + [102] + [0] * (T - L)
+            ids = [101] + [int(v) for v in rng.integers(lo_tok, vocab, L - 2)] + [102] + [0] * (T - L)
             enc.append({"input_ids": ids, "attention_mask": [1] * L + [0] * (T - L)})
         docs[item_num + 1 + k] = enc
     return docs
@@ -353,7 +362,7 @@ def run_eval_special(model, item_content, catalogue, batch_size, item_num, use_m
     if args.synthetic > 0:
         write_synthetic_special(args, item_num, vision)
         if use_modal and not vision:
-            docs = synthetic_new_item_docs(args, item_num)
+            docs = synthetic_new_item_docs(args, item_num, vocab=synthetic_vocab(args, True))
             catalogue = dict(catalogue, before_item_id_to_dic=docs,
                              before_item_name_to_id={synthetic_item_name(i, False): i for i in docs} | catalogue["item_name_to_id"])
     if use_modal and new_seqs == "None":
@@ -425,13 +434,15 @@ def model_dir_of(args, world: int = 1):
 
 def normalize_pretrained_bert_keys(sd: dict) -> dict:
     """Key names of a stock ``bert-*`` checkpoint file -> ``BertModel.state_dict()`` names, as ``from_pretrained`` does at load time
-    (``T/run.py:51-53``): the ``bert.`` prefix of ``BertForPreTraining`` files is dropped, the TF-era LayerNorm names ``*.LayerNorm.gamma``
+    (``T/run.py:51-53``): the ``bert.`` prefix of ``BertForPreTraining`` files (``roberta.`` of ``RobertaForMaskedLM`` ones) is dropped, the TF-era LayerNorm names ``*.LayerNorm.gamma``
     / ``*.LayerNorm.beta`` (what ``bert-base-uncased/pytorch_model.bin`` holds) become ``weight`` / ``bias``, and the pre-training
     heads (``cls.*``) and the ``position_ids`` buffer are left out."""
     out = {}
     for k, v in sd.items():
         if k.startswith("bert."):
             k = k[len("bert."):]
+        elif k.startswith("roberta."):
+            k = k[len("roberta."):]
         if k.startswith("cls.") or k.endswith("embeddings.position_ids"):
             continue
         if k.endswith("LayerNorm.gamma"):
@@ -463,6 +474,23 @@ def _load_pretrained_text_tower(bert, args):
             return True
     Log.warning("text tower: no pretrained weights under %s -- RANDOM initialisation" % d)
     return False
+
+
+def load_text_tokenizer(args):
+    """The tokenizer of ``--bert_model_load`` from ``<pretrained_dir>/<bert_model_load>`` (``T/run.py:28-39``): ``RobertaTokenizer``
+    (``vocab.json`` + ``merges.txt``, pads with id 1) for a name containing 'roberta', ``BertTokenizer`` (``vocab.txt``) otherwise."""
+    tok_dir = os.path.join(args.pretrained_dir, args.bert_model_load)
+    roberta = "roberta" in args.bert_model_load
+    needed = ("vocab.json", "merges.txt") if roberta else ("vocab.txt",)
+    absent = [f for f in needed if not os.path.exists(os.path.join(tok_dir, f))]
+    if absent:
+        raise SystemExit(f"modal run on real data: no tokenizer vocabulary under {tok_dir}: {' and '.join(absent)} missing "
+                         f"(--pretrained_dir / --bert_model_load; the tokenizer of this tower reads {' + '.join(needed)})")
+    if roberta:
+        from transformers import RobertaTokenizer
+        return RobertaTokenizer.from_pretrained(tok_dir)
+    from transformers import BertTokenizer
+    return BertTokenizer.from_pretrained(tok_dir)
 
 
 def build_text_tower(args, freeze=True):
@@ -511,7 +539,8 @@ def load_dataset(args, use_modal, vision):
         extra_T = [w for n, w in (("abstract", args.num_words_abstract), ("body", args.num_words_body))
                    if use_modal and not vision and n in args.news_attributes]
         item_num, content, users_train, users_valid, users_test, hist_valid, hist_test, pop = synthetic_dataset(
-            args.synthetic, args.synthetic_items, S, T, full_len=bool(getattr(args, "synthetic_full_len", False)), extra_T=extra_T)
+            args.synthetic, args.synthetic_items, S, T, full_len=bool(getattr(args, "synthetic_full_len", False)), extra_T=extra_T,
+            vocab=synthetic_vocab(args, use_modal and not vision))
         item_content = content if use_modal else np.arange(item_num + 1)
         if vision:      # decoded uint8 images; a real run passes --images_npy (what the LMDB of V/data_utils holds after Resize)
             R = args.CV_resize
@@ -520,12 +549,8 @@ def load_dataset(args, use_modal, vision):
             assert item_content.shape == (item_num + 1, R, R, 3) and item_content.dtype == np.uint8
         catalogue = dict(item_name_to_id={synthetic_item_name(i, vision): i for i in range(1, item_num + 1)})
     elif use_modal and not vision:                                       # T/run.py:28-98: tokenizer -> fixed-length id / mask tables
-        from transformers import BertTokenizer
         from .data_utils import get_doc_input_bert, read_news_bert
-        tok_dir = os.path.join(args.pretrained_dir, args.bert_model_load)
-        if not os.path.exists(os.path.join(tok_dir, "vocab.txt")):
-            raise SystemExit(f"modal run on real data: no tokenizer vocabulary under {tok_dir} (--pretrained_dir / --bert_model_load)")
-        tokenizer = BertTokenizer.from_pretrained(tok_dir)
+        tokenizer = load_text_tokenizer(args)
         a, b, c = read_news_bert(os.path.join(args.root_data_dir, args.dataset, args.news), args, tokenizer)
         item_num, item_id_to_dic, users_train, users_valid, users_test, hist_valid, hist_test, name_to_id, pop = read_behaviors(
             os.path.join(args.root_data_dir, args.dataset, args.behaviors), a, b, c, S, args.min_seq_len, Log)
@@ -897,18 +922,15 @@ def train_dssm(args, use_modal, local_rank):
     if args.synthetic > 0:
         extra_T = [w for n, w in (("abstract", args.num_words_abstract), ("body", args.num_words_body)) if use_modal and n in args.news_attributes]
         item_num, content, tr, _, te, _, _, _ = synthetic_dataset(args.synthetic, args.synthetic_items, S, T,
-                                                                 full_len=bool(getattr(args, "synthetic_full_len", False)), extra_T=extra_T)
+                                                                 full_len=bool(getattr(args, "synthetic_full_len", False)), extra_T=extra_T,
+                                                                 vocab=synthetic_vocab(args, use_modal))
         seqs = [list(tr[u]) + list(te[u][-2:]) for u in range(args.synthetic)]      # the raw sequences (at most S + 3 items), split by the DSSM rule
         users_train, _, train_pairs, valid_pairs, test_pairs, hist_valid, hist_test = dd.pairs_from_sequences(seqs)
         user_num = len(seqs)
         item_content = content if use_modal else np.arange(item_num + 1)
     elif use_modal:
-        from transformers import BertTokenizer
         from .data_utils import get_doc_input_bert, read_news_bert
-        tok_dir = os.path.join(args.pretrained_dir, args.bert_model_load)
-        if not os.path.exists(os.path.join(tok_dir, "vocab.txt")):
-            raise SystemExit(f"modal run on real data: no tokenizer vocabulary under {tok_dir} (--pretrained_dir / --bert_model_load)")
-        a, b, _ = read_news_bert(os.path.join(args.root_data_dir, args.dataset, args.news), args, BertTokenizer.from_pretrained(tok_dir))
+        a, b, _ = read_news_bert(os.path.join(args.root_data_dir, args.dataset, args.news), args, load_text_tokenizer(args))
         user_num, item_num, id2content, users_train, _, train_pairs, valid_pairs, test_pairs, hist_valid, hist_test = dd.read_behaviors(
             os.path.join(args.root_data_dir, args.dataset, args.behaviors), a, b, args.min_seq_len, S, Log)
         item_content = np.concatenate([x for x in get_doc_input_bert(id2content, args) if x is not None], axis=1)

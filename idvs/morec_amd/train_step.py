@@ -342,6 +342,7 @@ class TrainStep:
             H, L = bert.config.hidden_size, bert.config.num_hidden_layers
             self.bert_heads = bert.config.num_attention_heads
             self.bert_layers, self.bert_eps = L, bert.config.layer_norm_eps
+            self.bert_pos_kw = engine.bert_position_rule(bert.config)      # RoBERTa: position rows counted from the pad token id
             self.bert_mask_value = m.bert_encoder.text_encoders["title"].mask_value
             # lowest trainable point of the tower: the backward (and what the forward keeps for it) stops there
             self.bert_grad_from = engine.bert_grad_from(list(a0.offsets) if len(self.groups) > 1 else [], L)
@@ -469,7 +470,7 @@ class TrainStep:
                 passes.append(engine.bert_forward(p, prep_b, sub, self.bert_heads, self.dtype, True, self.bert_eps,
                                                   self.bert_mask_value, engine.TE, d_item.stream(ai), grad_from=self.bert_grad_from,
                                                   packing=packs[ai], on_use=self._await_params if (self._param_ready and ai == 0) else None,
-                                                  res32=self.res32))
+                                                  res32=self.res32, **self.bert_pos_kw))
             E = passes[0][0] if n_attr == 1 else ops.scaled_sum([e for e, _ in passes], 1.0 / n_attr)      # encoders.py:113-116: the mean
             self._await_params(None)      # whatever the tower did not ask for (the recommender group's slice) before SASRec reads it
         else:

@@ -573,6 +573,26 @@ int morec_bert_embed_fwd(const int32_t* ids, const float* word, const float* pos
  * caller error (lost updates); without order every row is added atomically. */
 int morec_bert_embed_bwd(const int32_t* ids, const void* dz, float* dword, float* dpos, float* dtype0, int pad_id,
                          int M, int T, int H, int dtype, const int32_t* order, void* stream);
+/* RoBERTa embeddings: position ids counted from the pad token (HF create_position_ids_from_input_ids, computed from the ids, never
+ * from the attention mask).  Per sequence n of T tokens: pos_ids[n*T + t] = pad_id if ids == pad_id, else pad_id + 1 + k for the
+ * k-th (from 0) non-pad token; cnt[n] = number of non-pad tokens; perm[n*T + k] = position of the k-th non-pad token for
+ * k < cnt[n], followed by the pad positions in order (a permutation of 0 .. T-1).  All int32 device arrays.  One wavefront per
+ * sequence, no LDS, no atomics, no allocation, no host synchronisation.  Null pointers, n_seq or T <= 0, pad_id < 0, or
+ * pad_id + T >= n_pos (the largest id written must be a row of the n_pos-row table): MOREC_E_ARG before anything is launched. */
+int morec_roberta_pos_ids(const int32_t* ids, int pad_id, int n_seq, int T, int n_pos, int32_t* pos_ids_out, int32_t* perm_out,
+                          int32_t* cnt_out, void* stream);
+/* morec_bert_embed_fwd with the position row of token m taken from pos_ids[m] instead of m % T (same summation order, LayerNorm and
+ * dropout stream). */
+int morec_bert_embed_fwd_pos(const int32_t* ids, const int32_t* pos_ids, const float* word, const float* pos, const float* type0,
+                             const float* gamma, const float* beta, float eps, void* z_out, void* y, float* mean, float* rstd,
+                             int M, int T, int H, int dtype, float p_out, uint64_t seed_out, void* stream);
+/* morec_bert_embed_bwd under the pad-relative rule (perm, cnt from morec_roberta_pos_ids): dpos[pos_pad + 1 + k] += the rows
+ * n*T + perm[n*T + k] of the sequences with k < cnt[n]; dtype0 += every row; the word scatter as above.  Row pos_pad of dpos and the
+ * rows outside pos_pad + 1 .. pos_pad + T are not written.  pos_pad < 0 or pos_pad + T >= n_pos: MOREC_E_ARG.  Row widths outside
+ * the 16-byte vector layout (H % (16 / sizeof(dtype)) != 0 or more than 256 vectors per row): MOREC_E_UNSUPPORTED. */
+int morec_roberta_embed_bwd(const int32_t* ids, const void* dz, float* dword, float* dpos, float* dtype0, int pad_id, int M, int T,
+                            int H, int dtype, const int32_t* order, const int32_t* perm, const int32_t* cnt, int pos_pad, int n_pos,
+                            void* stream);
 /* out[r, :] = table[idx[r], :]  (fp32 table -> dtype out).  T/model/model.py:37 nn.Embedding lookup. */
 int morec_gather_rows(const float* table, const int32_t* idx, void* out, int R, int D, int dtype, void* stream);
 /* dtable[idx[r], :] += d[r, :] unless idx[r] == pad_id (padding_idx=0, T/model/model.py:27) */
