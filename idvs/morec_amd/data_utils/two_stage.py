@@ -14,8 +14,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .. import beit_engine, engine, mae_engine, ops, swin_engine
-from ..model.encoders import Bert_Encoder, MAE_Encoder, Vit_Encoder, resolve_fp32_gemm
+from .. import beit_engine, engine, mae_engine, ops, opt_engine, swin_engine
+from ..model.encoders import Bert_Encoder, MAE_Encoder, Text_Encoder_mean, Vit_Encoder, resolve_fp32_gemm
 from .dataset import collate_bce_batch
 from .metrics import _module
 
@@ -23,6 +23,19 @@ from .metrics import _module
 def _text_features_fn(enc: Bert_Encoder):
     te = enc.text_encoders["title"]
     c = te.bert_model.config
+    if isinstance(te, Text_Encoder_mean):      # the OPT tower: the pooled mean in front of fc (opt_engine.opt_forward(features_only=True))
+        po = dict(te.named_parameters())
+        oprep = opt_engine.opt_prepare(po, te.bert_model.shape, te.compute_dtype, "", features_only=True)
+
+        def run_opt(news):
+            vecs = []
+            for name in enc.newsname:
+                text = torch.narrow(news, 1, enc.attributes2start[name], enc.attributes2length[name]).contiguous()
+                mean, _ = opt_engine.opt_forward(po, oprep, te.bert_model.shape, text, te.compute_dtype, False, "", unpad=te.unpad,
+                                                 features_only=True)
+                vecs.append(mean.float())
+            return vecs[0] if len(vecs) == 1 else torch.mean(torch.stack(vecs, dim=1), dim=1)
+        return run_opt
     p = {n: t for n, t in te.named_parameters() if ".pooler." not in n}
     prep = engine.bert_prepare(p, c.num_hidden_layers, te.compute_dtype, "")
 

@@ -8,7 +8,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from . import beit_engine, engine, mae_engine, ops, swin_engine
+from . import beit_engine, engine, mae_engine, ops, opt_engine, swin_engine
 
 
 def _zeros_like_params(names, params, skip=()):
@@ -140,6 +140,42 @@ class MaeEncoderFn(torch.autograd.Function):
         grads = _zeros_like_params(names, [p[n] for n in names], skip=skip)
         with ops.fp32_gemm_mode(ctx.fp32_gemm):
             mae_engine.mae_backward(p, prep, saved, d_item.contiguous(), grads, prefix)
+            engine.WgradStream.join(d_item.device)
+        needs = ctx.needs[2:]
+        return (None, None) + tuple(grads.get(n) if nd else None for n, nd in zip(names, needs))
+
+
+class OptEncoderFn(torch.autograd.Function):
+    """``Text_Encoder_mean.forward`` (``T/model/encoders.py:41-50``) over HF ``OPTModel`` arithmetic.  ``cfg = (names, shape, dtype,
+    prefix, drop, unpad, features_only)``.  The backward ends at the lowest trainable layer (``opt_engine.opt_grad_from``); above it every
+    gradient is computed and a frozen parameter's is not handed out."""
+
+    @staticmethod
+    def forward(ctx, text, cfg, *params):
+        names, shape, dtype, prefix, drop, unpad, features_only = cfg
+        p = dict(zip(names, params))
+        need = any(ctx.needs_input_grad) and not features_only
+        prep = opt_engine.opt_prepare(p, shape, dtype, prefix, features_only=features_only)
+        # the backward stops at the lowest trainable point of the tower (T/run.py:73-75 freezes a prefix by parameter index)
+        grad_from = opt_engine.opt_grad_from([n for n, nd in zip(names, ctx.needs_input_grad[2:]) if nd], shape.num_hidden_layers, prefix)
+        out, saved = opt_engine.opt_forward(p, prep, shape, text, dtype, need, prefix, drop, unpad=unpad, features_only=features_only,
+                                            grad_from=grad_from)
+        ctx.stuff = (p, prep, saved, names, prefix, shape)
+        ctx.needs = ctx.needs_input_grad
+        ctx.fp32_gemm = ops.FP32_GEMM
+        if features_only:
+            ctx.mark_non_differentiable(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_item):
+        p, prep, saved, names, prefix, shape = ctx.stuff
+        ctx.stuff = None
+        skip = {opt_engine.opt_layer_names(prefix, l) + f"self_attn.{n}.{k}" for l in range(shape.num_hidden_layers)
+                for n in ("q_proj", "k_proj", "v_proj") for k in ("weight", "bias")}
+        grads = _zeros_like_params(names, [p[n] for n in names], skip=skip)
+        with ops.fp32_gemm_mode(ctx.fp32_gemm):
+            opt_engine.opt_backward(p, prep, saved, d_item.contiguous(), grads, prefix)
             engine.WgradStream.join(d_item.device)
         needs = ctx.needs[2:]
         return (None, None) + tuple(grads.get(n) if nd else None for n, nd in zip(names, needs))

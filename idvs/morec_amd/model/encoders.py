@@ -14,6 +14,8 @@ from .bert import HipBertModel
 from .swin import HipSwinForImageClassification
 from .beit import HipBeitForImageClassification, check_beit_config
 from .mae import HipViTMAEModel
+from .opt import HipOPTModel
+from ..opt_engine import check_opt_config
 from ..mae_engine import MAE_SEED_EVAL, MAE_SEED_TRAIN, mae_keep
 from .modules import TransformerEncoder
 
@@ -175,6 +177,32 @@ class Text_Encoder(nn.Module):
         return self.encode(text).float()
 
 
+class Text_Encoder_mean(nn.Module):
+    """``T/model/encoders.py:31-50``: ``GELU(fc(sum(h * mask) / clamp(sum(mask), 1e-9)))`` with ``h`` the last hidden state of a HF
+    ``OPTModel`` (``opt_engine``).  The ``*_res32`` modes run this tower in the plain 16-bit type: a pre-LN residual stream is not
+    re-normalised between the blocks, and the fp32-stream LayerNorm kernels are built for the post-LN layers."""
+
+    def __init__(self, bert_model, item_embedding_dim, word_embedding_dim, compute_dtype=None):
+        super().__init__()
+        self.bert_model = bert_model if isinstance(bert_model, HipOPTModel) else HipOPTModel.from_hf(bert_model)
+        check_opt_config(self.bert_model.config)
+        if word_embedding_dim != self.bert_model.shape.hidden_size:
+            raise ValueError(f"word_embedding_dim {word_embedding_dim} does not match the OPT model's hidden size "
+                             f"{self.bert_model.shape.hidden_size}")
+        self.fc = nn.Linear(word_embedding_dim, item_embedding_dim)
+        self.compute_dtype = compute_dtype or resolve_dtype()
+        self.unpad = None      # None: MOREC_UNPAD decides; False keeps the padded layout
+
+    def encode(self, text, drop: DropCfg = NO_DROP, features_only: bool = False):
+        check_opt_config(self.bert_model.config)
+        names, params = zip(*self.named_parameters())
+        cfg = (names, self.bert_model.shape, self.compute_dtype, "", drop, self.unpad, features_only)
+        return F_.OptEncoderFn.apply(text, cfg, *params)
+
+    def forward(self, text):
+        return self.encode(text).float()
+
+
 class Bert_Encoder(nn.Module):
     def __init__(self, args, bert_model):
         super().__init__()
@@ -187,10 +215,13 @@ class Bert_Encoder(nn.Module):
         self.attributes2start = {key: sum(list(self.attributes2length.values())[:list(self.attributes2length.keys()).index(key)])
                                  for key in self.attributes2length.keys()}
         assert len(args.news_attributes) > 0
-        if 'opt' in args.bert_model_load:
-            raise NotImplementedError("OPT mean-pooling encoder (T/model/encoders.py:31-50) is outside the hot path")
-        self.text_encoders = nn.ModuleDict({
-            'title': Text_Encoder(bert_model, args.embedding_dim, args.word_embedding_dim, resolve_dtype(args), resolve_res32(args))})
+        # T/model/encoders.py:96-99; a name is tested for 'roberta' first, as the drivers do (T/run.py:37-47)
+        if 'opt' in args.bert_model_load and 'roberta' not in args.bert_model_load:
+            self.text_encoders = nn.ModuleDict({
+                'title': Text_Encoder_mean(bert_model, args.embedding_dim, args.word_embedding_dim, resolve_dtype(args))})
+        else:
+            self.text_encoders = nn.ModuleDict({
+                'title': Text_Encoder(bert_model, args.embedding_dim, args.word_embedding_dim, resolve_dtype(args), resolve_res32(args))})
         # (the reference iterates a set intersection, i.e. in hash order; the mean over attributes does not depend on it -- a fixed order
         # keeps the fp32 sum of three passes identical across processes)
         self.newsname = [name for name in ('title', 'abstract', 'body') if name in set(args.news_attributes)]

@@ -591,6 +591,49 @@ def roberta_embed_bwd_(ids32, dz, dword, dpos, dtype0, pad_id, T, perm, cnt, pos
                                              _p(order), _p(perm), _p(cnt), pos_pad, dpos.shape[0], _stream()), "morec_roberta_embed_bwd")
 
 
+def mask_pos_ids(mask32, T, offset, n_pos):
+    """Position ids counted from the attention mask (int32 [n_seq * T], nonzero = kept): ``(pos_ids, perm, cnt)`` int32 device tensors
+    (``morec_mask_pos_ids``); ``perm`` / ``cnt`` are what ``roberta_embed_bwd_`` walks with ``pos_pad = offset - 1``."""
+    _dev(mask32)
+    M = mask32.numel()
+    n_seq = M // T if T > 0 else 0
+    pos_ids = torch.empty(M, device=mask32.device, dtype=torch.int32)
+    perm = torch.empty(M, device=mask32.device, dtype=torch.int32)
+    cnt = torch.empty(max(n_seq, 1), device=mask32.device, dtype=torch.int32)
+    check(_lib.lib().morec_mask_pos_ids(_p(mask32), n_seq, T, offset, n_pos, _p(pos_ids), _p(perm), _p(cnt), _stream()),
+          "morec_mask_pos_ids")
+    return pos_ids, perm, cnt
+
+
+def opt_embed_fwd(ids32, pos_ids, word, pos, dtype):
+    """``round(word[ids] + pos[pos_ids])`` [M, H] in ``dtype`` (``morec_opt_embed_fwd``: no LayerNorm, token type or dropout)."""
+    _dev(word), _dev(pos)
+    M, H = ids32.numel(), word.shape[1]
+    out = torch.empty((M, H), device=word.device, dtype=dtype)
+    check(_lib.lib().morec_opt_embed_fwd(_p(ids32), _p(pos_ids), _p(word), _p(pos), _p(out), M, H, code(dtype), _stream()),
+          "morec_opt_embed_fwd")
+    return out
+
+
+def masked_mean_fwd(x, keep, n_seq, T, cu=None):
+    """Mean of the kept rows of every title ([n_seq, H], ``morec_masked_mean_fwd``): ``keep`` fp32 per row of ``x``; ``cu`` int32
+    [n_seq + 1] for the packed layout, None for the padded one ([n_seq * T] rows)."""
+    _dev(x), _dev(keep)
+    H = x.shape[1]
+    out = torch.empty((n_seq, H), device=x.device, dtype=x.dtype)
+    check(_lib.lib().morec_masked_mean_fwd(_p(x), _p(keep), _p(cu), _p(out), n_seq, T, H, code(x.dtype), _stream()), "morec_masked_mean_fwd")
+    return out
+
+
+def masked_mean_bwd(g, keep, n_seq, T, rows, cu=None):
+    """Backward of ``masked_mean_fwd``: [rows, H] with ``g[n] / count`` on the kept rows of title n and zeros on the others."""
+    _dev(g), _dev(keep)
+    H = g.shape[1]
+    dx = torch.empty((rows, H), device=g.device, dtype=g.dtype)
+    check(_lib.lib().morec_masked_mean_bwd(_p(g), _p(keep), _p(cu), _p(dx), n_seq, T, H, code(g.dtype), _stream()), "morec_masked_mean_bwd")
+    return dx
+
+
 def gather_rows(table, idx32, dtype):
     R, D = idx32.numel(), table.shape[1]
     out = torch.empty((R, D), device=table.device, dtype=dtype)

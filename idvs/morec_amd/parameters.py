@@ -199,6 +199,31 @@ def check_beit_args(args):
     return True
 
 
+def is_opt_run(args) -> bool:
+    """A run whose item tower is the OPT text tower: a modal text tower whose ``--bert_model_load`` the reference routes to ``OPTModel`` /
+    ``Text_Encoder_mean`` (``'opt' in bert_model_load``, tested after ``'roberta'``, ``T/run.py:37-47``)."""
+    name = str(getattr(args, "bert_model_load", ""))
+    return ("modal" in str(args.item_tower) and str(getattr(args, "CV_model_load", "None")) == "None" and "opt" in name
+            and "roberta" not in name)
+
+
+def check_opt_args(args):
+    """What the OPT tower does not run with: exits with the reason (before anything touches a device).  True for an OPT run."""
+    if not is_opt_run(args):
+        return False
+    why = None
+    if getattr(args, "fused_step", False):
+        why = ("--fused_step" + (" --pool_negatives" if getattr(args, "pool_negatives", False) else "") +
+               ": train_step.TrainStep covers the BERT / RoBERTa, ID and Swin towers; the OPT tower trains on the drop-in autograd path")
+    elif getattr(args, "graph", False):
+        why = "--graph replays the fused step (train_step.TrainStep), which the OPT tower does not use"
+    elif getattr(args, "arch", "sasrec") == "dssm":
+        why = "--arch dssm: the reference's DSSM package has no OPT branch, and none is built"
+    if why:
+        raise SystemExit(f"--bert_model_load {args.bert_model_load} (OPT text tower): " + why)
+    return True
+
+
 def check_dssm_args(args):
     """What ``--arch dssm`` does not run with: exits with the reason (before anything touches a device).  True for a DSSM run."""
     if getattr(args, "arch", "sasrec") != "dssm":

@@ -42,8 +42,10 @@ from .model.beit import HipBeitForImageClassification
 from .model.mae import HipViTMAEModel
 from .beit_engine import BeitShape
 from .mae_engine import MaeShape
-from .parameters import (check_beit_args, check_dssm_args, check_fusion_args, check_id_two_stage_args, check_mae_args, check_two_stage_args, is_beit_run, is_mae_run,
-                         parse_args)
+from .model.opt import HipOPTModel, strip_model_prefix
+from .opt_engine import OptShape
+from .parameters import (check_beit_args, check_dssm_args, check_fusion_args, check_id_two_stage_args, check_mae_args, check_opt_args, check_two_stage_args,
+                         is_beit_run, is_mae_run, is_opt_run, parse_args)
 from . import engine
 from .train_step import TrainStep
 from .lr_schedule import AutogradStepControl, schedule_from_args
@@ -61,16 +63,30 @@ def setup_seed(seed):   # T/run.py:307-314
 
 def synthetic_vocab(args, text):
     """Token ids of a ``--synthetic`` text catalogue must be rows of the tower's word table: its vocabulary size (30522 otherwise)."""
+    if text and is_opt_run(args):
+        return OptShape.named(args.bert_model_load).vocab_size
     return BertShape.named(args.bert_model_load).vocab_size if text else 30522
 
 
-def synthetic_dataset(n_users, n_items, S, T, seed=12345, full_len=False, extra_T=(), vocab=30522):
+def _synthetic_opt_titles(rng, n_items, T, vocab):
+    """[ids | mask] of OPT titles as GPT2Tokenizer lays them out for OPT: ``</s>`` (2) first, ids inside the vocabulary, right-padded
+    with 1 under mask 0."""
+    assert vocab > 4, "the OPT ids 0 .. 2 are special tokens"
+    tl = rng.integers(min(8, T), T + 1, n_items)
+    toks = rng.integers(3, vocab, (n_items, T))
+    valid = np.arange(T)[None, :] < tl[:, None]
+    toks = np.where(valid, toks, 1)
+    toks[:, 0] = 2
+    return toks, valid
+
+
+def synthetic_dataset(n_users, n_items, S, T, seed=12345, full_len=False, extra_T=(), vocab=30522, opt=False):
     """MIND-shaped synthetic data in the structures ``read_behaviors`` / ``get_doc_input_bert`` return.
     ``full_len``: every user has raw history S + 3 (train sequence of S + 1 items: the throughput shape of bench.py).
     ``extra_T``: token counts of further text attributes (abstract, body: ``--news_attributes title,abstract``); their [ids | mask]
     blocks follow the title's in the item rows, as ``get_doc_input_bert`` + ``T/run.py:86-90`` lay them out.
     ``vocab``: token ids stay below it (a micro tower has 512 word rows; 1000 .. 30521 as before for the full vocabularies)."""
-    assert vocab > 102, "the synthetic titles use the ids 101 / 102"
+    assert opt or vocab > 102, "the synthetic titles use the ids 101 / 102"
     lo_tok = 1000 if vocab > 2000 else 103
     rng = np.random.default_rng(seed)
     w = 1.0 / np.arange(1, n_items + 1)
@@ -87,6 +103,13 @@ def synthetic_dataset(n_users, n_items, S, T, seed=12345, full_len=False, extra_
     counts[1:] += 1e-9
     pop = np.append([1], counts[1:] / counts[1:].sum())
     content = np.zeros((n_items + 1, 2 * T), dtype=np.int64)
+    if opt:      # (row 0, the padding item, stays all-zero ids under an all-zero mask, as get_doc_input_bert leaves it)
+        blocks = []
+        for Tx in (T,) + tuple(extra_T):
+            blk = np.zeros((n_items + 1, 2 * Tx), dtype=np.int64)
+            blk[1:, :Tx], blk[1:, Tx:] = _synthetic_opt_titles(rng, n_items, Tx, vocab)
+            blocks.append(blk)
+        return n_items, np.concatenate(blocks, axis=1), users_train, users_valid, users_test, hist_valid, hist_test, pop
     tl = rng.integers(8, T + 1, n_items)
     toks = rng.integers(lo_tok, vocab, (n_items, T))
     valid = np.arange(T)[None, :] < tl[:, None]
@@ -336,6 +359,7 @@ def synthetic_new_item_docs(args, item_num, n_new=12, seed=1357, vocab=30522):
     (``input_ids`` / ``attention_mask`` lists) per attribute, ``[]`` for an attribute not in ``--news_attributes``."""
     rng = np.random.default_rng(seed)
     lo_tok = 1000 if vocab > 2000 else 103
+    opt = is_opt_run(args)      # </s> first, ids inside the vocabulary, right-padded with 1
     docs = {}
     for k in range(n_new):
         enc = []
@@ -344,7 +368,10 @@ def synthetic_new_item_docs(args, item_num, n_new=12, seed=1357, vocab=30522):
                 enc.append([])
                 continue
             L = int(rng.integers(3, T + 1))
-            ids = [101] + [int(v) for v in rng.integers(lo_tok, vocab, L - 2)] + [102] + [0] * (T - L)
+            if opt:
+                ids = [2] + [int(v) for v in rng.integers(3, vocab, L - 1)] + [1] * (T - L)
+            else:
+                ids = [101] + [int(v) for v in rng.integers(lo_tok, vocab, L - 2)] + [102] + [0] * (T - L)
             enc.append({"input_ids": ids, "attention_mask": [1] * L + [0] * (T - L)})
         docs[item_num + 1 + k] = enc
     return docs
@@ -453,7 +480,7 @@ def normalize_pretrained_bert_keys(sd: dict) -> dict:
     return out
 
 
-def _load_pretrained_text_tower(bert, args):
+def _load_pretrained_text_tower(bert, args, normalize=None):
     """``BertModel.from_pretrained(bert_model_load)`` (``T/run.py:51-53``): weights from ``<pretrained_dir>/<bert_model_load>/
     pytorch_model.bin`` (or ``model.safetensors``) when that directory exists; otherwise the tower keeps its random
     initialisation and says so -- there are no checkpoints in this image (``pretrained_models/`` ships configs only)."""
@@ -466,7 +493,7 @@ def _load_pretrained_text_tower(bert, args):
             else:
                 from safetensors.torch import load_file
                 sd = load_file(path)
-            missing, unexpected = bert.load_state_dict(normalize_pretrained_bert_keys(sd), strict=False)
+            missing, unexpected = bert.load_state_dict((normalize or normalize_pretrained_bert_keys)(sd), strict=False)
             missing = [k for k in missing if not k.startswith("pooler.")]      # the pooler is frozen and unused (T/run.py:67-69)
             if missing:     # a tower that silently keeps part of its random initialisation is a different experiment: refuse
                 raise SystemExit(f"text tower: {path} does not provide {len(missing)} parameter(s) of the tower, e.g. {missing[:4]}")
@@ -478,10 +505,12 @@ def _load_pretrained_text_tower(bert, args):
 
 def load_text_tokenizer(args):
     """The tokenizer of ``--bert_model_load`` from ``<pretrained_dir>/<bert_model_load>`` (``T/run.py:28-39``): ``RobertaTokenizer``
-    (``vocab.json`` + ``merges.txt``, pads with id 1) for a name containing 'roberta', ``BertTokenizer`` (``vocab.txt``) otherwise."""
+    (``vocab.json`` + ``merges.txt``, pads with id 1) for a name containing 'roberta', ``GPT2Tokenizer`` (the same two files; OPT's puts
+    ``</s>`` first and pads with id 1) for one containing 'opt' (``T/run.py:41-44``), ``BertTokenizer`` (``vocab.txt``) otherwise."""
     tok_dir = os.path.join(args.pretrained_dir, args.bert_model_load)
     roberta = "roberta" in args.bert_model_load
-    needed = ("vocab.json", "merges.txt") if roberta else ("vocab.txt",)
+    opt = not roberta and "opt" in args.bert_model_load
+    needed = ("vocab.json", "merges.txt") if (roberta or opt) else ("vocab.txt",)
     absent = [f for f in needed if not os.path.exists(os.path.join(tok_dir, f))]
     if absent:
         raise SystemExit(f"modal run on real data: no tokenizer vocabulary under {tok_dir}: {' and '.join(absent)} missing "
@@ -489,6 +518,9 @@ def load_text_tokenizer(args):
     if roberta:
         from transformers import RobertaTokenizer
         return RobertaTokenizer.from_pretrained(tok_dir)
+    if opt:
+        from transformers import GPT2Tokenizer
+        return GPT2Tokenizer.from_pretrained(tok_dir)
     from transformers import BertTokenizer
     return BertTokenizer.from_pretrained(tok_dir)
 
@@ -497,6 +529,16 @@ def build_text_tower(args, freeze=True):
     """The text tower of ``--bert_model_load`` with its pretrained weights (``T/run.py:51-75``); sets ``args.word_embedding_dim``.
     ``freeze``: the first ``freeze_paras_before`` parameters and the pooler do not train (stage 1 of the two-stage drivers runs the
     tower without gradients and leaves the flags alone)."""
+    if "opt" in args.bert_model_load and "roberta" not in args.bert_model_load:      # T/run.py:41-47: OPTModel, no pooler
+        shape = OptShape.named(args.bert_model_load)
+        args.word_embedding_dim = shape.hidden_size
+        bert = HipOPTModel(shape)
+        if freeze:
+            for index, (name, param) in enumerate(bert.named_parameters()):   # T/run.py:73-75, in the installed registration order
+                if index < args.freeze_paras_before:
+                    param.requires_grad = False
+        _load_pretrained_text_tower(bert, args, normalize=strip_model_prefix)
+        return bert
     shape = BertShape.named(args.bert_model_load)
     args.word_embedding_dim = shape.hidden_size
     bert = HipBertModel(shape)
@@ -540,7 +582,7 @@ def load_dataset(args, use_modal, vision):
                    if use_modal and not vision and n in args.news_attributes]
         item_num, content, users_train, users_valid, users_test, hist_valid, hist_test, pop = synthetic_dataset(
             args.synthetic, args.synthetic_items, S, T, full_len=bool(getattr(args, "synthetic_full_len", False)), extra_T=extra_T,
-            vocab=synthetic_vocab(args, use_modal and not vision))
+            vocab=synthetic_vocab(args, use_modal and not vision), opt=is_opt_run(args))
         item_content = content if use_modal else np.arange(item_num + 1)
         if vision:      # decoded uint8 images; a real run passes --images_npy (what the LMDB of V/data_utils holds after Resize)
             R = args.CV_resize
@@ -1164,6 +1206,7 @@ def main(argv=None):
     args = parse_args(argv)
     check_mae_args(args)
     check_beit_args(args)
+    check_opt_args(args)
     two_stage = check_two_stage_args(args)
     id_two_stage = check_id_two_stage_args(args)
     dssm = check_dssm_args(args)

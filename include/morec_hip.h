@@ -593,6 +593,30 @@ int morec_bert_embed_fwd_pos(const int32_t* ids, const int32_t* pos_ids, const f
 int morec_roberta_embed_bwd(const int32_t* ids, const void* dz, float* dword, float* dpos, float* dtype0, int pad_id, int M, int T,
                             int H, int dtype, const int32_t* order, const int32_t* perm, const int32_t* cnt, int pos_pad, int n_pos,
                             void* stream);
+/* OPT text tower (csrc/opt.hip; HF modeling_opt.py, the reference's Text_Encoder_mean).  None of the four uses atomics or LDS hand-offs
+ * between workgroups, every output element is written exactly once (no pre-zeroing), and every call computes the same bits in either
+ * setting of the deterministic mode.
+ * morec_mask_pos_ids: position ids counted from the attention MASK (OPTLearnedPositionalEmbedding), never from the ids.  mask int32
+ * [n_seq * T], nonzero = kept.  pos_ids[n*T + t] = offset + k for the k-th (from 0) kept token, offset - 1 for a masked one; cnt[n] =
+ * number of kept tokens; perm[n*T + k] = position of the k-th kept token for k < cnt[n], then the masked positions in order (what
+ * morec_roberta_embed_bwd walks with pos_pad = offset - 1).  Holes in the mask are legal.  One wavefront per sequence.  Null pointers,
+ * n_seq or T <= 0, offset - 1 < 0 or offset + T - 1 >= n_pos: MOREC_E_ARG before anything is launched. */
+int morec_mask_pos_ids(const int32_t* mask, int n_seq, int T, int offset, int n_pos, int32_t* pos_ids_out, int32_t* perm_out,
+                       int32_t* cnt_out, void* stream);
+/* out[m, :] = round(word[ids[m], :] + pos[pos_ids[m], :]): fp32 tables, one fp32 add, one rounding to dtype; 16-byte accesses.  No
+ * LayerNorm, token type or dropout (OPTDecoder).  H % (16 / sizeof(dtype)) != 0 or more than 256 vectors per row:
+ * MOREC_E_UNSUPPORTED; null pointers, M or H <= 0: MOREC_E_ARG; a base pointer off 16 bytes: MOREC_E_ALIGN. */
+int morec_opt_embed_fwd(const int32_t* ids, const int32_t* pos_ids, const float* word, const float* pos, void* out, int M, int H,
+                        int dtype, void* stream);
+/* Masked mean pooling (Text_Encoder_mean: sum(h * mask) / clamp(sum(mask), 1e-9)).  cu == NULL: the padded layout, title n owns rows
+ * n*T .. n*T + T - 1; otherwise the packed rows cu[n] .. cu[n+1] - 1.  keep: the fp32 per-row key mask of the attention kernels
+ * (nonzero = kept).  fwd: out[n, :] = (sum of the kept rows of x, fp32, in row order) / max(count, 1e-9), rounded once; a title
+ * without a kept row gives zeros.  bwd: dx[row, :] = keep[row] ? g[n, :] / count : 0, written for every row of every title.  The count
+ * is taken from keep, never from the packed length.  Errors as morec_opt_embed_fwd. */
+int morec_masked_mean_fwd(const void* x, const float* keep, const int32_t* cu, void* out, int n_seq, int T, int H, int dtype,
+                          void* stream);
+int morec_masked_mean_bwd(const void* g, const float* keep, const int32_t* cu, void* dx, int n_seq, int T, int H, int dtype,
+                          void* stream);
 /* out[r, :] = table[idx[r], :]  (fp32 table -> dtype out).  T/model/model.py:37 nn.Embedding lookup. */
 int morec_gather_rows(const float* table, const int32_t* idx, void* out, int R, int D, int dtype, void* stream);
 /* dtable[idx[r], :] += d[r, :] unless idx[r] == pad_id (padding_idx=0, T/model/model.py:27) */
