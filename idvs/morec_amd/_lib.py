@@ -193,6 +193,10 @@ _SIGS = {
     "morec_attn_bias_ws_bytes": (C.c_size_t, [C.POINTER(AttnDesc)]),
     "morec_attn_bias_fwd": (C.c_int, [C.POINTER(AttnDesc), _P, _P, _P, _P, _P]),
     "morec_attn_bias_bwd": (C.c_int, [C.POINTER(AttnDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "morec_disent_attn_ws_bytes": (C.c_size_t, [C.POINTER(AttnDesc)]),
+    "morec_disent_attn_fwd": (C.c_int, [C.POINTER(AttnDesc), _P, _P, _P, _P, _P, _P]),
+    "morec_disent_attn_bwd": (C.c_int, [C.POINTER(AttnDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "morec_rows_keep": (C.c_int, [_P, _P, C.c_long, C.c_int, C.c_int, _P]),
     "morec_beit_bias_expand": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "morec_beit_bias_reduce": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "morec_layerscale_res_fwd": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, C.c_long, C.c_int, C.c_int, _P]),

@@ -36,6 +36,12 @@ def _text_features_fn(enc: Bert_Encoder):
                 vecs.append(mean.float())
             return vecs[0] if len(vecs) == 1 else torch.mean(torch.stack(vecs, dim=1), dim=1)
         return run_opt
+    if getattr(te, "is_deberta", False):      # the DeBERTa tower: the [CLS] rows in front of fc (deberta_engine, features_only=True)
+        def run_deberta(news):
+            vecs = [te.encode(torch.narrow(news, 1, enc.attributes2start[name], enc.attributes2length[name]).contiguous(),
+                              features_only=True).float() for name in enc.newsname]
+            return vecs[0] if len(vecs) == 1 else torch.mean(torch.stack(vecs, dim=1), dim=1)
+        return run_deberta
     p = {n: t for n, t in te.named_parameters() if ".pooler." not in n}
     prep = engine.bert_prepare(p, c.num_hidden_layers, te.compute_dtype, "")
 

@@ -8,7 +8,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from . import beit_engine, engine, mae_engine, ops, opt_engine, swin_engine
+from . import beit_engine, deberta_engine, engine, mae_engine, ops, opt_engine, swin_engine
 
 
 def _zeros_like_params(names, params, skip=()):
@@ -176,6 +176,43 @@ class OptEncoderFn(torch.autograd.Function):
         grads = _zeros_like_params(names, [p[n] for n in names], skip=skip)
         with ops.fp32_gemm_mode(ctx.fp32_gemm):
             opt_engine.opt_backward(p, prep, saved, d_item.contiguous(), grads, prefix)
+            engine.WgradStream.join(d_item.device)
+        needs = ctx.needs[2:]
+        return (None, None) + tuple(grads.get(n) if nd else None for n, nd in zip(names, needs))
+
+
+class DebertaEncoderFn(torch.autograd.Function):
+    """``Text_Encoder.forward`` (``GELU(fc(hidden[:, 0]))``) over HF ``DebertaModel`` arithmetic (``deberta_engine``).  ``cfg = (names,
+    shape, dtype, prefix, drop, features_only)``.  The backward ends at the lowest trainable layer (``deberta_grad_from``) and forms
+    dPK / dPQ only in the layers ``deberta_pos_layers`` names; a frozen parameter's gradient is not handed out."""
+
+    @staticmethod
+    def forward(ctx, text, cfg, *params):
+        names, shape, dtype, prefix, drop, features_only = cfg
+        p = dict(zip(names, params))
+        need = any(ctx.needs_input_grad) and not features_only
+        prep = deberta_engine.deberta_prepare(p, shape, dtype, prefix, features_only=features_only)
+        trainable = [n for n, nd in zip(names, ctx.needs_input_grad[2:]) if nd]
+        grad_from = deberta_engine.deberta_grad_from(trainable, shape.num_hidden_layers, prefix)
+        pos_layers = deberta_engine.deberta_pos_layers(trainable, shape.num_hidden_layers, prefix)
+        out, saved = deberta_engine.deberta_forward(p, prep, shape, text, dtype, need, prefix, drop, features_only=features_only,
+                                                    grad_from=grad_from, pos_layers=pos_layers)
+        ctx.stuff = (p, prep, saved, names, prefix, shape)
+        ctx.needs = ctx.needs_input_grad
+        ctx.fp32_gemm = ops.FP32_GEMM
+        if features_only:
+            ctx.mark_non_differentiable(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_item):
+        p, prep, saved, names, prefix, shape = ctx.stuff
+        ctx.stuff = None
+        skip = {deberta_engine.deberta_layer_names(prefix, l) + "attention.self." + k for l in range(shape.num_hidden_layers)
+                for k in ("in_proj.weight", "q_bias", "v_bias")}
+        grads = _zeros_like_params(names, [p[n] for n in names], skip=skip)
+        with ops.fp32_gemm_mode(ctx.fp32_gemm):
+            deberta_engine.deberta_backward(p, prep, saved, d_item.contiguous(), grads, prefix)
             engine.WgradStream.join(d_item.device)
         needs = ctx.needs[2:]
         return (None, None) + tuple(grads.get(n) if nd else None for n, nd in zip(names, needs))

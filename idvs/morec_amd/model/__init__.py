@@ -6,6 +6,8 @@ from .beit import HipBeitForImageClassification  # noqa: F401
 from .mae import HipViTMAEModel  # noqa: F401
 from .opt import HipOPTModel  # noqa: F401
 from ..opt_engine import OptShape  # noqa: F401
+from .deberta import HipDebertaModel  # noqa: F401
+from ..deberta_engine import DebertaShape  # noqa: F401
 from .bce import BceModel  # noqa: F401  (drop-in for bce_text/main-end2end/model/model.py)
 from .dssm import DssmModel, MLP_Encoder  # noqa: F401  (drop-in for bce_text/main-end2end(DSSM)/model/model.py)
 from .two_stage import MLP_Layers, TwoStageModel  # noqa: F401  (drop-in for bce_text|bce_vision/main-2stage(SASRec)/model/model.py)

@@ -3,7 +3,7 @@ a user-id embedding through an MLP against ``1 + neg_num`` sampled item vectors 
 Constructor ``(args, user_num, item_num, use_modal, bert_model)``, ``forward(input_user, sample_items, bce_label)``, attributes
 ``user_embedding`` / ``user_encoder`` / ``bert_encoder`` | ``id_embedding`` + ``id_encoder`` / ``criterion``, identical ``state_dict``
 keys.  The MLPs are ``functional.MlpFn`` (the library's GEMMs), scoring, loss and their backward ``morec_dssm_bce_fwd/bwd``
-(``csrc/dssm.hip``).  The text tower is BERT or RoBERTa (``Bert_Encoder``, keyed on ``--bert_model_load``); the package's DeBERTa launcher and a vision DSSM are not built."""
+(``csrc/dssm.hip``).  The text tower is BERT, RoBERTa or DeBERTa (``Bert_Encoder``, keyed on ``--bert_model_load``; DeBERTa is this package's own launcher, ``run.py:26-31``); a vision DSSM is not built."""
 import torch
 from torch import nn
 from torch.nn.init import constant_, xavier_normal_

@@ -16,6 +16,8 @@ from .beit import HipBeitForImageClassification, check_beit_config
 from .mae import HipViTMAEModel
 from .opt import HipOPTModel
 from ..opt_engine import check_opt_config
+from .deberta import HipDebertaModel
+from ..deberta_engine import check_deberta_config
 from ..mae_engine import MAE_SEED_EVAL, MAE_SEED_TRAIN, mae_keep
 from .modules import TransformerEncoder
 
@@ -159,14 +161,28 @@ class User_Encoder(nn.Module):
 class Text_Encoder(nn.Module):
     def __init__(self, bert_model, item_embedding_dim, word_embedding_dim, compute_dtype=None, res32=None):
         super().__init__()
-        self.bert_model = bert_model if isinstance(bert_model, HipBertModel) else HipBertModel.from_hf(bert_model)
+        if isinstance(bert_model, (HipBertModel, HipDebertaModel)):
+            self.bert_model = bert_model
+        elif getattr(getattr(bert_model, "config", None), "model_type", "bert") in ("deberta", "deberta-v2"):
+            self.bert_model = HipDebertaModel.from_hf(bert_model)      # (v2 / v3: refused there, by name)
+        else:
+            self.bert_model = HipBertModel.from_hf(bert_model)
+        # the DeBERTa tower (deberta_engine): disentangled attention, padded layout; the *_res32 modes run it in the plain 16-bit type
+        self.is_deberta = isinstance(self.bert_model, HipDebertaModel)
         self.fc = nn.Linear(word_embedding_dim, item_embedding_dim)
         self.compute_dtype = compute_dtype or resolve_dtype()
         self.res32 = resolve_res32() if res32 is None else bool(res32)
         self.mask_value = FLT_MIN_MASK   # transformers >= 4.3x eager; set to -10000.0 for 4.20.1 behaviour
 
-    def encode(self, text, drop: DropCfg = NO_DROP):
+    def encode(self, text, drop: DropCfg = NO_DROP, features_only: bool = False):
         c = self.bert_model.config
+        if self.is_deberta:
+            check_deberta_config(c, text.shape[1] // 2)
+            names, params = zip(*self.named_parameters())
+            cfg = (names, self.bert_model.shape, self.compute_dtype, "", drop, features_only)
+            return F_.DebertaEncoderFn.apply(text, cfg, *params)
+        if features_only:
+            raise NotImplementedError("Text_Encoder.encode(features_only=True) is the DeBERTa tower's; BERT / RoBERTa: engine.bert_forward")
         named = [(n, p) for n, p in self.named_parameters() if ".pooler." not in n]
         names, params = zip(*named)
         cfg = (names, c.num_attention_heads, c.num_hidden_layers, self.compute_dtype, "", c.layer_norm_eps, self.mask_value,

@@ -1262,6 +1262,57 @@ def attn_bias_bwd(desc, qkv, key_keep, pos_bias, dctx, dbias=None, need_dpos=Tru
     return dqkv, dpos
 
 
+DISENT_T_MAX = 64      # longest sequence of morec_disent_attn_fwd / _bwd (csrc/deberta.hip)
+DISENT_DROP_TP = 64    # edge of the dropout stream's tile there, whatever T: element ((seq * heads + head) * 64 + i) * 64 + j
+
+
+def _disent_check(desc, qkv, key_keep, pk, pq):
+    _dev(qkv), _dev(key_keep), _dev(pk), _dev(pq)
+    H = desc.n_heads * desc.dh
+    if desc.T > DISENT_T_MAX:
+        raise _lib.MorecError(f"disentangled attention over {desc.T} positions: the kernels end at {DISENT_T_MAX} (MOREC_E_UNSUPPORTED)")
+    assert tuple(qkv.shape) == (desc.n_seq * desc.T, 3 * H) and code(qkv.dtype) == desc.dtype
+    assert key_keep.dtype == torch.float32 and tuple(key_keep.shape) == (desc.n_seq, desc.T)
+    assert tuple(pk.shape) == (2 * desc.T, H) and tuple(pq.shape) == (2 * desc.T, H) and pk.dtype == qkv.dtype and pq.dtype == qkv.dtype
+
+
+def disent_attn_fwd(desc, qkv, key_keep, pk, pq):
+    """DeBERTa's disentangled attention (``morec_disent_attn_fwd``): score (i, j) = (q_i.k_j + q_i.pk[i - j + T] + k_j.pq[i - j + T]) * scale,
+    REPLACED by ``mask_value`` where query or key is masked.  ``pk`` / ``pq``: [2 T, H] in the storage type, unscaled."""
+    _disent_check(desc, qkv, key_keep, pk, pq)
+    ctx = torch.empty((qkv.shape[0], qkv.shape[1] // 3), device=qkv.device, dtype=qkv.dtype)
+    check(_lib.lib().morec_disent_attn_fwd(C.byref(desc), _p(qkv), _p(key_keep), _p(pk), _p(pq), _p(ctx), _stream()), "morec_disent_attn_fwd")
+    return ctx
+
+
+def disent_attn_bwd(desc, qkv, key_keep, pk, pq, dctx, dbias=None, need_dpos=True):
+    """(dqkv, dpk, dpq).  ``dbias``: fp32 [3 H], accumulated into (column sums of dqkv).  ``dpk`` / ``dpq``: fp32 [2 T, H], written (row 0
+    is zero), or None with ``need_dpos=False`` (frozen position projections: no extra launch)."""
+    _disent_check(desc, qkv, key_keep, pk, pq)
+    _dev(dctx)
+    assert tuple(dctx.shape) == (qkv.shape[0], qkv.shape[1] // 3) and dctx.dtype == qkv.dtype
+    assert dbias is None or (dbias.dtype == torch.float32 and dbias.numel() == qkv.shape[1] and dbias.is_contiguous())
+    dqkv = torch.empty_like(qkv)
+    dpk = dpq = ws = None
+    nbytes = 0
+    if need_dpos:
+        dpk = torch.empty(pk.shape, device=qkv.device, dtype=torch.float32)
+        dpq = torch.empty_like(dpk)
+        nbytes = int(_lib.lib().morec_disent_attn_ws_bytes(C.byref(desc)))
+        ws = torch.empty(nbytes // 4, device=qkv.device, dtype=torch.float32)
+    check(_lib.lib().morec_disent_attn_bwd(C.byref(desc), _p(qkv), _p(key_keep), _p(pk), _p(pq), _p(dctx), _p(dqkv), _p(dbias), _p(dpk), _p(dpq),
+                                           _p(ws), nbytes, _stream()), "morec_disent_attn_bwd")
+    return dqkv, dpk, dpq
+
+
+def rows_keep_(x, keep):
+    """In place: the rows of ``x`` [M, N] whose ``keep`` entry (fp32 [M]) is zero become exact zeros (``morec_rows_keep``)."""
+    _dev(x), _dev(keep)
+    assert x.dim() == 2 and keep.dtype == torch.float32 and keep.numel() == x.shape[0]
+    check(_lib.lib().morec_rows_keep(_p(x), _p(keep), x.shape[0], x.shape[1], code(x.dtype), _stream()), "morec_rows_keep")
+    return x
+
+
 def layerscale_res_fwd(a, bias, lam, res, rowscale=None, rows_per_scale=0):
     """``res + rowscale[row / rows_per_scale] * (lam * (a + bias))``: fp32 arithmetic, one rounding."""
     _dev(a), _dev(res)

@@ -204,7 +204,30 @@ def is_opt_run(args) -> bool:
     ``Text_Encoder_mean`` (``'opt' in bert_model_load``, tested after ``'roberta'``, ``T/run.py:37-47``)."""
     name = str(getattr(args, "bert_model_load", ""))
     return ("modal" in str(args.item_tower) and str(getattr(args, "CV_model_load", "None")) == "None" and "opt" in name
-            and "roberta" not in name)
+            and "roberta" not in name and "deberta" not in name)
+
+
+def is_deberta_run(args) -> bool:
+    """A run whose item tower is the DeBERTa text tower: a text tower (modal or fusion) whose ``--bert_model_load`` contains 'deberta'
+    (``bce_text/main-end2end(DSSM)/run.py:26-31``; tested before 'roberta' and 'opt')."""
+    tower = str(args.item_tower)
+    text = "modal" in tower or "add" in tower or "cat" in tower
+    return text and str(getattr(args, "CV_model_load", "None")) == "None" and "deberta" in str(getattr(args, "bert_model_load", ""))
+
+
+def check_deberta_args(args):
+    """What the DeBERTa tower does not run with: exits with the reason (before anything touches a device).  True for a DeBERTa run."""
+    if not is_deberta_run(args):
+        return False
+    why = None
+    if getattr(args, "fused_step", False):
+        why = ("--fused_step" + (" --pool_negatives" if getattr(args, "pool_negatives", False) else "") +
+               ": train_step.TrainStep covers the BERT / RoBERTa, ID and Swin towers; the DeBERTa tower trains on the drop-in autograd path")
+    elif getattr(args, "graph", False):
+        why = "--graph replays the fused step (train_step.TrainStep), which the DeBERTa tower does not use"
+    if why:
+        raise SystemExit(f"--bert_model_load {args.bert_model_load} (DeBERTa text tower): " + why)
+    return True
 
 
 def check_opt_args(args):

@@ -44,8 +44,10 @@ from .beit_engine import BeitShape
 from .mae_engine import MaeShape
 from .model.opt import HipOPTModel, strip_model_prefix
 from .opt_engine import OptShape
-from .parameters import (check_beit_args, check_dssm_args, check_fusion_args, check_id_two_stage_args, check_mae_args, check_opt_args, check_two_stage_args,
-                         is_beit_run, is_mae_run, is_opt_run, parse_args)
+from .model.deberta import HipDebertaModel, strip_deberta_prefix
+from .deberta_engine import DebertaShape
+from .parameters import (check_beit_args, check_deberta_args, check_dssm_args, check_fusion_args, check_id_two_stage_args, check_mae_args, check_opt_args,
+                         check_two_stage_args, is_beit_run, is_deberta_run, is_mae_run, is_opt_run, parse_args)
 from . import engine
 from .train_step import TrainStep
 from .lr_schedule import AutogradStepControl, schedule_from_args
@@ -63,6 +65,8 @@ def setup_seed(seed):   # T/run.py:307-314
 
 def synthetic_vocab(args, text):
     """Token ids of a ``--synthetic`` text catalogue must be rows of the tower's word table: its vocabulary size (30522 otherwise)."""
+    if text and is_deberta_run(args):
+        return DebertaShape.named(args.bert_model_load).vocab_size
     if text and is_opt_run(args):
         return OptShape.named(args.bert_model_load).vocab_size
     return BertShape.named(args.bert_model_load).vocab_size if text else 30522
@@ -80,13 +84,26 @@ def _synthetic_opt_titles(rng, n_items, T, vocab):
     return toks, valid
 
 
-def synthetic_dataset(n_users, n_items, S, T, seed=12345, full_len=False, extra_T=(), vocab=30522, opt=False):
+def _synthetic_deberta_titles(rng, n_items, T, vocab):
+    """[ids | mask] of DeBERTa titles as DebertaTokenizer lays them out: ``[CLS]`` (1) first, ``[SEP]`` (2) last, ids inside the
+    vocabulary, right-padded with 0 under mask 0."""
+    assert vocab > 4, "the DeBERTa ids 0 .. 2 are special tokens"
+    tl = rng.integers(min(8, T), T + 1, n_items)
+    toks = rng.integers(3, vocab, (n_items, T))
+    valid = np.arange(T)[None, :] < tl[:, None]
+    toks = np.where(valid, toks, 0)
+    toks[np.arange(n_items), tl - 1] = 2
+    toks[:, 0] = 1
+    return toks, valid
+
+
+def synthetic_dataset(n_users, n_items, S, T, seed=12345, full_len=False, extra_T=(), vocab=30522, opt=False, deberta=False):
     """MIND-shaped synthetic data in the structures ``read_behaviors`` / ``get_doc_input_bert`` return.
     ``full_len``: every user has raw history S + 3 (train sequence of S + 1 items: the throughput shape of bench.py).
     ``extra_T``: token counts of further text attributes (abstract, body: ``--news_attributes title,abstract``); their [ids | mask]
     blocks follow the title's in the item rows, as ``get_doc_input_bert`` + ``T/run.py:86-90`` lay them out.
     ``vocab``: token ids stay below it (a micro tower has 512 word rows; 1000 .. 30521 as before for the full vocabularies)."""
-    assert opt or vocab > 102, "the synthetic titles use the ids 101 / 102"
+    assert opt or deberta or vocab > 102, "the synthetic titles use the ids 101 / 102"
     lo_tok = 1000 if vocab > 2000 else 103
     rng = np.random.default_rng(seed)
     w = 1.0 / np.arange(1, n_items + 1)
@@ -103,11 +120,12 @@ def synthetic_dataset(n_users, n_items, S, T, seed=12345, full_len=False, extra_
     counts[1:] += 1e-9
     pop = np.append([1], counts[1:] / counts[1:].sum())
     content = np.zeros((n_items + 1, 2 * T), dtype=np.int64)
-    if opt:      # (row 0, the padding item, stays all-zero ids under an all-zero mask, as get_doc_input_bert leaves it)
+    if opt or deberta:      # (row 0, the padding item, stays all-zero ids under an all-zero mask, as get_doc_input_bert leaves it)
         blocks = []
+        titles = _synthetic_deberta_titles if deberta else _synthetic_opt_titles
         for Tx in (T,) + tuple(extra_T):
             blk = np.zeros((n_items + 1, 2 * Tx), dtype=np.int64)
-            blk[1:, :Tx], blk[1:, Tx:] = _synthetic_opt_titles(rng, n_items, Tx, vocab)
+            blk[1:, :Tx], blk[1:, Tx:] = titles(rng, n_items, Tx, vocab)
             blocks.append(blk)
         return n_items, np.concatenate(blocks, axis=1), users_train, users_valid, users_test, hist_valid, hist_test, pop
     tl = rng.integers(8, T + 1, n_items)
@@ -360,6 +378,7 @@ def synthetic_new_item_docs(args, item_num, n_new=12, seed=1357, vocab=30522):
     rng = np.random.default_rng(seed)
     lo_tok = 1000 if vocab > 2000 else 103
     opt = is_opt_run(args)      # </s> first, ids inside the vocabulary, right-padded with 1
+    deberta = is_deberta_run(args)      # [CLS] = 1 ... [SEP] = 2, ids inside the vocabulary, right-padded with 0
     docs = {}
     for k in range(n_new):
         enc = []
@@ -368,7 +387,9 @@ def synthetic_new_item_docs(args, item_num, n_new=12, seed=1357, vocab=30522):
                 enc.append([])
                 continue
             L = int(rng.integers(3, T + 1))
-            if opt:
+            if deberta:
+                ids = [1] + [int(v) for v in rng.integers(3, vocab, L - 2)] + [2] + [0] * (T - L)
+            elif opt:
                 ids = [2] + [int(v) for v in rng.integers(3, vocab, L - 1)] + [1] * (T - L)
             else:
                 ids = [101] + [int(v) for v in rng.integers(lo_tok, vocab, L - 2)] + [102] + [0] * (T - L)
@@ -506,15 +527,21 @@ def _load_pretrained_text_tower(bert, args, normalize=None):
 def load_text_tokenizer(args):
     """The tokenizer of ``--bert_model_load`` from ``<pretrained_dir>/<bert_model_load>`` (``T/run.py:28-39``): ``RobertaTokenizer``
     (``vocab.json`` + ``merges.txt``, pads with id 1) for a name containing 'roberta', ``GPT2Tokenizer`` (the same two files; OPT's puts
-    ``</s>`` first and pads with id 1) for one containing 'opt' (``T/run.py:41-44``), ``BertTokenizer`` (``vocab.txt``) otherwise."""
+    ``</s>`` first and pads with id 1) for one containing 'opt' (``T/run.py:41-44``), ``DebertaTokenizer`` (the same two files, pads with
+    id 0; ``bce_text/main-end2end(DSSM)/run.py:26-31``) for one containing 'deberta' -- tested first --, ``BertTokenizer`` (``vocab.txt``)
+    otherwise."""
     tok_dir = os.path.join(args.pretrained_dir, args.bert_model_load)
-    roberta = "roberta" in args.bert_model_load
-    opt = not roberta and "opt" in args.bert_model_load
-    needed = ("vocab.json", "merges.txt") if (roberta or opt) else ("vocab.txt",)
+    deberta = "deberta" in args.bert_model_load
+    roberta = not deberta and "roberta" in args.bert_model_load
+    opt = not deberta and not roberta and "opt" in args.bert_model_load
+    needed = ("vocab.json", "merges.txt") if (deberta or roberta or opt) else ("vocab.txt",)
     absent = [f for f in needed if not os.path.exists(os.path.join(tok_dir, f))]
     if absent:
         raise SystemExit(f"modal run on real data: no tokenizer vocabulary under {tok_dir}: {' and '.join(absent)} missing "
                          f"(--pretrained_dir / --bert_model_load; the tokenizer of this tower reads {' + '.join(needed)})")
+    if deberta:
+        from transformers import DebertaTokenizer
+        return DebertaTokenizer.from_pretrained(tok_dir)
     if roberta:
         from transformers import RobertaTokenizer
         return RobertaTokenizer.from_pretrained(tok_dir)
@@ -529,6 +556,16 @@ def build_text_tower(args, freeze=True):
     """The text tower of ``--bert_model_load`` with its pretrained weights (``T/run.py:51-75``); sets ``args.word_embedding_dim``.
     ``freeze``: the first ``freeze_paras_before`` parameters and the pooler do not train (stage 1 of the two-stage drivers runs the
     tower without gradients and leaves the flags alone)."""
+    if "deberta" in args.bert_model_load:      # bce_text/main-end2end(DSSM)/run.py:26-31: DebertaModel, no pooler; tested before roberta / opt
+        shape = DebertaShape.named(args.bert_model_load)
+        args.word_embedding_dim = shape.hidden_size
+        bert = HipDebertaModel(shape, name=str(args.bert_model_load))
+        if freeze:
+            for index, (name, param) in enumerate(bert.named_parameters()):   # in the installed registration order: rel_embeddings is last
+                if index < args.freeze_paras_before:
+                    param.requires_grad = False
+        _load_pretrained_text_tower(bert, args, normalize=strip_deberta_prefix)
+        return bert
     if "opt" in args.bert_model_load and "roberta" not in args.bert_model_load:      # T/run.py:41-47: OPTModel, no pooler
         shape = OptShape.named(args.bert_model_load)
         args.word_embedding_dim = shape.hidden_size
@@ -582,7 +619,7 @@ def load_dataset(args, use_modal, vision):
                    if use_modal and not vision and n in args.news_attributes]
         item_num, content, users_train, users_valid, users_test, hist_valid, hist_test, pop = synthetic_dataset(
             args.synthetic, args.synthetic_items, S, T, full_len=bool(getattr(args, "synthetic_full_len", False)), extra_T=extra_T,
-            vocab=synthetic_vocab(args, use_modal and not vision), opt=is_opt_run(args))
+            vocab=synthetic_vocab(args, use_modal and not vision), opt=is_opt_run(args), deberta=is_deberta_run(args))
         item_content = content if use_modal else np.arange(item_num + 1)
         if vision:      # decoded uint8 images; a real run passes --images_npy (what the LMDB of V/data_utils holds after Resize)
             R = args.CV_resize
@@ -965,7 +1002,7 @@ def train_dssm(args, use_modal, local_rank):
         extra_T = [w for n, w in (("abstract", args.num_words_abstract), ("body", args.num_words_body)) if use_modal and n in args.news_attributes]
         item_num, content, tr, _, te, _, _, _ = synthetic_dataset(args.synthetic, args.synthetic_items, S, T,
                                                                  full_len=bool(getattr(args, "synthetic_full_len", False)), extra_T=extra_T,
-                                                                 vocab=synthetic_vocab(args, use_modal))
+                                                                 vocab=synthetic_vocab(args, use_modal), deberta=use_modal and is_deberta_run(args))
         seqs = [list(tr[u]) + list(te[u][-2:]) for u in range(args.synthetic)]      # the raw sequences (at most S + 3 items), split by the DSSM rule
         users_train, _, train_pairs, valid_pairs, test_pairs, hist_valid, hist_test = dd.pairs_from_sequences(seqs)
         user_num = len(seqs)
@@ -1207,6 +1244,7 @@ def main(argv=None):
     check_mae_args(args)
     check_beit_args(args)
     check_opt_args(args)
+    check_deberta_args(args)
     two_stage = check_two_stage_args(args)
     id_two_stage = check_id_two_stage_args(args)
     dssm = check_dssm_args(args)

@@ -531,6 +531,39 @@ int morec_beit_pool_bwd(const void* dpool, void* dx, int n_img, int T, int C, in
 int morec_beit_assemble_fwd(const void* e, const float* cls_token, void* x, int n_img, int N, int C, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DeBERTa's disentangled self-attention (HF modeling_deberta.py DisentangledSelfAttention with pos_att_type c2p + p2c; csrc/deberta.hip),
+ * T <= 64 (titles): morec_attn_fwd / _bwd with two position terms on every score,
+ *     score[i][j] = (q_i . k_j + q_i . PK_h[d] + k_j . PQ_h[d]) * scale,   d = i - j + T  (1 .. 2T-1: row 0 of PK / PQ is never read),
+ * `scale` = 1 / sqrt(3 dh) applied once to the fp32 sum.  A score whose query OR key is masked (key_keep[n][i] == 0 or key_keep[n][j] == 0)
+ * is REPLACED by `mask_value` (a finite value: finfo.min), not added to -- a query row without a kept key is the uniform average of all T
+ * value rows -- and takes no gradient.  Then softmax, dropout on P (p_drop > 0: element index ((seq * n_heads + head) * 64 + i) * 64 + j,
+ * TP = 64 for every T), ctx = P V.  The descriptor is the plain one; causal != 0, cu_seqlens != NULL and T > 64 return
+ * MOREC_E_UNSUPPORTED, and the descriptor is judged before any pointer (null: MOREC_E_ARG).
+ *
+ * LAYOUT: qkv [n_seq * T, 3 H] = [Q | K | V] with the projection biases already added; key_keep fp32 [n_seq, T]; PK = pos_proj(R) and
+ * PQ = pos_q_proj(R) [2 T, H] in the storage type, unscaled, row d = relative position d - T, the head's columns at h * dh as in Q;
+ * the same for every sequence.  ctx [n_seq * T, H].
+ *
+ * Two paths: mfma16 (bf16 / fp16 storage, dh % 32 == 0, dh <= 128: every product on v_mfma_f32_16x16x32_{bf16,f16}) and gen (fp32 storage
+ * or other head widths: fp32 FMAs).  One workgroup per (sequence, head); Q PK^T and K PQ^T are formed once as [T x 2T] fp32 tiles in LDS.
+ *
+ * Backward: dqkv as morec_attn_bwd.  dqkv_bias (fp32 [3 H], may be NULL) += the column sums of dqkv.  dPK, dPQ (fp32 [2 T, H], both or
+ * neither NULL = frozen position projections: nothing more is launched) are WRITTEN, row 0 as zero:
+ *     dPK_h[d] = sum_seq sum_{i-j+T=d} dS[i][j] q_i * scale,   dPQ_h[d] = sum_seq sum_{i-j+T=d} dS[i][j] k_j * scale.
+ * They need ws of morec_disent_attn_ws_bytes(desc) bytes (8 partial pairs; too small or NULL: MOREC_E_ARG): the sequences are cut into 8
+ * chunks of ceil(n_seq / 8), a workgroup per (chunk, head) adds its sequences' contributions in index order in fp32, and the partials of
+ * the chunks that hold a sequence are added in chunk order.  No atomics in these kernels, every output written once, two calls on the
+ * same inputs give the same bits.  morec_disent_attn_ws_bytes returns 0 for a descriptor the entry points refuse. */
+size_t morec_disent_attn_ws_bytes(const morec_attn_desc* desc);
+int morec_disent_attn_fwd(const morec_attn_desc* desc, const void* qkv, const float* key_keep, const void* PK, const void* PQ, void* ctx,
+                          void* stream);
+int morec_disent_attn_bwd(const morec_attn_desc* desc, const void* qkv, const float* key_keep, const void* PK, const void* PQ,
+                          const void* dctx, void* dqkv, float* dqkv_bias, float* dPK, float* dPQ, float* ws, size_t ws_bytes, void* stream);
+/* DebertaEmbeddings' `embeddings * mask` (modeling_deberta.py), in place: row m of x [M, N] becomes exact zeros where keep[m] == 0 and is
+ * left as it is elsewhere.  Its own backward (the mask applied to the gradient). */
+int morec_rows_keep(void* x, const float* keep, long M, int N, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * BCE variant, one sampled negative per position (bce_text/main-end2end/model/model.py:30-51).
  * E [B, S+1, 2, D] item vectors (pos at [:, :, 0], neg at [:, :, 1]), P [B, S, D] user states, row_valid u8 [B*S].
  * scores fp32 [2][B*S] (pos | neg) are saved for the backward; loss_sum[0] += sum_valid softplus(-pos) + softplus(neg).
