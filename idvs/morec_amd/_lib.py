@@ -204,6 +204,21 @@ _SIGS = {
     "morec_beit_pool_fwd": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "morec_beit_pool_bwd": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "morec_beit_assemble_fwd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "morec_conv2d_uses_mfma": (C.c_int, [C.c_int, C.c_int]),
+    "morec_conv2d_fwd": (C.c_int, [_P, _P, _P] + [C.c_int] * 10 + [_P]),
+    "morec_conv2d_bwd_data": (C.c_int, [_P, _P, _P] + [C.c_int] * 10 + [_P]),
+    "morec_im2col_nhwc": (C.c_int, [_P, _P] + [C.c_int] * 12 + [_P]),
+    "morec_bn_slab_rows": (C.c_int, []),
+    "morec_bn_stats": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "morec_bn_merge": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P]),
+    "morec_bn_rstd": (C.c_int, [_P, _P, C.c_int, C.c_float, _P]),
+    "morec_bn_apply_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "morec_bn_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "morec_bn_bwd_reduce": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "morec_bn_bwd_apply": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "morec_maxpool3x3s2_fwd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "morec_maxpool3x3s2_bwd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "morec_pixels_to_nhwc": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P]),
     "morec_image_resize_u8": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P]),
     "morec_comm_available": (C.c_int, []),
     "morec_comm_unique_id": (C.c_int, [_P]),

@@ -14,8 +14,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .. import beit_engine, engine, mae_engine, ops, opt_engine, swin_engine
-from ..model.encoders import Bert_Encoder, MAE_Encoder, Text_Encoder_mean, Vit_Encoder, resolve_fp32_gemm
+from .. import beit_engine, engine, mae_engine, ops, opt_engine, resnet_engine, swin_engine
+from ..model.encoders import Bert_Encoder, MAE_Encoder, Resnet_Encoder, Text_Encoder_mean, Vit_Encoder, resolve_fp32_gemm
 from .dataset import collate_bce_batch
 from .metrics import _module
 
@@ -86,6 +86,19 @@ def _mae_features_fn(enc: MAE_Encoder):
     return run
 
 
+def _resnet_features_fn(enc):
+    p = dict(enc.named_parameters())
+    bufs = dict(enc.named_buffers())
+    shape = enc.image_net.shape
+    prep = resnet_engine.resnet_prepare(p, shape, enc.compute_dtype, "image_net.", need_grad=False, features_only=True)
+
+    def run(pixels):      # evaluation mode: the running statistics, so the catalogue may be chunked
+        pooled, _ = resnet_engine.resnet_forward(p, bufs, prep, shape, pixels, enc.compute_dtype, False, "image_net.", training=False,
+                                                 features_only=True)
+        return pooled.float()
+    return run
+
+
 def extract_item_features(encoder, item_content, batch_size, device=None):
     """Stage 1: ``encoder`` (a ``Bert_Encoder`` or a ``Vit_Encoder``) in eval mode, without gradients or saved activations, over every
     catalogue row of ``item_content`` (token rows ``[item_num + 1, 2T...]``; images as a float ``[n, 3, R, R]`` / uint8 ``[n, R, R, 3]``
@@ -99,6 +112,8 @@ def extract_item_features(encoder, item_content, batch_size, device=None):
         run, mode = _text_features_fn(enc), resolve_fp32_gemm(enc.args)
     elif isinstance(enc, Vit_Encoder):
         run, mode = _vision_features_fn(enc), ops.FP32_GEMM
+    elif isinstance(enc, Resnet_Encoder):      # the globally pooled rows in front of fc
+        run, mode = _resnet_features_fn(enc), ops.FP32_GEMM
     elif isinstance(enc, MAE_Encoder):      # the normalised [CLS] rows in front of cv_proj (image_net(x)[0][:, 0]): this project's definition
         run, mode = _mae_features_fn(enc), ops.FP32_GEMM
     else:

@@ -8,7 +8,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from . import beit_engine, deberta_engine, engine, mae_engine, ops, opt_engine, swin_engine
+from . import beit_engine, deberta_engine, engine, mae_engine, ops, opt_engine, resnet_engine, swin_engine
 
 
 def _zeros_like_params(names, params, skip=()):
@@ -246,6 +246,35 @@ class BeitEncoderFn(torch.autograd.Function):
         grads = _zeros_like_params(names, [p[n] for n in names], skip=skip)
         with ops.fp32_gemm_mode(ctx.fp32_gemm):
             beit_engine.beit_backward(p, prep, saved, d_item.contiguous(), grads, prefix)
+            engine.WgradStream.join(d_item.device)
+        return (None, None) + tuple(grads.get(n) if nd else None for n, nd in zip(names, needs))
+
+
+class ResNetEncoderFn(torch.autograd.Function):
+    """``Resnet_Encoder.forward`` (``V/model/encoders.py:40-41``) over torchvision ``ResNet`` arithmetic.  ``cfg = (names, shape, dtype,
+    prefix, bufs, training)``: ``bufs`` are the BatchNorm buffers by name (training mode updates the running statistics in place).  A frozen
+    parameter gets no buffer: a frozen convolution skips its weight gradient, a frozen BatchNorm still normalises with batch statistics."""
+
+    @staticmethod
+    def forward(ctx, pixels, cfg, *params):
+        names, shape, dtype, prefix, bufs, training = cfg
+        p = dict(zip(names, params))
+        need = any(ctx.needs_input_grad)
+        prep = resnet_engine.resnet_prepare(p, shape, dtype, prefix, need_grad=need)
+        item, saved = resnet_engine.resnet_forward(p, bufs, prep, shape, pixels, dtype, need, prefix, training)
+        ctx.stuff = (p, prep, saved, names, prefix)
+        ctx.needs = ctx.needs_input_grad
+        ctx.fp32_gemm = ops.FP32_GEMM
+        return item
+
+    @staticmethod
+    def backward(ctx, d_item):
+        p, prep, saved, names, prefix = ctx.stuff
+        ctx.stuff = None
+        needs = ctx.needs[2:]
+        grads = _zeros_like_params(names, [p[n] for n in names], skip={n for n, nd in zip(names, needs) if not nd})
+        with ops.fp32_gemm_mode(ctx.fp32_gemm):
+            resnet_engine.resnet_backward(p, prep, saved, d_item.contiguous(), grads, prefix)
             engine.WgradStream.join(d_item.device)
         return (None, None) + tuple(grads.get(n) if nd else None for n, nd in zip(names, needs))
 

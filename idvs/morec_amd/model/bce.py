@@ -10,7 +10,7 @@ from torch import nn
 from torch.nn.init import xavier_normal_
 
 from .. import engine, ops
-from .encoders import (Bert_Encoder, IdEmbedding, MAE_Encoder, User_Encoder, Vit_Encoder, fusion_tower, is_mae_name, make_fusion, resolve_dtype, resolve_fp32_gemm,
+from .encoders import (Bert_Encoder, IdEmbedding, MAE_Encoder, Resnet_Encoder, User_Encoder, Vit_Encoder, fusion_tower, is_mae_name, make_fusion, resolve_dtype, resolve_fp32_gemm,
                        resolve_res32)
 
 
@@ -47,14 +47,19 @@ class BceModel(nn.Module):
         self.user_encoder = User_Encoder(item_num=item_num, max_seq_len=args.max_seq_len, item_dim=args.embedding_dim,
                                          num_attention_heads=args.num_attention_heads, dropout=args.drop_rate,
                                          n_layers=args.transformer_block, compute_dtype=self.compute_dtype, res32=resolve_res32(args))
-        # the vision twin (bce_vision/main-end2end/model/model.py): the MAE and BEiT towers; Swin under this loss is not built
+        # the vision twin (bce_vision/main-end2end/model/model.py): the ResNet, MAE and BEiT towers; Swin under this loss is not built
         self.vision = bool(self.use_modal and getattr(args, "CV_model_load", "None") not in ("None", None))
         if self.vision:
             cv = args.CV_model_load
-            if "swin" in cv or "resnet" in cv or not ("beit" in cv or is_mae_name(cv)):
-                raise NotImplementedError(f"BceModel: CV_model_load {cv!r}: only the MAE and BEiT towers are built for the BCE loss (Swin "
-                                          "runs under the in-batch loss; ResNet is not implemented)")
-            if "beit" in cv:
+            if "swin" in cv or not ("resnet" in cv or "beit" in cv or is_mae_name(cv)):
+                raise NotImplementedError(f"BceModel: CV_model_load {cv!r}: only the ResNet, MAE and BEiT towers are built for the BCE loss "
+                                          "(Swin runs under the in-batch loss)")
+            if "resnet" in cv:      # bce_vision/main-end2end/model/model.py:23-24
+                if bert_model is None:
+                    raise NotImplementedError("ResNet tower: BceModel needs the image network (a HipResNet, or a module with torchvision's "
+                                              "ResNet keys) as its fourth argument")
+                self.cv_encoder = Resnet_Encoder(image_net=bert_model, compute_dtype=self.compute_dtype)
+            elif "beit" in cv:
                 self.cv_encoder = Vit_Encoder(image_net=bert_model, compute_dtype=self.compute_dtype, family="beit")
             else:
                 self.cv_encoder = MAE_Encoder(image_net=bert_model, item_dim=args.embedding_dim, compute_dtype=self.compute_dtype)

@@ -14,6 +14,7 @@ from .bert import HipBertModel
 from .swin import HipSwinForImageClassification
 from .beit import HipBeitForImageClassification, check_beit_config
 from .mae import HipViTMAEModel
+from .resnet import HipResNet
 from .opt import HipOPTModel
 from ..opt_engine import check_opt_config
 from .deberta import HipDebertaModel
@@ -282,6 +283,26 @@ class Vit_Encoder(nn.Module):
 
     def forward(self, item_content, interpolate_pos_encoding: bool = False):
         return self.encode(item_content, interpolate_pos_encoding=interpolate_pos_encoding).float()
+
+
+class Resnet_Encoder(nn.Module):
+    """``V/model/encoders.py:34-41``: ``GELU(image_net(item_content))`` with ``image_net`` a torchvision ``ResNet`` whose ``fc`` was
+    replaced by ``Linear(num_fc_ftr, embedding_dim)`` (``V/run.py:38-46``): a ``HipResNet`` container, or any module with torchvision's
+    ResNet keys (``HipResNet.from_torch``).  The GELU is the epilogue of the ``fc`` product.  Training mode normalises with the statistics
+    of the whole call and updates the running statistics; evaluation mode applies the running statistics."""
+
+    def __init__(self, image_net, compute_dtype=None):
+        super().__init__()
+        self.image_net = image_net if isinstance(image_net, HipResNet) else HipResNet.from_torch(image_net)
+        self.compute_dtype = compute_dtype or resolve_dtype()
+
+    def encode(self, item_content, drop: DropCfg = NO_DROP):
+        names, params = zip(*self.named_parameters())
+        cfg = (names, self.image_net.shape, self.compute_dtype, "image_net.", dict(self.named_buffers()), self.training)
+        return F_.ResNetEncoderFn.apply(item_content, cfg, *params)
+
+    def forward(self, item_content):
+        return self.encode(item_content).float()
 
 
 def is_mae_name(name) -> bool:

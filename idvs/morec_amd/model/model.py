@@ -12,7 +12,7 @@ from torch.nn.init import xavier_normal_
 
 from .. import engine, ops
 from .. import functional as F_
-from .encoders import (Bert_Encoder, IdEmbedding, MAE_Encoder, User_Encoder, Vit_Encoder, fusion_tower, is_mae_name, make_fusion, resolve_dtype,
+from .encoders import (Bert_Encoder, IdEmbedding, MAE_Encoder, Resnet_Encoder, User_Encoder, Vit_Encoder, fusion_tower, is_mae_name, make_fusion, resolve_dtype,
                        resolve_fp32_gemm, resolve_res32)
 
 
@@ -44,11 +44,15 @@ class Model(nn.Module):
                 self.cv_encoder = Vit_Encoder(image_net=bert_model, compute_dtype=self.compute_dtype)
             elif "beit" in args.CV_model_load:      # V/model/model.py:26-27: the same encoder class over a BEiT classifier
                 self.cv_encoder = Vit_Encoder(image_net=bert_model, compute_dtype=self.compute_dtype, family="beit")
-            elif "resnet" not in args.CV_model_load and is_mae_name(args.CV_model_load):
+            elif "resnet" in args.CV_model_load:      # V/model/model.py:24-25 (the reference tests this name first; no other name contains it)
+                if bert_model is None:
+                    raise NotImplementedError("ResNet tower: Model needs the image network (a HipResNet, or a module with torchvision's "
+                                              "ResNet keys) as its fourth argument; there is none to build from a name alone")
+                self.cv_encoder = Resnet_Encoder(image_net=bert_model, compute_dtype=self.compute_dtype)
+            elif is_mae_name(args.CV_model_load):
                 self.cv_encoder = MAE_Encoder(image_net=bert_model, item_dim=args.embedding_dim, compute_dtype=self.compute_dtype)
             else:
-                raise NotImplementedError("only the Swin, BEiT and MAE towers of V/model/model.py:24-29 are implemented (the ResNet "
-                                          "launchers are outside the benchmarked path)")
+                raise NotImplementedError("only the ResNet, Swin, BEiT and MAE towers of V/model/model.py:24-29 are implemented")
         elif self.use_modal:
             self.bert_encoder = Bert_Encoder(args=args, bert_model=bert_model)
         # ID (+) modality fusion (bce_text/id_plus_mo-end2end/model/model.py:23-39, here under the in-batch loss too): the model then owns

@@ -286,17 +286,19 @@ def mlp_dact_recompute(dy, w2t, x, w1, b1, colsum_out=None):
 _TN_WS = {}
 
 
-def gemm_tn_(dy, x, out, split_m=1, accumulate=True, slabs=True, stream=None):
+def gemm_tn_(dy, x, out, split_m=1, accumulate=True, slabs=True, stream=None, ws_cache=None):
     """out[N, K] (+)= dy[M, N]^T @ x[M, K] (bf16 operands, fp32 out) without transposed copies.  ``slabs``: reduce the
     split-m partials through a reusable fp32 workspace (deterministic) instead of fp32 atomics.  ``stream``: raw handle of the stream to
-    launch on (default: torch's current stream) -- the weight-gradient stream, without a ``torch.cuda.stream`` context per launch."""
+    launch on (default: torch's current stream) -- the weight-gradient stream, without a ``torch.cuda.stream`` context per launch.
+    ``ws_cache``: the per-device slab workspace to use instead of the shared one (launches of ONE stream share a workspace: a caller on
+    another stream than the weight-gradient stream brings its own)."""
     _dev(dy), _dev(x)
     M, N = dy.shape
     K = x.shape[1]
     ws = None
     if slabs and split_m > 1:
         need = _lib.lib().morec_gemm_tn_workspace_bytes(N, K, split_m) // 4
-        ws = _scratch(_TN_WS, dy.device, need, 20 * 1024 * 1024)
+        ws = _scratch(_TN_WS if ws_cache is None else ws_cache, dy.device, need, 20 * 1024 * 1024)
     check(_lib.lib().morec_gemm_tn(_p(dy), _p(x), _p(out), M, N, K, dy.stride(0), x.stride(0), out.stride(0), code(dy.dtype),
                                    split_m, int(accumulate), _p(ws), _stream() if stream is None else stream), "morec_gemm_tn")
     return out
@@ -1402,3 +1404,143 @@ def image_resize_u8(images, R: int, device=None):
         raise _lib.MorecError("libmorec_hip needs device tensors (no CPU fallback)")
     flat, meta, tabs = pack_images(images, R)
     return image_resize_u8_packed(torch.from_numpy(flat).pin_memory(), torch.from_numpy(meta), torch.from_numpy(tabs), R, device)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# The ResNet item tower (csrc/conv.hip, csrc/resnet.hip): NHWC activations as [N H W, C] rows.
+def conv_out_size(H: int, K: int, stride: int, pad: int) -> int:
+    return (H + 2 * pad - K) // stride + 1
+
+
+def conv2d_uses_mfma(reduction_channels: int, dtype) -> bool:
+    """Does a convolution of this storage type and reduction channel count (Cin forward, Cout for the data gradient) run on the
+    matrix cores?  Otherwise it runs the fp32-FMA kernel."""
+    return bool(_lib.lib().morec_conv2d_uses_mfma(int(reduction_channels), code(dtype)))
+
+
+def conv2d_fwd(x, w, N, H, W, stride, pad):
+    """x [N H W, Cin] rows, w [Cout, KH, KW, Cin] (both the storage type) -> [N Ho Wo, Cout]."""
+    _dev(x), _dev(w)
+    Cout, KH, KW, Cin = w.shape
+    assert x.shape == (N * H * W, Cin) and x.dtype == w.dtype
+    Ho, Wo = conv_out_size(H, KH, stride, pad), conv_out_size(W, KW, stride, pad)
+    out = torch.empty((N * Ho * Wo, Cout), device=x.device, dtype=x.dtype)
+    check(_lib.lib().morec_conv2d_fwd(_p(x), _p(w), _p(out), N, H, W, Cin, Cout, KH, KW, stride, pad, code(x.dtype), _stream()), "morec_conv2d_fwd")
+    return out
+
+
+def conv2d_bwd_data(dy, wt, N, H, W, stride, pad):
+    """dy [N Ho Wo, Cout] rows, wt [Cin, KH, KW, Cout] -> dx [N H W, Cin]; H, W: the convolution's INPUT grid."""
+    _dev(dy), _dev(wt)
+    Cin, KH, KW, Cout = wt.shape
+    Ho, Wo = conv_out_size(H, KH, stride, pad), conv_out_size(W, KW, stride, pad)
+    assert dy.shape == (N * Ho * Wo, Cout) and dy.dtype == wt.dtype
+    dx = torch.empty((N * H * W, Cin), device=dy.device, dtype=dy.dtype)
+    check(_lib.lib().morec_conv2d_bwd_data(_p(dy), _p(wt), _p(dx), N, H, W, Cin, Cout, KH, KW, stride, pad, code(dy.dtype), _stream()),
+          "morec_conv2d_bwd_data")
+    return dx
+
+
+def im2col_nhwc(x, N, H, W, KH, KW, stride, pad, row0=0, row1=None, ld=None):
+    """The operand rows [row1 - row0, ld] of output rows row0 .. row1 (k = (kh, kw, c); the columns past KH KW Cin are zero)."""
+    _dev(x)
+    Cin = x.shape[1]
+    Ho, Wo = conv_out_size(H, KH, stride, pad), conv_out_size(W, KW, stride, pad)
+    row1 = N * Ho * Wo if row1 is None else row1
+    ev = 16 // x.element_size()
+    ld = (KH * KW * Cin + ev - 1) // ev * ev if ld is None else ld
+    col = torch.empty((row1 - row0, ld), device=x.device, dtype=x.dtype)
+    check(_lib.lib().morec_im2col_nhwc(_p(x), _p(col), N, H, W, Cin, KH, KW, stride, pad, row0, row1, ld, code(x.dtype), _stream()),
+          "morec_im2col_nhwc")
+    return col
+
+
+def bn_slab_rows() -> int:
+    return int(_lib.lib().morec_bn_slab_rows())
+
+
+def bn_stats(x):
+    """fp32 [slabs, 3, C]: (count, mean, M2) of every slab of ``bn_slab_rows()`` rows, per channel."""
+    _dev(x)
+    rows, Cc = x.shape
+    part = torch.empty(((rows + bn_slab_rows() - 1) // bn_slab_rows(), 3, Cc), device=x.device, dtype=torch.float32)
+    check(_lib.lib().morec_bn_stats(_p(x), _p(part), rows, Cc, code(x.dtype), _stream()), "morec_bn_stats")
+    return part
+
+
+def bn_merge(part, eps, running_mean=None, running_var=None, momentum=0.1, need_merged=False):
+    """The partials of ``bn_stats`` merged in slab order (Chan): (mean, rstd, merged [3, C] or None); updates the running statistics in
+    place when they are given."""
+    _dev(part)
+    nslabs, _, Cc = part.shape
+    out = torch.empty((2, Cc), device=part.device, dtype=torch.float32)
+    merged = torch.empty((3, Cc), device=part.device, dtype=torch.float32) if need_merged else None
+    check(_lib.lib().morec_bn_merge(_p(part), nslabs, Cc, float(eps), float(momentum), _p(merged), _p(out[0]), _p(out[1]), _p(running_mean),
+                                    _p(running_var), _stream()), "morec_bn_merge")
+    return out[0], out[1], merged
+
+
+def bn_rstd(var, eps):
+    out = torch.empty_like(var)
+    check(_lib.lib().morec_bn_rstd(_p(_dev(var)), _p(out), var.numel(), float(eps), _stream()), "morec_bn_rstd")
+    return out
+
+
+def bn_apply_fwd(x, mean, rstd, gamma, beta, res=None, relu=False):
+    _dev(x)
+    y = torch.empty_like(x)
+    check(_lib.lib().morec_bn_apply_fwd(_p(x), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(res), _p(y), x.shape[0], x.shape[1], int(relu),
+                                        code(x.dtype), _stream()), "morec_bn_apply_fwd")
+    return y
+
+
+def bn_bwd_reduce(dy, y, x, mean, rstd):
+    """fp32 [2, C]: sum dz, sum dz xhat (dz = dy [y > 0] when ``y``, the output of the ReLU behind the BatchNorm, is given)."""
+    _dev(dy), _dev(x)
+    rows, Cc = x.shape
+    ws = torch.empty(_lib.lib().morec_bn_bwd_workspace_bytes(rows, Cc) // 4, device=x.device, dtype=torch.float32)
+    sums = torch.empty((2, Cc), device=x.device, dtype=torch.float32)
+    check(_lib.lib().morec_bn_bwd_reduce(_p(dy), _p(y), _p(x), _p(mean), _p(rstd), _p(ws), _p(sums), rows, Cc, code(x.dtype), _stream()),
+          "morec_bn_bwd_reduce")
+    return sums
+
+
+def bn_bwd_apply(dy, y, x, mean, rstd, gamma, sums, need_dz=False):
+    """(dx, dz or None); ``sums`` None: the statistics were constants (evaluation mode), dx = gamma rstd dz."""
+    _dev(dy), _dev(x)
+    dx = torch.empty_like(x)
+    dz = torch.empty_like(x) if need_dz else None
+    check(_lib.lib().morec_bn_bwd_apply(_p(dy), _p(y), _p(x), _p(mean), _p(rstd), _p(gamma), _p(sums), _p(dx), _p(dz), x.shape[0], x.shape[1],
+                                        code(x.dtype), _stream()), "morec_bn_bwd_apply")
+    return dx, dz
+
+
+def maxpool3x3s2_fwd(x, N, H, W):
+    """MaxPool2d(3, 2, 1) over [N H W, C] rows -> (y [N Ho Wo, C], tap uint8 [N Ho Wo, C])."""
+    _dev(x)
+    Cc = x.shape[1]
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    y = torch.empty((N * Ho * Wo, Cc), device=x.device, dtype=x.dtype)
+    idx = torch.empty((N * Ho * Wo, Cc), device=x.device, dtype=torch.uint8)
+    check(_lib.lib().morec_maxpool3x3s2_fwd(_p(x), _p(y), _p(idx), N, H, W, Cc, code(x.dtype), _stream()), "morec_maxpool3x3s2_fwd")
+    return y, idx
+
+
+def maxpool3x3s2_bwd(dy, idx, N, H, W):
+    _dev(dy), _dev(idx)
+    dx = torch.empty((N * H * W, dy.shape[1]), device=dy.device, dtype=dy.dtype)
+    check(_lib.lib().morec_maxpool3x3s2_bwd(_p(dy), _p(idx), _p(dx), N, H, W, dy.shape[1], code(dy.dtype), _stream()), "morec_maxpool3x3s2_bwd")
+    return dx
+
+
+def pixels_to_nhwc(pixels, dtype, mean=0.5, std=0.5):
+    """fp32 [n, C, H, W] (normalised already) or uint8 [n, H, W, C] (decoded: ``(x / 255 - mean) / std`` is applied) -> [n H W, C] rows."""
+    _dev(pixels)
+    u8 = pixels.dtype == torch.uint8
+    if not u8 and pixels.dtype != torch.float32:
+        raise _lib.MorecError("pixels must be fp32 NCHW or uint8 NHWC")
+    n, Cc, H, W = (pixels.shape[0], pixels.shape[3], pixels.shape[1], pixels.shape[2]) if u8 else pixels.shape
+    out = torch.empty((n * H * W, Cc), device=pixels.device, dtype=dtype)
+    check(_lib.lib().morec_pixels_to_nhwc(_p(pixels), _p(out), n, Cc, H, W, int(u8), float(mean), float(std), code(dtype), _stream()),
+          "morec_pixels_to_nhwc")
+    return out

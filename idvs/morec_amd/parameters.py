@@ -68,7 +68,8 @@ def build_parser():
     p.add_argument("--news_attributes", type=str, default="title")
     # ============== vision variant (V/parameters.py:34-39) ==============
     p.add_argument("--CV_model_load", type=str, default="None", help="swin_tiny | swin_small | swin_base, mae_base | mae_large (a name with 'mae' "
-                   "or 'checkpoint': the MAE / ViT tower of V/model/model.py:28), or beit_base | beit_large | beit_micro (a name with 'beit': "
+                   "or 'checkpoint': the MAE / ViT tower of V/model/model.py:28), or resnet18 | 34 | 50 | 101 | 152 (a name with 'resnet', 'resnet-50' too: the "
+                   "ResNet tower of V/model/model.py:24), or beit_base | beit_large | beit_micro (a name with 'beit': "
                    "V/model/model.py:26) (vision item tower)")
     p.add_argument("--mae_mask_ratio", type=float, default=None, help="MAE tower: share of the patches masked in a training forward "
                    "(default: the model's, 0.75)")
@@ -196,6 +197,36 @@ def check_beit_args(args):
         why = "--arch dssm: a vision item tower is not built for DSSM"
     if why:
         raise SystemExit(f"--CV_model_load {args.CV_model_load} (BEiT item tower): " + why)
+    return True
+
+
+def is_resnet_run(args) -> bool:
+    """A run whose item tower is the ResNet tower: a modal tower with a ``--CV_model_load`` the reference routes to ``Resnet_Encoder``
+    (``'resnet' in CV_model_load``, tested first, ``V/model/model.py:24-25``)."""
+    return "modal" in str(args.item_tower) and "resnet" in str(getattr(args, "CV_model_load", "None"))
+
+
+def check_resnet_args(args):
+    """What the ResNet tower does not run with: exits with the reason (before anything touches a device).  True for a ResNet run."""
+    if not is_resnet_run(args):
+        return False
+    import os
+    why = None
+    tower = str(args.item_tower)
+    if getattr(args, "fused_step", False):
+        why = ("--fused_step" + (" --pool_negatives" if getattr(args, "pool_negatives", False) else "") +
+               ": train_step.TrainStep covers the text, ID and Swin towers; the ResNet tower trains on the drop-in autograd path")
+    elif getattr(args, "graph", False):
+        why = "--graph replays the fused step (train_step.TrainStep), which the ResNet tower does not use"
+    elif getattr(args, "arch", "sasrec") == "dssm":
+        why = "--arch dssm: a vision item tower is not built for DSSM"
+    elif "add" in tower or "cat" in tower:
+        why = f"--item_tower {tower}: the ID + modality fusion towers are not built over the ResNet tower"
+    elif int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        why = ("a world size above 1: the reference converts the tower to SyncBatchNorm, and BatchNorm statistics per rank would silently be "
+               "another model; merging the (count, mean, M2) partials across ranks is not built")
+    if why:
+        raise SystemExit(f"--CV_model_load {args.CV_model_load} (ResNet item tower): " + why)
     return True
 
 

@@ -30,6 +30,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 import torch.optim as optim
+from torch import nn
+from torch.nn.init import constant_, xavier_normal_
 from torch.nn.parallel import DistributedDataParallel as DDP
 
 from .data_utils import (collate_bce_batch, collate_train_batch, epoch_batches, eval_model, get_checkpoint, get_item_embeddings,
@@ -39,6 +41,7 @@ from .model import BceModel, BertShape, DssmModel, HipBertModel, Model
 from .model.swin import HipSwinForImageClassification
 from .swin_engine import SwinShape
 from .model.beit import HipBeitForImageClassification
+from .model.resnet import HipResNet, ResNetShape
 from .model.mae import HipViTMAEModel
 from .beit_engine import BeitShape
 from .mae_engine import MaeShape
@@ -46,7 +49,7 @@ from .model.opt import HipOPTModel, strip_model_prefix
 from .opt_engine import OptShape
 from .model.deberta import HipDebertaModel, strip_deberta_prefix
 from .deberta_engine import DebertaShape
-from .parameters import (check_beit_args, check_deberta_args, check_dssm_args, check_fusion_args, check_id_two_stage_args, check_mae_args, check_opt_args,
+from .parameters import (check_beit_args, check_deberta_args, check_dssm_args, check_fusion_args, check_id_two_stage_args, check_mae_args, check_opt_args, check_resnet_args, is_resnet_run,
                          check_two_stage_args, is_beit_run, is_deberta_run, is_mae_run, is_opt_run, parse_args)
 from . import engine
 from .train_step import TrainStep
@@ -591,6 +594,15 @@ def build_vision_tower(args):
     """The image network of a vision run, keyed on ``--CV_model_load`` the way ``V/model/model.py:24-29`` is: a Swin classifier
     (``V/run.py:47-54``) or, for a name with 'mae' / 'checkpoint', the ``ViTMAEModel`` container (``--mae_mask_ratio`` /
     ``--mae_eval_mask_ratio`` override the shape's masking), or, for a name with 'beit', the BEiT classifier container."""
+    if is_resnet_run(args):      # V/run.py:38-46: the torchvision net, its checkpoint when the file is there, a fresh fc
+        net = HipResNet(ResNetShape.named(args.CV_model_load))
+        path = os.path.join(args.pretrained_dir, args.CV_model_load)
+        if os.path.isfile(path):
+            net.load_state_dict(torch.load(path, map_location="cpu"))
+        net.fc = nn.Linear(net.shape.num_features, args.embedding_dim)
+        xavier_normal_(net.fc.weight.data)
+        constant_(net.fc.bias.data, 0)
+        return net
     if is_beit_run(args):
         shape = BeitShape.named(args.CV_model_load)
         if shape.image_size != args.CV_resize:
@@ -808,8 +820,8 @@ def train(args, use_modal, local_rank):
         bert = build_text_tower(args)
     bce = args.loss == "bce"
     fusion = check_fusion_args(args) if use_modal else None
-    if bce and (args.fused_step or (vision and not (is_mae_run(args) or is_beit_run(args)))):
-        raise SystemExit("--loss bce runs on the drop-in autograd path with the text / ID / MAE / BEiT towers (bce_text/main-end2end, "
+    if bce and (args.fused_step or (vision and not (is_mae_run(args) or is_beit_run(args) or is_resnet_run(args)))):
+        raise SystemExit("--loss bce runs on the drop-in autograd path with the text / ID / ResNet / MAE / BEiT towers (bce_text/main-end2end, "
                          "bce_vision/main-end2end)")
     model = (BceModel(args, item_num, use_modal, bert) if bce else Model(args, item_num, use_modal, bert, pop)).to(local_rank)
     users = list(users_train.keys())
@@ -1122,9 +1134,11 @@ def two_stage_features(args, item_content, item_num, vision, local_rank, rank):
     """Stage 1 of ``--arch two_stage``: the frozen item tower once over the catalogue (``data_utils.extract_item_features``) -> fp32
     [item_num + 1, W] on the device; ``--save_features`` writes it (rank 0).  The tower is dropped afterwards."""
     from .data_utils import extract_item_features
-    from .model.encoders import Bert_Encoder, MAE_Encoder, Vit_Encoder, resolve_dtype
+    from .model.encoders import Bert_Encoder, MAE_Encoder, Resnet_Encoder, Vit_Encoder, resolve_dtype
     t0 = time.time()
-    if vision and is_mae_run(args):
+    if vision and is_resnet_run(args):      # the pooled vector in front of fc: num_fc_ftr = 512 or 2048
+        tower = Resnet_Encoder(image_net=build_vision_tower(args), compute_dtype=resolve_dtype(args))
+    elif vision and is_mae_run(args):
         tower = MAE_Encoder(image_net=build_vision_tower(args), item_dim=args.embedding_dim, compute_dtype=resolve_dtype(args))
     elif vision:      # Swin, or BEiT (the container decides)
         tower = Vit_Encoder(image_net=build_vision_tower(args), compute_dtype=resolve_dtype(args))
@@ -1243,6 +1257,7 @@ def main(argv=None):
     args = parse_args(argv)
     check_mae_args(args)
     check_beit_args(args)
+    check_resnet_args(args)
     check_opt_args(args)
     check_deberta_args(args)
     two_stage = check_two_stage_args(args)

@@ -531,6 +531,54 @@ int morec_beit_pool_bwd(const void* dpool, void* dx, int n_img, int T, int C, in
 int morec_beit_assemble_fwd(const void* e, const float* cls_token, void* x, int n_img, int N, int C, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The ResNet item tower (resnet_engine.py; csrc/conv.hip, csrc/resnet.hip).  Activations are NHWC, viewed as [N H W, C] rows of the storage
+ * type (any of the three).  No atomics anywhere below: every output element has one writer and every call repeats its bits.
+ *
+ * Convolution as an implicit GEMM.  KH == KW in {1, 3, 7}, stride 1 or 2, 0 <= pad < KH (anything else: MOREC_E_UNSUPPORTED);
+ * Ho = (H + 2 pad - KH) / stride + 1.  fwd: out[(n, ho, wo), co] = sum_{kh, kw, c} x[n, ho s - p + kh, wo s - p + kw, c] w[co, kh, kw, c]
+ * (zero outside the image), w as [Cout, KH, KW, Cin], Cout % 8 == 0.  bwd_data: dx[(n, h, w), c] = sum over the taps whose
+ * (h + p - kh) / s and (w + p - kw) / s are exact and in range of dy[n, ., ., co] wt[c, kh, kw, co], wt as [Cin, KH, KW, Cout],
+ * Cin % 8 == 0; H, W are the INPUT grid in both.  16-bit storage whose reduction channel count (Cin for fwd, Cout for bwd_data) is a
+ * multiple of 32 runs on the 16x16x32 MFMAs (morec_conv2d_uses_mfma); everything else on an fp32-FMA kernel, in (kh, kw, c) order. */
+int morec_conv2d_uses_mfma(int reduction_channels, int dtype);
+int morec_conv2d_fwd(const void* x, const void* w, void* out, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                     int dtype, void* stream);
+int morec_conv2d_bwd_data(const void* dy, const void* wt, void* dx, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                          int pad, int dtype, void* stream);
+/* col[r - row0, (kh, kw, c)] for output rows row0 <= r < row1, row pitch ld >= KH KW Cin elements (a multiple of the 16-byte vector; the
+ * columns past KH KW Cin are zeroed): the operand of the weight gradient, dW[co, (kh, kw, c)] += dy[rows]^T col. */
+int morec_im2col_nhwc(const void* x, void* col, int N, int H, int W, int Cin, int KH, int KW, int stride, int pad, int row0, int row1, int ld,
+                      int dtype, void* stream);
+/* BatchNorm2d over [rows, C], C % 8 == 0.  stats: part fp32 [ceil(rows / morec_bn_slab_rows()), 3, C] = (count, mean, M2) of every slab
+ * of rows, the slab mean first and then the squared deviations from it.  merge: the partials combined in slab order by Chan's formula
+ * into merged [3, C] (optional), mean and rstd = 1 / sqrt(M2 / count + eps) (optional), and, when running_mean / running_var are given,
+ * torch's update running = (1 - momentum) running + momentum batch with the unbiased variance.  rstd: 1 / sqrt(var + eps) of given
+ * (running) variances.  apply_fwd: y = relu?(gamma (x - mean) rstd + beta (+ res)), fp32, one rounding.
+ * bwd_reduce: sums fp32 [2, C] = sum dz, sum dz xhat with dz = dy [y > 0] when y (the saved output of a ReLU) is given, else dy; per-slab
+ * partials in ws (morec_bn_bwd_workspace_bytes) added in slab order.  bwd_apply: dx = gamma rstd (dz - sums[0] / rows - xhat sums[1] /
+ * rows), or gamma rstd dz with sums == NULL (running statistics); dz (optional) receives dz itself. */
+int morec_bn_slab_rows(void);
+int morec_bn_stats(const void* x, float* part, int rows, int C, int dtype, void* stream);
+int morec_bn_merge(const float* part, int nslabs, int C, float eps, float momentum, float* merged, float* mean, float* rstd,
+                   float* running_mean, float* running_var, void* stream);
+int morec_bn_rstd(const float* var, float* rstd, int C, float eps, void* stream);
+int morec_bn_apply_fwd(const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const void* res, void* y,
+                       int rows, int C, int relu, int dtype, void* stream);
+size_t morec_bn_bwd_workspace_bytes(int rows, int C);
+int morec_bn_bwd_reduce(const void* dy, const void* y, const void* x, const float* mean, const float* rstd, float* ws, float* sums, int rows,
+                        int C, int dtype, void* stream);
+int morec_bn_bwd_apply(const void* dy, const void* y, const void* x, const float* mean, const float* rstd, const float* gamma,
+                       const float* sums, void* dx, void* dz, int rows, int C, int dtype, void* stream);
+/* MaxPool2d(3, stride 2, padding 1), C % 8 == 0: y [N Ho Wo, C] with Ho = (H - 1) / 2 + 1; idx uint8 [N Ho Wo, C] = the selected tap
+ * kh * 3 + kw, the FIRST in scan order among equal values (torch's rule; ties are the normal case on post-ReLU input).  bwd: dx[N H W, C],
+ * every pixel gathers dy from the windows that selected it. */
+int morec_maxpool3x3s2_fwd(const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, int dtype, void* stream);
+int morec_maxpool3x3s2_bwd(const void* dy, const uint8_t* idx, void* dx, int N, int H, int W, int C, int dtype, void* stream);
+/* src fp32 [n, C, H, W] (src_u8 == 0; copied), or uint8 [n, H, W, C] (src_u8 != 0; (x / 255 - mean) / std as morec_swin_patchify_u8)
+ * -> out [n H W, C] of the storage type. */
+int morec_pixels_to_nhwc(const void* src, void* out, int n, int C, int H, int W, int src_u8, float mean, float std, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * DeBERTa's disentangled self-attention (HF modeling_deberta.py DisentangledSelfAttention with pos_att_type c2p + p2c; csrc/deberta.hip),
  * T <= 64 (titles): morec_attn_fwd / _bwd with two position terms on every score,
  *     score[i][j] = (q_i . k_j + q_i . PK_h[d] + k_j . PQ_h[d]) * scale,   d = i - j + T  (1 .. 2T-1: row 0 of PK / PQ is never read),
