@@ -216,6 +216,8 @@ _SIGS = {
     "morec_bn_bwd_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "morec_bn_bwd_reduce": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "morec_bn_bwd_apply": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "morec_bn_bwd_fold": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    "morec_bn_bwd_apply_n": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "morec_maxpool3x3s2_fwd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "morec_maxpool3x3s2_bwd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "morec_pixels_to_nhwc": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P]),

@@ -6,6 +6,13 @@
 // mode.  The partials are merged in slab order with Chan's formula (morec_bn_merge: one thread per channel; resnet_engine.merge_bn_partials
 // is the same arithmetic on the host, the form a later change merges across ranks).  The backward sums are per-slab partials folded in slab
 // order too.  Nothing here uses atomics: every call repeats its bits.
+//
+// Synchronised BatchNorm (data-parallel ranks; resnet_engine._bn_fwd / _bn_bwd with a sync context) is the same kernels over one more level:
+// a rank merges its slabs into one [3, C] partial, the ranks' partials are all-gathered rank-major and morec_bn_merge runs once more over
+// those "W slabs" in rank order (that launch updates the running statistics with the global count); the backward sums [2, C] of the ranks
+// are gathered and added in rank order by morec_bn_bwd_fold, and morec_bn_bwd_apply_n divides by the global row count it READS from the
+// merged count row on the device -- the host never learns that count.  An all-gather and a fixed-order fold, never an all-reduce, whose
+// order of summation belongs to the library: every rank computes the same bits.
 #include <algorithm>
 #include "common.hpp"
 
@@ -230,6 +237,53 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
     }
 }
 
+// The same with the means divided by the row count of ALL ranks read from device memory: synchronised BatchNorm, whose sums are the
+// ranks' folded sums (never null).  count: the merged count row (fp32 [C]); every channel counts the same rows, so count[0] is read, once,
+// and 1 / count[0] takes the place of inv_rows -- the correctly rounded division the host does there, and the text after it is that kernel's,
+// so that the compiler contracts and pairs the same operations: a count equal to rows gives the kernel above's bits.  A kernel of its own, so that the one above keeps its instruction stream.  An fp32
+// count is exact below 2^24 rows and relatively 2^-24 off beyond (704 images x 112^2 x 8 ranks passes it): far inside every bound.
+template <typename T>
+__global__ __launch_bounds__(256) void bn_bwd_apply_n_kernel(const T* __restrict__ dy, const T* __restrict__ y, const T* __restrict__ x,
+                                                             const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                             const float* __restrict__ gamma, const float* __restrict__ sums,
+                                                             const float* __restrict__ count, T* __restrict__ dx, T* __restrict__ dz_out,
+                                                             size_t rows, int C) {
+    constexpr int EV = vio<T>::EV;
+    const int vpr = C / EV;
+    const size_t total = rows * vpr;
+    const float inv_rows = 1.0f / count[0];
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const size_t row = e / vpr;
+        const int c = (int)(e - row * vpr) * EV;
+        float d[EV], v[EV], m[EV], rs[EV], g[EV], a[EV], b[EV];
+        vio<T>::load(dy + row * C + c, d);
+        vio<T>::load(x + row * C + c, v);
+        load_f32v<EV>(mean + c, m);
+        load_f32v<EV>(rstd + c, rs);
+        load_f32v<EV>(gamma + c, g);
+        if (y) {
+            float o[EV];
+            vio<T>::load(y + row * C + c, o);
+#pragma unroll
+            for (int k = 0; k < EV; ++k) d[k] = o[k] > 0.f ? d[k] : 0.f;
+        }
+        if (dz_out) vio<T>::store(dz_out + row * C + c, d);
+        if (sums) {
+            load_f32v<EV>(sums + c, a);
+            load_f32v<EV>(sums + C + c, b);
+#pragma unroll
+            for (int k = 0; k < EV; ++k) {
+                const float xh = (v[k] - m[k]) * rs[k];
+                d[k] = g[k] * rs[k] * (d[k] - a[k] * inv_rows - xh * (b[k] * inv_rows));
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < EV; ++k) d[k] = g[k] * rs[k] * d[k];
+        }
+        vio<T>::store(dx + row * C + c, d);
+    }
+}
+
 // ---- MaxPool2d(3, stride 2, padding 1) over NHWC: among equal values the first tap in (kh, kw) scan order wins; its index is kept
 template <typename T>
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, uint8_t* __restrict__ idx, int N, int H,
@@ -400,20 +454,54 @@ extern "C" int morec_bn_bwd_reduce(const void* dy, const void* y, const void* x,
     return MOREC_OK;
 }
 
-extern "C" int morec_bn_bwd_apply(const void* dy, const void* y, const void* x, const float* mean, const float* rstd, const float* gamma,
-                                  const float* sums, void* dx, void* dz, int rows, int C, int dtype, void* stream) {
+extern "C" int morec_bn_bwd_fold(const float* parts, int n, int C, float* sums, void* stream) {
+    if (!parts || !sums || n <= 0 || C <= 0) return MOREC_E_ARG;
+    hipLaunchKernelGGL(bn_bwd_fold_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), parts, n, C, sums);
+    MOREC_CHECK_LAUNCH();
+    return MOREC_OK;
+}
+
+namespace {
+int bn_bwd_apply_check(const void* dy, const void* y, const void* x, const float* mean, const float* rstd, const float* gamma, const float* sums,
+                       const void* dx, const void* dz, int rows, int C) {
     const int rc = vec_check(dy, x, rows, C);
     if (rc) return rc;
     if (!mean || !rstd || !gamma || !dx) return MOREC_E_ARG;
     if (!aligned16(mean) || !aligned16(rstd) || !aligned16(gamma) || !aligned16(dx) || (y && !aligned16(y)) || (dz && !aligned16(dz)) ||
         (sums && !aligned16(sums)))
         return MOREC_E_ALIGN;
+    return MOREC_OK;
+}
+}  // namespace
+
+extern "C" int morec_bn_bwd_apply(const void* dy, const void* y, const void* x, const float* mean, const float* rstd, const float* gamma,
+                                  const float* sums, void* dx, void* dz, int rows, int C, int dtype, void* stream) {
+    const int rc = bn_bwd_apply_check(dy, y, x, mean, rstd, gamma, sums, dx, dz, rows, C);
+    if (rc) return rc;
     const size_t total = (size_t)rows * (C / (16 / elt_size(dtype)));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (!by_dtype(dtype, [&](auto* t) {
             using T = MOREC_TAG_T(t);
             hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(grid_for(total)), dim3(256), 0, s, (const T*)dy, (const T*)y, (const T*)x, mean, rstd,
                                gamma, sums, 1.0f / (float)rows, (T*)dx, (T*)dz, (size_t)rows, C);
+        }))
+        return MOREC_E_DTYPE;
+    MOREC_CHECK_LAUNCH();
+    return MOREC_OK;
+}
+
+extern "C" int morec_bn_bwd_apply_n(const void* dy, const void* y, const void* x, const float* mean, const float* rstd, const float* gamma,
+                                    const float* sums, const float* count, void* dx, void* dz, int rows, int C, int dtype, void* stream) {
+    const int rc = bn_bwd_apply_check(dy, y, x, mean, rstd, gamma, sums, dx, dz, rows, C);
+    if (rc) return rc;
+    if (!sums || !count) return MOREC_E_ARG;
+    if (!aligned16(count)) return MOREC_E_ALIGN;
+    const size_t total = (size_t)rows * (C / (16 / elt_size(dtype)));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (!by_dtype(dtype, [&](auto* t) {
+            using T = MOREC_TAG_T(t);
+            hipLaunchKernelGGL((bn_bwd_apply_n_kernel<T>), dim3(grid_for(total)), dim3(256), 0, s, (const T*)dy, (const T*)y, (const T*)x, mean,
+                               rstd, gamma, sums, count, (T*)dx, (T*)dz, (size_t)rows, C);
         }))
         return MOREC_E_DTYPE;
     MOREC_CHECK_LAUNCH();

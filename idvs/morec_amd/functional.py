@@ -252,16 +252,17 @@ class BeitEncoderFn(torch.autograd.Function):
 
 class ResNetEncoderFn(torch.autograd.Function):
     """``Resnet_Encoder.forward`` (``V/model/encoders.py:40-41``) over torchvision ``ResNet`` arithmetic.  ``cfg = (names, shape, dtype,
-    prefix, bufs, training)``: ``bufs`` are the BatchNorm buffers by name (training mode updates the running statistics in place).  A frozen
+    prefix, bufs, training, sync)``: ``bufs`` are the BatchNorm buffers by name (training mode updates the running statistics in place);
+    ``sync`` is a ``resnet_engine.BnSync`` (training mode takes the statistics over every rank's rows) or None.  A frozen
     parameter gets no buffer: a frozen convolution skips its weight gradient, a frozen BatchNorm still normalises with batch statistics."""
 
     @staticmethod
     def forward(ctx, pixels, cfg, *params):
-        names, shape, dtype, prefix, bufs, training = cfg
+        names, shape, dtype, prefix, bufs, training, sync = cfg
         p = dict(zip(names, params))
         need = any(ctx.needs_input_grad)
         prep = resnet_engine.resnet_prepare(p, shape, dtype, prefix, need_grad=need)
-        item, saved = resnet_engine.resnet_forward(p, bufs, prep, shape, pixels, dtype, need, prefix, training)
+        item, saved = resnet_engine.resnet_forward(p, bufs, prep, shape, pixels, dtype, need, prefix, training, sync=sync)
         ctx.stuff = (p, prep, saved, names, prefix)
         ctx.needs = ctx.needs_input_grad
         ctx.fp32_gemm = ops.FP32_GEMM
@@ -582,15 +583,16 @@ class DssmBceFn(torch.autograd.Function):
         return dU, dE, None, None, None
 
 
-def _all_gather_cat(t: torch.Tensor, world: int, comm=None) -> torch.Tensor:
+def _all_gather_cat(t: torch.Tensor, world: int, comm=None, group=None) -> torch.Tensor:
+    """``group``: the process group (None: the world), of ``world`` ranks."""
     if comm is not None:       # morec_comm_all_gather: RCCL on the compute stream (comm.MorecComm)
         return comm.all_gather(t)
     out = torch.empty((world * t.shape[0],) + tuple(t.shape[1:]), device=t.device, dtype=t.dtype)
-    if dist.get_backend() == "gloo" and t.is_cuda:   # gloo smoke tests on a GPU box: list form, staged through the host
+    if dist.get_backend(group) == "gloo" and t.is_cuda:   # gloo smoke tests on a GPU box: list form, staged through the host
         parts = [torch.empty_like(t, device="cpu") for _ in range(world)]
-        dist.all_gather(parts, t.detach().cpu().contiguous())
+        dist.all_gather(parts, t.detach().cpu().contiguous(), group=group)
         return torch.cat(parts, 0).to(t.device)
-    dist.all_gather_into_tensor(out, t.contiguous())
+    dist.all_gather_into_tensor(out, t.contiguous(), group=group)
     return out
 
 

@@ -289,16 +289,44 @@ class Resnet_Encoder(nn.Module):
     """``V/model/encoders.py:34-41``: ``GELU(image_net(item_content))`` with ``image_net`` a torchvision ``ResNet`` whose ``fc`` was
     replaced by ``Linear(num_fc_ftr, embedding_dim)`` (``V/run.py:38-46``): a ``HipResNet`` container, or any module with torchvision's
     ResNet keys (``HipResNet.from_torch``).  The GELU is the epilogue of the ``fc`` product.  Training mode normalises with the statistics
-    of the whole call and updates the running statistics; evaluation mode applies the running statistics."""
+    of the whole call and updates the running statistics; evaluation mode applies the running statistics.
+
+    ``torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)`` (``V/run.py:98``) turns the container's ``nn.BatchNorm2d`` modules into
+    ``nn.SyncBatchNorm`` with the same keys and parameters; the tower then takes its training-mode statistics over every rank of that
+    module's ``process_group`` (None: the world) -- ``resnet_engine.BnSync``.  World size 1, or no initialised process group, is the
+    plain path, as torch falls back."""
 
     def __init__(self, image_net, compute_dtype=None):
         super().__init__()
         self.image_net = image_net if isinstance(image_net, HipResNet) else HipResNet.from_torch(image_net)
         self.compute_dtype = compute_dtype or resolve_dtype()
 
+    def sync_context(self):
+        """The ``BnSync`` of the converted tower, or None: all BatchNorm modules under ``image_net`` are ``SyncBatchNorm`` (of one process
+        group) or none is; a mixture raises."""
+        import torch.distributed as dist
+        from ..resnet_engine import BnSync
+        bns = [(n, m) for n, m in self.image_net.named_modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
+        synced = [n for n, m in bns if isinstance(m, nn.SyncBatchNorm)]
+        if not synced:
+            return None
+        if len(synced) != len(bns):
+            plain = [n for n, m in bns if not isinstance(m, nn.SyncBatchNorm)]
+            raise NotImplementedError(f"ResNet tower: a mixture of SyncBatchNorm ({len(synced)}, e.g. {synced[0]}) and BatchNorm2d "
+                                      f"({len(plain)}, e.g. {plain[0]}) modules: convert the whole tower or none of it")
+        groups = {id(m.process_group): m.process_group for _, m in bns}
+        if len(groups) != 1:
+            raise NotImplementedError("ResNet tower: the SyncBatchNorm modules name different process groups")
+        if not (dist.is_available() and dist.is_initialized()):
+            return None
+        group = next(iter(groups.values()))
+        world = dist.get_world_size(group)
+        return BnSync(group, world) if world > 1 else None
+
     def encode(self, item_content, drop: DropCfg = NO_DROP):
         names, params = zip(*self.named_parameters())
-        cfg = (names, self.image_net.shape, self.compute_dtype, "image_net.", dict(self.named_buffers()), self.training)
+        cfg = (names, self.image_net.shape, self.compute_dtype, "image_net.", dict(self.named_buffers()), self.training,
+               self.sync_context())
         return F_.ResNetEncoderFn.apply(item_content, cfg, *params)
 
     def forward(self, item_content):

@@ -1480,6 +1480,17 @@ def bn_merge(part, eps, running_mean=None, running_var=None, momentum=0.1, need_
     return out[0], out[1], merged
 
 
+def bn_merged(part):
+    """fp32 [n, 3, C] -> [3, C]: the (count, mean, M2) partials merged in index order and nothing else written (one ``morec_bn_merge``
+    launch: a rank's own slabs in front of the gather of synchronised BatchNorm)."""
+    _dev(part)
+    n, three, Cc = part.shape
+    assert three == 3 and part.dtype == torch.float32 and part.is_contiguous()
+    merged = torch.empty((3, Cc), device=part.device, dtype=torch.float32)
+    check(_lib.lib().morec_bn_merge(_p(part), n, Cc, 0.0, 0.0, _p(merged), None, None, None, None, _stream()), "morec_bn_merge")
+    return merged
+
+
 def bn_rstd(var, eps):
     out = torch.empty_like(var)
     check(_lib.lib().morec_bn_rstd(_p(_dev(var)), _p(out), var.numel(), float(eps), _stream()), "morec_bn_rstd")
@@ -1505,11 +1516,28 @@ def bn_bwd_reduce(dy, y, x, mean, rstd):
     return sums
 
 
-def bn_bwd_apply(dy, y, x, mean, rstd, gamma, sums, need_dz=False):
-    """(dx, dz or None); ``sums`` None: the statistics were constants (evaluation mode), dx = gamma rstd dz."""
+def bn_bwd_fold(parts):
+    """fp32 [n, 2, C] -> [2, C]: the backward sums of n ranks (or slabs) added in index order."""
+    _dev(parts)
+    n, two, Cc = parts.shape
+    assert two == 2 and parts.dtype == torch.float32 and parts.is_contiguous()
+    sums = torch.empty((2, Cc), device=parts.device, dtype=torch.float32)
+    check(_lib.lib().morec_bn_bwd_fold(_p(parts), n, Cc, _p(sums), _stream()), "morec_bn_bwd_fold")
+    return sums
+
+
+def bn_bwd_apply(dy, y, x, mean, rstd, gamma, sums, need_dz=False, count=None):
+    """(dx, dz or None); ``sums`` None: the statistics were constants (evaluation mode), dx = gamma rstd dz.  ``count`` (fp32 [C] on the
+    device, the merged count row of every rank's rows; one value for all channels): the means of ``sums`` divide by it instead of by ``x.shape[0]``
+    (``morec_bn_bwd_apply_n``; synchronised BatchNorm, whose ``sums`` are the ranks' folded sums)."""
     _dev(dy), _dev(x)
     dx = torch.empty_like(x)
     dz = torch.empty_like(x) if need_dz else None
+    if count is not None:
+        assert sums is not None and count.dtype == torch.float32 and count.shape == (x.shape[1],) and count.is_contiguous()
+        check(_lib.lib().morec_bn_bwd_apply_n(_p(dy), _p(y), _p(x), _p(mean), _p(rstd), _p(gamma), _p(sums), _p(_dev(count)), _p(dx), _p(dz),
+                                              x.shape[0], x.shape[1], code(x.dtype), _stream()), "morec_bn_bwd_apply_n")
+        return dx, dz
     check(_lib.lib().morec_bn_bwd_apply(_p(dy), _p(y), _p(x), _p(mean), _p(rstd), _p(gamma), _p(sums), _p(dx), _p(dz), x.shape[0], x.shape[1],
                                         code(x.dtype), _stream()), "morec_bn_bwd_apply")
     return dx, dz

@@ -102,6 +102,10 @@ def build_parser():
                         "operand splits (fp32 nn.Linear numerics to ~1e-5); fp16_res32 / bf16_res32 = 16-bit GEMMs with an fp32 residual stream "
                         "(LayerNorm in and out fp32): the data flow of torch.cuda.amp.autocast itself, text / ID towers")
     p.add_argument("--pool_negatives", action="store_true", help="pool in-batch negatives over ranks (RCCL all-gather)")
+    p.add_argument("--sync_bn", action="store_true",
+                   help="torch.nn.SyncBatchNorm.convert_sync_batchnorm(model) before the DDP wrap, as V/run.py:98 does unconditionally: the ResNet "
+                   "item tower then takes its BatchNorm statistics over every rank's rows (required for it at a world size above 1); a no-op "
+                   "at world size 1 and for every tower without BatchNorm layers")
     p.add_argument("--fused_step", action="store_true",
                    help="flat-arena TrainStep (fused AdamW, one gradient all-reduce) instead of DDP + torch.optim.AdamW")
     p.add_argument("--loss", type=str, default="inbatch", choices=["inbatch", "bce"],
@@ -222,9 +226,9 @@ def check_resnet_args(args):
         why = "--arch dssm: a vision item tower is not built for DSSM"
     elif "add" in tower or "cat" in tower:
         why = f"--item_tower {tower}: the ID + modality fusion towers are not built over the ResNet tower"
-    elif int(os.environ.get("WORLD_SIZE", 1)) > 1:
-        why = ("a world size above 1: the reference converts the tower to SyncBatchNorm, and BatchNorm statistics per rank would silently be "
-               "another model; merging the (count, mean, M2) partials across ranks is not built")
+    elif int(os.environ.get("WORLD_SIZE", 1)) > 1 and not getattr(args, "sync_bn", False):
+        why = ("a world size above 1 needs --sync_bn: the reference converts the tower to SyncBatchNorm (V/run.py:98), and BatchNorm "
+               "statistics per rank would silently be another model; --sync_bn converts it and merges the statistics across ranks")
     if why:
         raise SystemExit(f"--CV_model_load {args.CV_model_load} (ResNet item tower): " + why)
     return True

@@ -15,8 +15,20 @@ that the im2col workspace stays under ``WGRAD_WS_CAP`` bytes.  Correctness first
 BatchNorm2d in training mode uses the statistics of ALL rows of the call (the zero images of padding items included, as in the
 reference), so the training forward never chunks the batch; the statistics are per-slab ``(count, mean, M2)`` partials merged in slab
 order (``merge_bn_partials``).  Evaluation mode applies the running statistics through the same apply kernel.  A frozen gamma / beta
-still normalises with batch statistics in training mode: it only gets no gradient buffer."""
+still normalises with batch statistics in training mode: it only gets no gradient buffer.
+
+Synchronised BatchNorm (``BnSync``: a process group and its size; ``None`` is the plain path, untouched).  Training mode with W ranks is
+BatchNorm over the concatenation of the ranks' rows, as torch documents ``SyncBatchNorm``.  Forward: stats -> the rank's own slabs merged
+-> one all-gather of the [3, C] results, rank-major -> ``morec_bn_merge`` over those W partials in rank order, which also updates the
+running statistics with the global count.  Backward: the local sums (d gamma and d beta stay LOCAL: DDP averages them like every other
+parameter gradient) -> one all-gather of [2, C] -> ``morec_bn_bwd_fold`` in rank order -> the apply kernel that divides by the merged
+count row it reads on the device.  An all-gather and a fixed-order fold, never an all-reduce: every rank computes the same bits, and the
+host never learns the global row count.  One collective per BatchNorm forward and one per backward (53 + 53 at ResNet-50), all on the
+current stream.  Whether a BatchNorm communicates follows from configuration alone (training flag, sync context, the frozen prefix), never
+from data: every rank issues the same collectives in the same order.  Evaluation mode has none."""
 from __future__ import annotations
+
+from typing import Any, NamedTuple
 
 import torch
 
@@ -33,7 +45,7 @@ WGRAD_WS_CAP = 256 << 20      # bytes of im2col workspace per weight-gradient ch
 def merge_bn_partials(part: torch.Tensor) -> torch.Tensor:
     """``part`` [slabs, 3, C] = (count, mean, M2) per slab and channel -> [3, C], merged in slab order with Chan's formula
     (``mean += delta nb / n``, ``M2 += M2b + delta^2 na nb / n``) in the dtype of ``part``.  Device tensors run ``morec_bn_merge`` (the
-    same arithmetic, one thread per channel); host tensors run it here -- the form that merges the partials of several ranks."""
+    same arithmetic, one thread per channel); host tensors run it here.  ``merge_bn_over_ranks`` runs it over the gathered [3, C] results of the ranks, in rank order."""
     if part.is_cuda:
         return ops.bn_merge(part.contiguous(), 0.0, need_merged=True)[2]
     n, mean, m2 = part[0, 0].clone(), part[0, 1].clone(), part[0, 2].clone()
@@ -44,6 +56,36 @@ def merge_bn_partials(part: torch.Tensor) -> torch.Tensor:
         m2 = m2 + m2b + delta * delta * (n * nb / tot)
         n = tot
     return torch.stack([n, mean, m2])
+
+
+class BnSync(NamedTuple):
+    """The sync context of the BatchNorm layers: ``group`` (a ``torch.distributed`` process group; None: the world) of ``world`` ranks."""
+    group: Any
+    world: int
+
+
+def gather_over_ranks(t: torch.Tensor, sync: BnSync) -> torch.Tensor:
+    """[k, C] of every rank -> [W, k, C], rank-major (one all-gather; host tensors too)."""
+    from .functional import _all_gather_cat
+    return _all_gather_cat(t.unsqueeze(0).contiguous(), sync.world, group=sync.group)
+
+
+def merge_bn_over_ranks(merged: torch.Tensor, sync: BnSync) -> torch.Tensor:
+    """A rank's own merged [3, C] -> the [3, C] of all ranks' rows: gathered, then ``merge_bn_partials`` over the W partials in rank
+    order.  The same bits on every rank."""
+    return merge_bn_partials(gather_over_ranks(merged, sync))
+
+
+def fold_bn_sums_over_ranks(sums: torch.Tensor, sync: BnSync) -> torch.Tensor:
+    """A rank's backward sums [2, C] -> the sums over all ranks, added in rank order (``morec_bn_bwd_fold``; a host loop for host
+    tensors)."""
+    parts = gather_over_ranks(sums, sync)
+    if parts.is_cuda:
+        return ops.bn_bwd_fold(parts)
+    total = torch.zeros_like(parts[0])
+    for r in range(parts.shape[0]):
+        total = total + parts[r]
+    return total
 
 
 def conv_names(shape, prefix: str = IN):
@@ -127,33 +169,45 @@ def _conv_bwd(dy, x, xs, geom, cw, gw, need_dx, chunk_images=None):
     return ops.conv2d_bwd_data(dy, wt, N, H, W, stride, pad)
 
 
-def _bn_fwd(p, bufs, name, x, training, relu, res=None):
-    """BatchNorm2d ``name`` over x [rows, C] (+ residual, ReLU) -> (y, mean, rstd)."""
+def _bn_fwd(p, bufs, name, x, training, relu, res=None, sync=None):
+    """BatchNorm2d ``name`` over x [rows, C] (+ residual, ReLU) -> (y, (mean, rstd, count)); ``count``: the merged count row of all
+    ranks' rows under ``sync`` in training mode (what the backward divides by), else None."""
     rm, rv = bufs[name + ".running_mean"], bufs[name + ".running_var"]
-    if training:
+    count = None
+    if training and sync is not None:
+        parts = gather_over_ranks(ops.bn_merged(ops.bn_stats(x)), sync)
+        mean, rstd, merged = ops.bn_merge(parts, p["eps"], rm, rv, p["momentum"], need_merged=True)
+        count = merged[0]
+        bufs[name + ".num_batches_tracked"].add_(1)
+    elif training:
         mean, rstd, _ = ops.bn_merge(ops.bn_stats(x), p["eps"], rm, rv, p["momentum"])
         bufs[name + ".num_batches_tracked"].add_(1)
     else:
         mean, rstd = rm, ops.bn_rstd(rv, p["eps"])
     y = ops.bn_apply_fwd(x, mean, rstd, p[name + ".weight"], p[name + ".bias"], res=res, relu=relu)
-    return y, mean, rstd
+    return y, (mean, rstd, count)
 
 
-def _bn_bwd(p, grads, name, dy, y_relu, x, mean, rstd, training, need_dz=False):
-    """-> (dx, dz).  ``y_relu``: the BatchNorm's saved output when a ReLU follows it, else None."""
+def _bn_bwd(p, grads, name, dy, y_relu, x, stat, training, need_dz=False, sync=None):
+    """-> (dx, dz).  ``y_relu``: the BatchNorm's saved output when a ReLU follows it, else None.  ``stat``: ``_bn_fwd``'s."""
+    mean, rstd, count = stat
     sums = ops.bn_bwd_reduce(dy, y_relu, x, mean, rstd)
     if name + ".weight" in grads:
         grads[name + ".weight"].copy_(sums[1])
     if name + ".bias" in grads:
         grads[name + ".bias"].copy_(sums[0])
+    if training and sync is not None:
+        return ops.bn_bwd_apply(dy, y_relu, x, mean, rstd, p[name + ".weight"], fold_bn_sums_over_ranks(sums, sync), need_dz=need_dz,
+                                count=count)
     return ops.bn_bwd_apply(dy, y_relu, x, mean, rstd, p[name + ".weight"], sums if training else None, need_dz=need_dz)
 
 
 def resnet_forward(p: dict, bufs: dict, prep, shape, pixels: torch.Tensor, dtype, need_grad: bool, prefix: str = IN, training: bool = False,
-                   features_only: bool = False):
+                   features_only: bool = False, sync=None):
     """pixels fp32 [n_img, 3, H, W] (normalised) or uint8 [n_img, H, W, 3] (decoded) -> item vectors [n_img, D]
     (``GELU(fc(avgpool(layer4(...))))``).  ``bufs``: the BatchNorm buffers by name (training mode updates them in place).
-    ``features_only``: return ``(pooled [n_img, num_fc_ftr], None)``, the input of ``fc``."""
+    ``features_only``: return ``(pooled [n_img, num_fc_ftr], None)``, the input of ``fc``.  ``sync``: a ``BnSync`` -- training mode takes
+    the BatchNorm statistics over every rank's rows (under ``no_grad`` too); None: this call's rows alone."""
     q = dict(p)
     q["eps"], q["momentum"] = shape.eps, shape.momentum
     u8 = pixels.dtype == torch.uint8
@@ -161,10 +215,10 @@ def resnet_forward(p: dict, bufs: dict, prep, shape, pixels: torch.Tensor, dtype
     x0 = ops.pixels_to_nhwc(pixels.contiguous(), dtype)
     tape = []
     c0, g1, _ = _conv_fwd(x0, (N, H, W), prep[prefix + "conv1.weight"])
-    y0, m0, r0 = _bn_fwd(q, bufs, prefix + "bn1", c0, training, True)
+    y0, s0 = _bn_fwd(q, bufs, prefix + "bn1", c0, training, True, sync=sync)
     x, idx = ops.maxpool3x3s2_fwd(y0, *g1)
     geom = (N, (g1[1] - 1) // 2 + 1, (g1[2] - 1) // 2 + 1)
-    stem = (x0, (N, H, W), c0, y0, m0, r0, g1, idx)
+    stem = (x0, (N, H, W), c0, y0, s0, g1, idx)
     n_conv = 2 if shape.block == "basic" else 3
     for name, _, _, stride, down in shape.blocks():
         B = prefix + name + "."
@@ -178,12 +232,12 @@ def resnet_forward(p: dict, bufs: dict, prep, shape, pixels: torch.Tensor, dtype
                 ident = x
                 if down:
                     dc, _, dxs = _conv_fwd(x, geom, prep[B + "downsample.0.weight"])
-                    ident, dm, dr = _bn_fwd(q, bufs, B + "downsample.1", dc, training, False)
-                    rec["down"] = (dxs, dc, dm, dr)
-                y, m, r = _bn_fwd(q, bufs, B + f"bn{i}", c, training, True, res=ident)
+                    ident, ds = _bn_fwd(q, bufs, B + "downsample.1", dc, training, False, sync=sync)
+                    rec["down"] = (dxs, dc, ds)
+                y, st = _bn_fwd(q, bufs, B + f"bn{i}", c, training, True, res=ident, sync=sync)
             else:
-                y, m, r = _bn_fwd(q, bufs, B + f"bn{i}", c, training, True)
-            rec["convs"].append((h, xs, hg, c, y, m, r))
+                y, st = _bn_fwd(q, bufs, B + f"bn{i}", c, training, True, sync=sync)
+            rec["convs"].append((h, xs, hg, c, y, st))
             h, hg = y, cg
         tape.append(rec)
         x, geom = h, hg
@@ -193,14 +247,16 @@ def resnet_forward(p: dict, bufs: dict, prep, shape, pixels: torch.Tensor, dtype
     D = prep["fc"].w.shape[0]
     pre = torch.empty((N, D), device=x.device, dtype=dtype) if need_grad else None
     item = ops.gemm_nt(pooled, prep["fc"].w, bias=p[prefix + "fc.bias"], act=ACT_GELU, aux_out=pre)
-    saved = (shape, stem, tape, geom, pooled, pre, training) if need_grad else None
+    saved = (shape, stem, tape, geom, pooled, pre, training, sync) if need_grad else None
     return item, saved
 
 
 def resnet_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefix: str = IN, chunk_images=None):
     """grads: name -> fp32 buffer (zeroed; accumulated into).  A name that is missing from ``grads`` is frozen: a convolution without a
-    buffer skips its weight gradient, a BatchNorm without one only skips its own gamma / beta gradient."""
-    shape, stem, tape, geom, pooled, pre, training = saved
+    buffer skips its weight gradient, a BatchNorm without one only skips its own gamma / beta gradient.  Under a sync context every
+    BatchNorm that is walked gathers once; which ones are walked follows from the names in ``grads`` (configuration, the same on every
+    rank)."""
+    shape, stem, tape, geom, pooled, pre, training, sync = saved
     n_conv = 2 if shape.block == "basic" else 3
     dv = ops.act_bwd(d_item.contiguous(), pre, ACT_GELU)
     if prefix + "fc.bias" in grads:
@@ -219,21 +275,21 @@ def resnet_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, pre
         B = rec["name"]
         d, dz = dout, None
         for i in range(n_conv, 0, -1):
-            h, xs, hg, c, y, m, r = rec["convs"][i - 1]
+            h, xs, hg, c, y, st = rec["convs"][i - 1]
             last = i == n_conv
-            d, dzi = _bn_bwd(p, grads, B + f"bn{i}", d, y, c, m, r, training, need_dz=last)
+            d, dzi = _bn_bwd(p, grads, B + f"bn{i}", d, y, c, st, training, need_dz=last, sync=sync)
             if last:
                 dz = dzi
             d = _conv_bwd(d, h, xs, hg, prep[B + f"conv{i}.weight"], grads.get(B + f"conv{i}.weight"), True, chunk_images)
         if rec["down"] is not None:
-            dxs, dc, dm, dr = rec["down"]
-            dd, _ = _bn_bwd(p, grads, B + "downsample.1", dz, None, dc, dm, dr, training)
+            dxs, dc, ds = rec["down"]
+            dd, _ = _bn_bwd(p, grads, B + "downsample.1", dz, None, dc, ds, training, sync=sync)
             dz = _conv_bwd(dd, rec["x"], dxs, rec["geom"], prep[B + "downsample.0.weight"], grads.get(B + "downsample.0.weight"), True,
                            chunk_images)
         dout = ops.scaled_sum([d, dz], 1.0)
     if not stem_trains:
         return
-    x0, g0, c0, y0, m0, r0, g1, idx = stem
+    x0, g0, c0, y0, s0, g1, idx = stem
     dy0 = ops.maxpool3x3s2_bwd(dout, idx, *g1)
-    dc0, _ = _bn_bwd(p, grads, prefix + "bn1", dy0, y0, c0, m0, r0, training)
+    dc0, _ = _bn_bwd(p, grads, prefix + "bn1", dy0, y0, c0, s0, training, sync=sync)
     _conv_bwd(dc0, x0, None, g0, prep[prefix + "conv1.weight"], grads.get(prefix + "conv1.weight"), False, chunk_images)      # pixels take no gradient

@@ -800,6 +800,16 @@ class EarlyStop:
         Log.info("max eval Hit10 %.5f in epoch %d; early stop in epoch %d" % (self.best * 100, self.max_epoch, self.early_stop_epoch))
 
 
+def convert_sync_bn(args, model, world):
+    """``--sync_bn``: ``V/run.py:98`` -- every BatchNorm module becomes a ``SyncBatchNorm`` (same keys, same parameter objects), before the
+    DDP wrap.  Nothing at world size 1 (torch's ``SyncBatchNorm`` falls back to the plain path there too)."""
+    if getattr(args, "sync_bn", False) and world > 1:
+        model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)
+        Log.info("--sync_bn: %d BatchNorm modules synchronised over %d ranks" %
+                 (sum(isinstance(m, torch.nn.SyncBatchNorm) for m in model.modules()), world))
+    return model
+
+
 def train(args, use_modal, local_rank):
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -845,6 +855,7 @@ def train(args, use_modal, local_rank):
             stepper.load_scaler_state_dict(ckpt["scaler_state"])
         wrapped = model
     else:
+        model = convert_sync_bn(args, model, world)
         wrapped = DDP(model, device_ids=[local_rank], output_device=local_rank, find_unused_parameters=True) if world > 1 else model
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
         if vision and is_mae_run(args):      # V/run.py:121-135 over the reference's own (transformers 4.20.1) MAE names, none of which
@@ -1138,6 +1149,7 @@ def two_stage_features(args, item_content, item_num, vision, local_rank, rank):
     t0 = time.time()
     if vision and is_resnet_run(args):      # the pooled vector in front of fc: num_fc_ftr = 512 or 2048
         tower = Resnet_Encoder(image_net=build_vision_tower(args), compute_dtype=resolve_dtype(args))
+        tower = convert_sync_bn(args, tower, dist.get_world_size() if dist.is_initialized() else 1)      # (evaluation mode: no collective)
     elif vision and is_mae_run(args):
         tower = MAE_Encoder(image_net=build_vision_tower(args), item_dim=args.embedding_dim, compute_dtype=resolve_dtype(args))
     elif vision:      # Swin, or BEiT (the container decides)

@@ -556,7 +556,12 @@ int morec_im2col_nhwc(const void* x, void* col, int N, int H, int W, int Cin, in
  * (running) variances.  apply_fwd: y = relu?(gamma (x - mean) rstd + beta (+ res)), fp32, one rounding.
  * bwd_reduce: sums fp32 [2, C] = sum dz, sum dz xhat with dz = dy [y > 0] when y (the saved output of a ReLU) is given, else dy; per-slab
  * partials in ws (morec_bn_bwd_workspace_bytes) added in slab order.  bwd_apply: dx = gamma rstd (dz - sums[0] / rows - xhat sums[1] /
- * rows), or gamma rstd dz with sums == NULL (running statistics); dz (optional) receives dz itself. */
+ * rows), or gamma rstd dz with sums == NULL (running statistics); dz (optional) receives dz itself.
+ * Synchronised over data-parallel ranks: bwd_fold adds n gathered [2, C] sums (parts [n, 2, C]) in index order into sums [2, C], no
+ * atomics; bwd_apply_n is bwd_apply dividing by count[0] (count: fp32 [C] in device memory, the merged count row of all ranks' rows --
+ * every channel counts the same rows; exact below 2^24 rows) instead of by its own rows, so the host never learns that count; with
+ * count[0] == rows it writes bwd_apply's bits; sums is required.  The forward merge over ranks is
+ * morec_bn_merge itself over the gathered [W, 3, C] partials. */
 int morec_bn_slab_rows(void);
 int morec_bn_stats(const void* x, float* part, int rows, int C, int dtype, void* stream);
 int morec_bn_merge(const float* part, int nslabs, int C, float eps, float momentum, float* merged, float* mean, float* rstd,
@@ -569,6 +574,9 @@ int morec_bn_bwd_reduce(const void* dy, const void* y, const void* x, const floa
                         int C, int dtype, void* stream);
 int morec_bn_bwd_apply(const void* dy, const void* y, const void* x, const float* mean, const float* rstd, const float* gamma,
                        const float* sums, void* dx, void* dz, int rows, int C, int dtype, void* stream);
+int morec_bn_bwd_fold(const float* parts, int n, int C, float* sums, void* stream);
+int morec_bn_bwd_apply_n(const void* dy, const void* y, const void* x, const float* mean, const float* rstd, const float* gamma,
+                         const float* sums, const float* count, void* dx, void* dz, int rows, int C, int dtype, void* stream);
 /* MaxPool2d(3, stride 2, padding 1), C % 8 == 0: y [N Ho Wo, C] with Ho = (H - 1) / 2 + 1; idx uint8 [N Ho Wo, C] = the selected tap
  * kh * 3 + kw, the FIRST in scan order among equal values (torch's rule; ties are the normal case on post-ReLU input).  bwd: dx[N H W, C],
  * every pixel gathers dy from the windows that selected it. */
