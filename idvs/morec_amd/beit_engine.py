@@ -17,8 +17,8 @@ from dataclasses import dataclass
 
 import torch
 
-from . import ops
-from ._lib import ACT_GELU, DACT_MUL
+from . import engine, ops
+from ._lib import ACT_GELU
 from .engine import NO_DROP, DropCfg, linear_wgrad_, prepare_linear
 
 IN = "image_net."
@@ -109,13 +109,9 @@ def beit_prepare(p: dict, shape: BeitShape, dtype, prefix: str = IN, features_on
     pw = p[net + "embeddings.patch_embeddings.projection.weight"]
     prep = dict(patch=prepare_linear(pw.reshape(pw.shape[0], -1), dtype), layers=[])
     for l in range(shape.num_hidden_layers):
-        L = beit_layer_names(prefix, l)
-        A = L + "attention."
-        wqkv = torch.cat([p[A + f"{n}.weight"] for n in ("q_proj", "k_proj", "v_proj")], 0)
-        bq, bv = p[A + "q_proj.bias"], p[A + "v_proj.bias"]
-        bqkv = torch.cat([bq, torch.zeros_like(bq), bv], 0)      # k_proj has no bias
-        prep["layers"].append(dict(qkv=prepare_linear(wqkv, dtype), bqkv=bqkv, o=prepare_linear(p[A + "o_proj.weight"], dtype),
-                                   f1=prepare_linear(p[L + "mlp.fc1.weight"], dtype), f2=prepare_linear(p[L + "mlp.fc2.weight"], dtype)))
+        L = beit_layer_names(prefix, l)      # (k_proj has no bias: zeros in the fused one)
+        prep["layers"].append(engine.prepare_block(p, L + "attention.", L + "attention.o_proj.weight", L + "mlp.fc1.weight",
+                                                   L + "mlp.fc2.weight", dtype))
     if not features_only:
         prep["cls"] = prepare_linear(p[prefix + "classifier.weight"], dtype)
     return prep
@@ -142,9 +138,7 @@ def beit_forward(p: dict, prep, shape: BeitShape, pixels: torch.Tensor, dtype, n
     n_img = pixels.shape[0]
     eps = shape.layer_norm_eps
     C, heads, g = shape.hidden_size, shape.num_attention_heads, shape.grid
-    R = pixels.shape[1] if pixels.dtype == torch.uint8 else pixels.shape[2]
-    if R != shape.image_size:
-        raise ValueError(f"input image size {R} does not match the model's {shape.image_size} (interpolate_pos_encoding is not implemented)")
+    engine.check_image_size(pixels, shape.image_size)
     T = shape.num_patches + 1
     if pixels.dtype == torch.uint8:
         patches = ops.swin_patchify_u8(pixels.contiguous(), shape.patch_size, dtype)
@@ -178,9 +172,7 @@ def beit_forward(p: dict, prep, shape: BeitShape, pixels: torch.Tensor, dtype, n
                                                   save_z=False)
     if features_only:
         return pooled, None
-    D = prep["cls"].w.shape[0]
-    pre_c = torch.empty((n_img, D), device=x.device, dtype=dtype) if need_grad else None
-    item = ops.gemm_nt(pooled, prep["cls"].w, bias=p[prefix + "classifier.bias"], act=ACT_GELU, aux_out=pre_c)
+    item, pre_c = engine.head_forward(pooled, prep["cls"], p[prefix + "classifier.bias"], need_grad)
     saved = (shape, n_img, T, desc, key_keep, patches, saved_layers, pooled_raw, mean_f, rstd_f, pooled, pre_c) if need_grad else None
     return item, saved
 
@@ -192,10 +184,7 @@ def beit_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefi
     net = prefix + "beit."
     shape, n_img, T, desc, key_keep, patches, saved_layers, pooled_raw, mean_f, rstd_f, pooled, pre_c = saved
     C, g = shape.hidden_size, shape.grid
-    dv = ops.act_bwd(d_item.contiguous(), pre_c, ACT_GELU)
-    ops.colsum_(dv, grads[prefix + "classifier.bias"])
-    linear_wgrad_(dv, pooled, grads[prefix + "classifier.weight"])
-    dpooled = ops.gemm_nt(dv, prep["cls"].wt, K=dv.shape[1], N=C)
+    dpooled = engine.head_backward(d_item, pre_c, pooled, prep["cls"], grads[prefix + "classifier.weight"], grads[prefix + "classifier.bias"], C)
     dpr, _ = ops.layernorm_bwd(dpooled, None, pooled_raw, mean_f, rstd_f, p[net + "pooler.layernorm.weight"],
                                grads[net + "pooler.layernorm.weight"], grads[net + "pooler.layernorm.bias"])
     dout = ops.beit_pool_bwd(dpr, n_img, T)
@@ -207,10 +196,7 @@ def beit_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefi
         # out = h + dp2 * lambda_2 * (fc2(gelu(fc1(LN2(h)))) + b2)
         df = ops.layerscale_res_bwd(dout, f, p[L + "mlp.fc2.bias"], p[L + "lambda_2"], sc2, T, dlam=grads.get(L + "lambda_2"),
                                     dbias=grads[L + "mlp.fc2.bias"])
-        linear_wgrad_(df, gl, grads[L + "mlp.fc2.weight"])
-        du = ops.gemm_nt(df, w["f2"].wt, dact=DACT_MUL, dact_in=pre, K=df.shape[1], N=pre.shape[1], colsum_out=grads[L + "mlp.fc1.bias"])
-        linear_wgrad_(du, hn, grads[L + "mlp.fc1.weight"])
-        dhn = ops.gemm_nt(du, w["f1"].wt, K=du.shape[1], N=C)
+        dhn = engine.mlp_backward(df, w, gl, pre, hn, grads[L + "mlp.fc2.weight"], grads[L + "mlp.fc1.bias"], grads[L + "mlp.fc1.weight"], C)
         dh, _ = ops.layernorm_bwd(dhn, None, h, mean2, rstd2, p[L + "layernorm_after.weight"], grads[L + "layernorm_after.weight"],
                                   grads[L + "layernorm_after.bias"], dres=dout)
         # h = x + dp1 * lambda_1 * (o_proj(ctx) + bo)
@@ -218,20 +204,29 @@ def beit_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefi
                                     dbias=grads[A + "o_proj.bias"])
         linear_wgrad_(da, ctx, grads[A + "o_proj.weight"])
         dctx = ops.gemm_nt(da, w["o"].wt, K=da.shape[1], N=C)
-        gw = torch.zeros((3 * C, C), device=dctx.device, dtype=torch.float32)
-        gb = torch.zeros(3 * C, device=dctx.device, dtype=torch.float32)
+        gw, gb = engine.fused_qkv_grads(C, dctx.device)
         dtable = grads.get(L + TABLE)
         dqkv, dpos = ops.attn_bias_bwd(desc, qkv, key_keep, pos_bias, dctx, dbias=gb, need_dpos=dtable is not None)
         if dtable is not None:
             ops.beit_bias_reduce_(dpos, dtable, g)
         linear_wgrad_(dqkv, xn, gw)
-        for i, n in enumerate(("q_proj", "k_proj", "v_proj")):
-            grads[A + f"{n}.weight"] = gw[i * C:(i + 1) * C]
-        grads[A + "q_proj.bias"], grads[A + "v_proj.bias"] = gb[:C], gb[2 * C:]
+        engine.hand_out_qkv(grads, A, gw, gb, C, key_bias="absent")
         dxn = ops.gemm_nt(dqkv, w["qkv"].wt, K=dqkv.shape[1], N=C)
         dout, _ = ops.layernorm_bwd(dxn, None, x, mean1, rstd1, p[L + "layernorm_before.weight"], grads[L + "layernorm_before.weight"],
                                     grads[L + "layernorm_before.bias"], dres=dh)
-    de, _ = ops.mae_assemble_bwd(dout, n_img, T - 1, d_cls=grads[net + "embeddings.cls_token"].view(-1))
-    ops.colsum_(de, grads[net + "embeddings.patch_embeddings.projection.bias"])
-    gpw = grads[net + "embeddings.patch_embeddings.projection.weight"]
-    linear_wgrad_(de, patches, gpw.view(gpw.shape[0], -1))
+    engine.patch_embed_backward(dout, n_img, T - 1, patches, grads, net + "embeddings.")
+
+
+def _no_buffer(names, needs, c, plan):
+    skip = {n for l in range(c.shape.num_hidden_layers) for n in engine.qkv_names(beit_layer_names(c.prefix, l) + "attention.", key_bias="absent")}
+    # a frozen bias table or layer scale gets no buffer: its gradient work is skipped (``beit_backward``)
+    return skip | {n for n, nd in zip(names, needs) if not nd and n.endswith((TABLE, ".lambda_1", ".lambda_2"))}
+
+
+TOWER = engine.Tower(
+    prepare=lambda p, c, need_grad: beit_prepare(p, c.shape, c.dtype, c.prefix, features_only=c.features_only),
+    plan=engine.no_plan,
+    forward=lambda p, prep, x, c, need_grad: beit_forward(p, prep, c.shape, x, c.dtype, need_grad, c.prefix, c.drop, c.training,
+                                                          features_only=c.features_only),
+    backward=lambda p, prep, saved, d, grads, c: beit_backward(p, prep, saved, d, grads, c.prefix),
+    no_buffer=_no_buffer)

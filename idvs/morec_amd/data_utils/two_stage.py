@@ -14,89 +14,30 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .. import beit_engine, engine, mae_engine, ops, opt_engine, resnet_engine, swin_engine
-from ..model.encoders import Bert_Encoder, MAE_Encoder, Resnet_Encoder, Text_Encoder_mean, Vit_Encoder, resolve_fp32_gemm
+from .. import ops
+from ..model.encoders import Bert_Encoder, MAE_Encoder, Resnet_Encoder, Vit_Encoder, resolve_fp32_gemm
 from .dataset import collate_bce_batch
 from .metrics import _module
 
 
-def _text_features_fn(enc: Bert_Encoder):
-    te = enc.text_encoders["title"]
-    c = te.bert_model.config
-    if isinstance(te, Text_Encoder_mean):      # the OPT tower: the pooled mean in front of fc (opt_engine.opt_forward(features_only=True))
-        po = dict(te.named_parameters())
-        oprep = opt_engine.opt_prepare(po, te.bert_model.shape, te.compute_dtype, "", features_only=True)
+def _features_fn(enc):
+    """``enc`` (in evaluation mode) -> the function from a chunk of content to its fp32 feature rows: the tower's ``features_only`` pass,
+    prepared once.  Evaluation mode means no dropout or DropPath, the MAE tower's fixed seed (keyed by the row within the chunk) and
+    evaluation mask ratio, and the ResNet tower's running statistics, so the catalogue may be chunked."""
+    te = enc.text_encoders["title"] if isinstance(enc, Bert_Encoder) else enc
+    tower, call, params = te.tower_call(features_only=True)
+    p = dict(zip(call.names, params))
+    prep = tower.prepare(p, call, False)
 
-        def run_opt(news):
-            vecs = []
-            for name in enc.newsname:
-                text = torch.narrow(news, 1, enc.attributes2start[name], enc.attributes2length[name]).contiguous()
-                mean, _ = opt_engine.opt_forward(po, oprep, te.bert_model.shape, text, te.compute_dtype, False, "", unpad=te.unpad,
-                                                 features_only=True)
-                vecs.append(mean.float())
-            return vecs[0] if len(vecs) == 1 else torch.mean(torch.stack(vecs, dim=1), dim=1)
-        return run_opt
-    if getattr(te, "is_deberta", False):      # the DeBERTa tower: the [CLS] rows in front of fc (deberta_engine, features_only=True)
-        def run_deberta(news):
-            vecs = [te.encode(torch.narrow(news, 1, enc.attributes2start[name], enc.attributes2length[name]).contiguous(),
-                              features_only=True).float() for name in enc.newsname]
-            return vecs[0] if len(vecs) == 1 else torch.mean(torch.stack(vecs, dim=1), dim=1)
-        return run_deberta
-    p = {n: t for n, t in te.named_parameters() if ".pooler." not in n}
-    prep = engine.bert_prepare(p, c.num_hidden_layers, te.compute_dtype, "")
+    def run(x):
+        return tower.forward(p, prep, x, call, False)[0].float()
+    if te is enc:
+        return run
 
-    def run(news):
-        vecs = []
-        for name in enc.newsname:      # one pass of the shared encoder per attribute, averaged (model/encoders.py:127-137)
-            text = torch.narrow(news, 1, enc.attributes2start[name], enc.attributes2length[name]).contiguous()
-            cls, _ = engine.bert_forward(p, prep, text, c.num_attention_heads, te.compute_dtype, False, c.layer_norm_eps, te.mask_value, "",
-                                         res32=te.res32, features_only=True, **engine.bert_position_rule(c))
-            vecs.append(cls.float())
+    def run_text(news):      # one pass of the shared encoder per attribute, averaged (model/encoders.py:127-137)
+        vecs = [run(torch.narrow(news, 1, enc.attributes2start[name], enc.attributes2length[name]).contiguous()) for name in enc.newsname]
         return vecs[0] if len(vecs) == 1 else torch.mean(torch.stack(vecs, dim=1), dim=1)
-    return run
-
-
-def _vision_features_fn(enc: Vit_Encoder):
-    p = dict(enc.named_parameters())
-    shape = enc.image_net.shape
-    if getattr(enc, "is_beit", False):      # the pooler output = the classifier's input
-        bprep = beit_engine.beit_prepare(p, shape, enc.compute_dtype, "image_net.", features_only=True)
-
-        def run_beit(pixels):
-            pooled, _ = beit_engine.beit_forward(p, bprep, shape, pixels, enc.compute_dtype, False, "image_net.", features_only=True)
-            return pooled.float()
-        return run_beit
-    prep = swin_engine.swin_prepare(p, shape, enc.compute_dtype, "image_net.")
-
-    def run(pixels):
-        pooled, _ = swin_engine.swin_forward(p, prep, shape, pixels, enc.compute_dtype, False, "image_net.", features_only=True)
-        return pooled.float()
-    return run
-
-
-def _mae_features_fn(enc: MAE_Encoder):
-    p = dict(enc.named_parameters())
-    shape = enc.image_net.shape
-    prep = mae_engine.mae_prepare(p, shape, enc.compute_dtype, "", features_only=True)
-    seed, ratio = enc.masking()      # evaluation mode: the fixed seed, keyed by the row within the chunk
-
-    def run(pixels):
-        cls, _ = mae_engine.mae_forward(p, prep, shape, pixels, enc.compute_dtype, False, "", seed=seed, mask_ratio=ratio, features_only=True)
-        return cls.float()
-    return run
-
-
-def _resnet_features_fn(enc):
-    p = dict(enc.named_parameters())
-    bufs = dict(enc.named_buffers())
-    shape = enc.image_net.shape
-    prep = resnet_engine.resnet_prepare(p, shape, enc.compute_dtype, "image_net.", need_grad=False, features_only=True)
-
-    def run(pixels):      # evaluation mode: the running statistics, so the catalogue may be chunked
-        pooled, _ = resnet_engine.resnet_forward(p, bufs, prep, shape, pixels, enc.compute_dtype, False, "image_net.", training=False,
-                                                 features_only=True)
-        return pooled.float()
-    return run
+    return run_text
 
 
 def extract_item_features(encoder, item_content, batch_size, device=None):
@@ -108,17 +49,12 @@ def extract_item_features(encoder, item_content, batch_size, device=None):
     enc = _module(encoder)
     enc.eval()
     dev = torch.device(device) if device is not None else next(enc.parameters()).device
-    if isinstance(enc, Bert_Encoder):
-        run, mode = _text_features_fn(enc), resolve_fp32_gemm(enc.args)
-    elif isinstance(enc, Vit_Encoder):
-        run, mode = _vision_features_fn(enc), ops.FP32_GEMM
-    elif isinstance(enc, Resnet_Encoder):      # the globally pooled rows in front of fc
-        run, mode = _resnet_features_fn(enc), ops.FP32_GEMM
-    elif isinstance(enc, MAE_Encoder):      # the normalised [CLS] rows in front of cv_proj (image_net(x)[0][:, 0]): this project's definition
-        run, mode = _mae_features_fn(enc), ops.FP32_GEMM
-    else:
+    if not isinstance(enc, (Bert_Encoder, Vit_Encoder, Resnet_Encoder, MAE_Encoder)):
         raise TypeError(f"extract_item_features: no features_only path for {type(enc).__name__}; write the features to a .npy file and use "
                         "load_feature_table")
+    # text: the [CLS] rows (OPT: the pooled mean) in front of fc; Swin / BEiT / ResNet: the pooled rows in front of the classifier; MAE: the
+    # normalised [CLS] rows in front of cv_proj (image_net(x)[0][:, 0]): this project's definition
+    run, mode = _features_fn(enc), (resolve_fp32_gemm(enc.args) if isinstance(enc, Bert_Encoder) else ops.FP32_GEMM)
     lazy = hasattr(item_content, "device_batch")
     if not lazy:
         content = torch.as_tensor(np.asarray(item_content)) if not torch.is_tensor(item_content) else item_content

@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import engine, ops
-from ._lib import ACT_GELU, DACT_MUL
+from ._lib import ACT_GELU
 from .engine import NO_DROP, DropCfg, linear_wgrad_, prepare_linear
 
 TE = engine.TE
@@ -259,9 +259,7 @@ def deberta_forward(p: dict, prep, shape: DebertaShape, text: torch.Tensor, dtyp
     cls = ops.strided_rows_copy(x, torch.empty((Nc, H), device=x.device, dtype=dtype), Nc, H, T, 1)
     if features_only:
         return cls, None
-    D = prep["fc"].w.shape[0]
-    pre = torch.empty((Nc, D), device=x.device, dtype=dtype) if need_grad else None
-    item = ops.gemm_nt(cls, prep["fc"].w, bias=p[prefix + "fc.bias"], act=ACT_GELU, aux_out=pre)
+    item, pre = engine.head_forward(cls, prep["fc"], p[prefix + "fc.bias"], need_grad)
     saved = ((shape, Nc, T, ids32, keep, keep_rows, e, mean_e, rstd_e, rel_idx, ph, drop.site(0), saved_layers, cls, pre, grad_from)
              if need_grad else None)
     return item, saved
@@ -274,12 +272,10 @@ def deberta_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, pr
     shape, Nc, T, ids32, keep, keep_rows, e, mean_e, rstd_e, rel_idx, ph, seed_e, saved_layers, cls, pre, grad_from = saved
     H, heads = shape.hidden_size, shape.num_attention_heads
     n_layers = shape.num_hidden_layers
-    dv = ops.act_bwd(d_item.contiguous(), pre, ACT_GELU)
-    ops.colsum_(dv, grads[prefix + "fc.bias"])
-    linear_wgrad_(dv, cls, grads[prefix + "fc.weight"])
-    if grad_from >= n_layers and n_layers > 0:      # the whole of bert_model is frozen
+    frozen = grad_from >= n_layers and n_layers > 0      # the whole of bert_model is frozen
+    dcls = engine.head_backward(d_item, pre, cls, prep["fc"], grads[prefix + "fc.weight"], grads[prefix + "fc.bias"], H, need_dx=not frozen)
+    if frozen:
         return
-    dcls = ops.gemm_nt(dv, prep["fc"].wt, K=dv.shape[1], N=H)
     da = torch.zeros((Nc * T, H), device=dcls.device, dtype=dcls.dtype)      # only hidden[:, 0] is consumed
     ops.strided_rows_copy(dcls, da, Nc, H, 1, T)
     db = None
@@ -291,17 +287,14 @@ def deberta_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, pr
         desc, x0, R, PK, PQ, qkv, ctx, z1, mean1, rstd1, x1, u, gact, z2, mean2, rstd2, s_pos, s1, s2, dpos = saved_layers[l]
         dz2, dzd2 = ops.layernorm_bwd(da, db, z2, mean2, rstd2, w["ln2_g"], grads[L + "output.LayerNorm.weight"],
                                       grads[L + "output.LayerNorm.bias"], p_in=ph, seed_in=s2, dbias=grads[L + "output.dense.bias"])
-        linear_wgrad_(dzd2, gact, grads[L + "output.dense.weight"])
-        du = ops.gemm_nt(dzd2, w["f2"].wt, dact=DACT_MUL, dact_in=u, K=dzd2.shape[1], N=u.shape[1], colsum_out=grads[L + "intermediate.dense.bias"])
-        linear_wgrad_(du, x1, grads[L + "intermediate.dense.weight"])
-        dx1 = ops.gemm_nt(du, w["f1"].wt, K=du.shape[1], N=H)
+        dx1 = engine.mlp_backward(dzd2, w, gact, u, x1, grads[L + "output.dense.weight"], grads[L + "intermediate.dense.bias"],
+                                  grads[L + "intermediate.dense.weight"], H)
         dz1, dzd1 = ops.layernorm_bwd(dx1, dz2, z1, mean1, rstd1, w["ln1_g"], grads[L + "attention.output.LayerNorm.weight"],
                                       grads[L + "attention.output.LayerNorm.bias"], p_in=ph, seed_in=s1,
                                       dbias=grads[L + "attention.output.dense.bias"])
         linear_wgrad_(dzd1, ctx, grads[L + "attention.output.dense.weight"])
         dctx = ops.gemm_nt(dzd1, w["o"].wt, K=dzd1.shape[1], N=H)
-        gw = torch.zeros((3 * H, H), device=dctx.device, dtype=torch.float32)
-        gb = torch.zeros(3 * H, device=dctx.device, dtype=torch.float32)
+        gw, gb = engine.fused_qkv_grads(H, dctx.device)
         dqkv, dPK, dPQ = ops.disent_attn_bwd(desc, qkv, keep, PK, PQ, dctx, dbias=gb, need_dpos=dpos)
         linear_wgrad_(dqkv, x0, gw)
         engine.WgradStream.join(dqkv.device)      # gw is read (permuted) right below
@@ -332,3 +325,22 @@ def deberta_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, pr
     de, _ = ops.layernorm_bwd(da, db, e, mean_e, rstd_e, p[bm + "embeddings.LayerNorm.weight"], grads[bm + "embeddings.LayerNorm.weight"],
                               grads[bm + "embeddings.LayerNorm.bias"], p_out=ph, seed_out=seed_e)
     ops.scatter_add_rows_(de, ids32, grads[bm + "embeddings.word_embeddings.weight"], shape.pad_token_id)
+
+
+def _plan(trainable, c):
+    n = c.shape.num_hidden_layers
+    return dict(grad_from=deberta_grad_from(trainable, n, c.prefix), pos_layers=deberta_pos_layers(trainable, n, c.prefix))
+
+
+def _no_buffer(names, needs, c, plan):      # handed out as fresh tensors by ``deberta_backward``
+    return {deberta_layer_names(c.prefix, l) + "attention.self." + k for l in range(c.shape.num_hidden_layers)
+            for k in ("in_proj.weight", "q_bias", "v_bias")}
+
+
+TOWER = engine.Tower(
+    prepare=lambda p, c, need_grad: deberta_prepare(p, c.shape, c.dtype, c.prefix, features_only=c.features_only),
+    plan=_plan,
+    forward=lambda p, prep, x, c, need_grad, **plan: deberta_forward(p, prep, c.shape, x, c.dtype, need_grad, c.prefix, c.drop,
+                                                                     features_only=c.features_only, **plan),
+    backward=lambda p, prep, saved, d, grads, c: deberta_backward(p, prep, saved, d, grads, c.prefix),
+    no_buffer=_no_buffer)

@@ -14,7 +14,8 @@ from __future__ import annotations
 
 import math
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, field
+from typing import Any, Callable
 
 import torch
 
@@ -81,6 +82,37 @@ def prepare_linear(weight: torch.Tensor, dtype: torch.dtype, shadow: torch.Tenso
         return PreparedLinear(w, shadow_t)
     wt = ops.transpose(w.contiguous(), out_dtype=dtype)
     return PreparedLinear(w.contiguous(), wt)
+
+
+@dataclass(frozen=True)
+class TowerCall:
+    """What one call of an item tower (or of the SASRec user encoder) is made with.  ``shape``: the tower's shape object (None where it
+    has none); ``kw``: the tower's own keywords -- MAE ``noise`` / ``seed`` / ``mask_ratio``, OPT ``unpad``, ResNet ``bufs`` / ``sync``,
+    BERT ``heads`` / ``n_layers`` / ``eps`` / ``mask_value`` / ``res32`` / ``position`` (``bert_position_rule``), SASRec ``heads`` /
+    ``n_layers`` / ``res32``."""
+    names: tuple
+    shape: Any
+    dtype: torch.dtype
+    prefix: str
+    drop: DropCfg = NO_DROP
+    training: bool = False
+    features_only: bool = False
+    kw: dict = field(default_factory=dict)
+
+
+@dataclass(frozen=True)
+class Tower:
+    """An item tower as ``functional.TowerFn`` and ``data_utils.two_stage`` drive it: thin adapters over the engine module's public
+    ``*_prepare`` / ``*_forward`` / ``*_backward``.  Each engine module exports one instance, ``TOWER``."""
+    prepare: Callable       # (p, call, need_grad) -> prep
+    plan: Callable          # (trainable_names, call) -> the forward keywords decided by what trains
+    forward: Callable       # (p, prep, x, call, need_grad, **plan) -> (out, saved)
+    backward: Callable      # (p, prep, saved, d_out, grads, call)
+    no_buffer: Callable     # (names, needs, call, plan) -> the names that get no zero-filled fp32 gradient buffer
+
+
+def no_plan(trainable_names, call) -> dict:
+    return {}
 
 
 def _cdiv(a: int, b: int) -> int:
@@ -177,6 +209,94 @@ def linear_wgrad_(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, dyt=None,
 
 
 # ---------------------------------------------------------------------------------------------------------
+# straight-line fragments every tower's engine is composed of
+# ---------------------------------------------------------------------------------------------------------
+QKV = ("q_proj", "k_proj", "v_proj")
+
+
+def head_forward(x: torch.Tensor, lin: PreparedLinear, bias, need_grad: bool):
+    """The GELU projection head ``GELU(x W^T + b)`` -> (item, pre); ``pre``: the pre-activation the backward takes, None without one."""
+    pre = torch.empty((x.shape[0], lin.w.shape[0]), device=x.device, dtype=x.dtype) if need_grad else None
+    return ops.gemm_nt(x, lin.w, bias=bias, act=ACT_GELU, aux_out=pre), pre
+
+
+def head_backward(d_item, pre, x, lin: PreparedLinear, g_weight, g_bias, n_in: int, need_dx: bool = True):
+    """Backward of ``head_forward``: adds into the fp32 buffers ``g_bias`` / ``g_weight`` (None: frozen, skipped) and returns dx
+    [rows, n_in]; ``need_dx=False`` (nothing trainable below the head) ends before the data-gradient GEMM and returns None."""
+    dv = ops.act_bwd(d_item.contiguous(), pre, ACT_GELU)
+    if g_bias is not None:
+        ops.colsum_(dv, g_bias)
+    if g_weight is not None:
+        linear_wgrad_(dv, x, g_weight)
+    return ops.gemm_nt(dv, lin.wt, K=dv.shape[1], N=n_in) if need_dx else None
+
+
+def prepare_block(p: dict, A: str, o: str, f1: str, f2: str, dtype, shadow: dict | None = None) -> dict:
+    """The four Linears of a block: ``qkv`` from the q / k / v projections under ``A`` (or the caller's ``qkv_fused`` arena views), the
+    fused bias ``bqkv`` (a projection without a bias contributes zeros), and the weights named ``o`` / ``f1`` / ``f2``."""
+    sh = shadow or {}
+    wqkv, bqkv = p.get(A + "qkv_fused.weight"), p.get(A + "qkv_fused.bias")
+    if wqkv is None:
+        wqkv = torch.cat([p[A + n + ".weight"] for n in QKV], 0)
+        bq = p[A + "q_proj.bias"]
+        bqkv = torch.cat([p[A + n + ".bias"] if A + n + ".bias" in p else torch.zeros_like(bq) for n in QKV], 0)
+    out = dict(qkv=prepare_linear(wqkv, dtype, sh.get(A + "qkv_fused.weight"), sh.get(A + "qkv_fused.weight" + "^T")), bqkv=bqkv)
+    for key, k in (("o", o), ("f1", f1), ("f2", f2)):
+        out[key] = prepare_linear(p[k], dtype, sh.get(k), sh.get(k + "^T"))
+    return out
+
+
+def fused_qkv_grads(C: int, device):
+    """Fresh zeroed fp32 (gw [3C, C], gb [3C]): the fused q | k | v gradient a block's backward accumulates into."""
+    return torch.zeros((3 * C, C), device=device, dtype=torch.float32), torch.zeros(3 * C, device=device, dtype=torch.float32)
+
+
+def qkv_names(A: str, names=QKV, key_bias: str = "kept"):
+    """The parameter names ``hand_out_qkv`` assigns: they get no zero buffer of their own."""
+    return [A + n + k for i, n in enumerate(names) for k in (".weight", ".bias") if not (i == 1 and k == ".bias" and key_bias == "absent")]
+
+
+def hand_out_qkv(grads: dict, A: str, gw, gb, C: int, names=QKV, key_bias: str = "kept"):
+    """Hand the row blocks of the fused (gw, gb) out as the gradients of the three projections under ``A`` (views, no arithmetic).
+    ``key_bias``: what becomes of the key third of gb -- "kept" as the column sums are, "zero", or "absent" (no such parameter: the third
+    is discarded)."""
+    for i, n in enumerate(names):
+        grads[A + n + ".weight"] = gw[i * C:(i + 1) * C]
+        if i != 1 or key_bias != "absent":
+            grads[A + n + ".bias"] = gb[i * C:(i + 1) * C]
+    if key_bias == "zero":
+        # The key bias adds q_i . b to every score of row i: a per-row constant that the softmax removes (under a causal and a key
+        # mask as without them), so its gradient is exactly zero (BEiT drops the parameter for this reason).  The column sums of dK only
+        # hold the rounding noise of the attention backward (16-bit: ~1e-3 in norm, which Adam would normalise into steps of the
+        # learning rate); the exact value is written.
+        gb[C:2 * C].zero_()
+
+
+def mlp_backward(d, w: dict, g, pre, hn, g_fc2_w, g_fc1_b, g_fc1_w, C: int):
+    """The MLP branch ``fc2(act(fc1(hn)))`` backwards from ``d``, the gradient at fc2's output: ``g`` the activation, ``pre`` its saved
+    derivative, ``w`` the block's prepared Linears; adds into the three fp32 buffers and returns d(hn) [rows, C]."""
+    linear_wgrad_(d, g, g_fc2_w)
+    du = ops.gemm_nt(d, w["f2"].wt, dact=DACT_MUL, dact_in=pre, K=d.shape[1], N=pre.shape[1], colsum_out=g_fc1_b)   # x act', + d(b1)
+    linear_wgrad_(du, hn, g_fc1_w)
+    return ops.gemm_nt(du, w["f1"].wt, K=du.shape[1], N=C)
+
+
+def check_image_size(pixels: torch.Tensor, image_size: int):
+    R = pixels.shape[1] if pixels.dtype == torch.uint8 else pixels.shape[2]
+    if R != image_size:
+        raise ValueError(f"input image size {R} does not match the model's {image_size} (interpolate_pos_encoding is not implemented)")
+
+
+def patch_embed_backward(dout, n_img: int, n_patch: int, patches, grads: dict, E: str):
+    """From the gradient at the assembled [CLS] + patch rows: writes ``E + "cls_token"``, adds into the patch projection's bias and
+    weight (``E + "patch_embeddings.projection.*"``); the pixels take no gradient."""
+    de, _ = ops.mae_assemble_bwd(dout, n_img, n_patch, d_cls=grads[E + "cls_token"].view(-1))
+    ops.colsum_(de, grads[E + "patch_embeddings.projection.bias"])
+    gpw = grads[E + "patch_embeddings.projection.weight"]
+    linear_wgrad_(de, patches, gpw.view(gpw.shape[0], -1))
+
+
+# ---------------------------------------------------------------------------------------------------------
 # one transformer layer
 # ---------------------------------------------------------------------------------------------------------
 # res32 modes: the fp32 residual stream between the LayerNorms of the encoder layers is handed on as ``ops.PreLN`` (the previous LayerNorm's
@@ -229,10 +349,7 @@ def layer_backward(cfg: LayerCfg, w: dict, saved, dx2_a, dx2_b, g: dict, need_dx
     # dz* = gradient at the residual sum (also the residual branch's gradient); dzd* = after the sub-layer's dropout
     dz2, dzd2 = ops.layernorm_bwd(dx2_a, dx2_b, z2, mean2, rstd2, w["ln2_g"], g["ln2_g"], g["ln2_b"], p_in=ph, seed_in=s2,
                                   dbias=g.get("b2"))
-    linear_wgrad_(dzd2, gact, g["f2"])
-    du = ops.gemm_nt(dzd2, w["f2"].wt, dact=DACT_MUL, dact_in=u, K=dzd2.shape[1], N=u.shape[1], colsum_out=g.get("b1"))   # x act', + d(b1)
-    linear_wgrad_(du, x1, g["f1"])
-    dx1 = ops.gemm_nt(du, w["f1"].wt, K=du.shape[1], N=x1.shape[1])
+    dx1 = mlp_backward(dzd2, w, gact, u, x1, g["f2"], g.get("b1"), g["f1"], x1.shape[1])
     dz1, dzd1 = ops.layernorm_bwd(dx1, dz2, z1, mean1, rstd1, w["ln1_g"], g["ln1_g"], g["ln1_b"], p_in=ph, seed_in=s1,
                                   dbias=g.get("bo"))
     linear_wgrad_(dzd1, ctx, g["o"])
@@ -308,10 +425,7 @@ def layer_backward_cls(cfg: LayerCfg, w: dict, saved, dx2_c: torch.Tensor, g: di
     H, T = cfg.H, cfg.T
     dz2, dzd2 = ops.layernorm_bwd(dx2_c, None, z2, mean2, rstd2, w["ln2_g"], g["ln2_g"], g["ln2_b"], p_in=ph, seed_in=s2,
                                   dbias=g.get("b2"))
-    linear_wgrad_(dzd2, gact, g["f2"])
-    du = ops.gemm_nt(dzd2, w["f2"].wt, dact=DACT_MUL, dact_in=u, K=dzd2.shape[1], N=u.shape[1], colsum_out=g.get("b1"))   # x act', + d(b1)
-    linear_wgrad_(du, x1, g["f1"])
-    dx1 = ops.gemm_nt(du, w["f1"].wt, K=du.shape[1], N=H)
+    dx1 = mlp_backward(dzd2, w, gact, u, x1, g["f2"], g.get("b1"), g["f1"], H)
     dz1, dzd1 = ops.layernorm_bwd(dx1, dz2, z1, mean1, rstd1, w["ln1_g"], g["ln1_g"], g["ln1_b"], p_in=ph, seed_in=s1,
                                   dbias=g.get("bo"))
     linear_wgrad_(dzd1, ctx_c, g["o"])
@@ -341,6 +455,11 @@ def sasrec_layer_names(l: int, prefix: str = UE):
     a = prefix + f"transformer_blocks.{l}.multi_head_attention."
     f = prefix + f"transformer_blocks.{l}.feed_forward."
     return a, f
+
+
+def sasrec_no_buffer(n_layers: int, prefix: str = UE):
+    """The names ``sasrec_backward`` hands out as row views of a fresh fused buffer: they get no zero buffer of their own."""
+    return {sasrec_layer_names(l, prefix)[0] + w + ".weight" for l in range(n_layers) for w in ("w_Q", "w_K", "w_V")}
 
 
 def sasrec_prepare(p: dict, n_layers: int, dtype, prefix: str = UE, shadow: dict | None = None):
@@ -415,6 +534,7 @@ def sasrec_backward(p: dict, prep, saved, dout: torch.Tensor, grads: dict, prefi
 # BERT text encoder (T/model/encoders.py:53-70 + HF BertModel)
 # ---------------------------------------------------------------------------------------------------------
 TE = "bert_encoder.text_encoders.title."
+BERT_QKV = ("query", "key", "value")
 # encoder layers on real tokens only (see bert_forward); MOREC_UNPAD=0 / bench.py --padded keep all T positions of every title
 UNPAD_DEFAULT = os.environ.get("MOREC_UNPAD", "1") != "0"
 
@@ -633,9 +753,7 @@ def bert_forward(p: dict, prep, text: torch.Tensor, heads: int, dtype, need_grad
         return cls, None
     if on_use is not None:
         on_use("head")
-    D = prep["fc"].w.shape[0]
-    pre = torch.empty((Nc, D), device=cls.device, dtype=dtype) if need_grad else None
-    item = ops.gemm_nt(cls, prep["fc"].w, bias=p[prefix + "fc.bias"], act=ACT_GELU, aux_out=pre)
+    item, pre = head_forward(cls, prep["fc"], p[prefix + "fc.bias"], need_grad)
     saved = (cfg, ids32, z_e, mean_e, rstd_e, saved_layers, cls, pre, Nc, T, H, drop, tok_idx, grad_from, order, inv, pos_rule) if need_grad else None
     return item, saved
 
@@ -647,16 +765,12 @@ def bert_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefi
     bm = prefix + "bert_model."
     cfg, ids32, z_e, mean_e, rstd_e, saved_layers, cls, pre, Nc, T, H, drop, tok_idx, grad_from, order, inv, pos_rule = saved
     n_layers = len(prep["layers"])
-    dv = ops.act_bwd(d_item.contiguous(), pre, ACT_GELU)
-    ops.colsum_(dv, grads[prefix + "fc.bias"])
-    linear_wgrad_(dv, cls, grads[prefix + "fc.weight"])
-    if grad_from >= n_layers and n_layers > 0:      # the whole of bert_model is frozen: the backward ends at the projection head
-        if on_ready is not None:
-            on_ready("head")
-        return
-    dcls = ops.gemm_nt(dv, prep["fc"].wt, K=dv.shape[1], N=H)
+    frozen = grad_from >= n_layers and n_layers > 0      # the whole of bert_model is frozen: the backward ends at the projection head
+    dcls = head_backward(d_item, pre, cls, prep["fc"], grads[prefix + "fc.weight"], grads[prefix + "fc.bias"], H, need_dx=not frozen)
     if on_ready is not None:
         on_ready("head")
+    if frozen:
+        return
     da, db = None, None
     if n_layers == 0:
         da = torch.zeros((Nc * T, H), device=dcls.device, dtype=dcls.dtype)
@@ -666,8 +780,7 @@ def bert_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefi
         dqkv, dbqkv = grads.get(L + "qkv_fused.weight"), grads.get(L + "qkv_fused.bias")
         fused = dqkv is not None
         if not fused:
-            dqkv = torch.zeros((3 * H, H), device=dcls.device, dtype=torch.float32)
-            dbqkv = torch.zeros(3 * H, device=dcls.device, dtype=torch.float32)
+            dqkv, dbqkv = fused_qkv_grads(H, dcls.device)
         g = dict(qkv=dqkv, bqkv=dbqkv, o=grads[L + "attention.output.dense.weight"], bo=grads[L + "attention.output.dense.bias"],
                  ln1_g=grads[L + "attention.output.LayerNorm.weight"], ln1_b=grads[L + "attention.output.LayerNorm.bias"],
                  f1=grads[L + "intermediate.dense.weight"], b1=grads[L + "intermediate.dense.bias"],
@@ -679,9 +792,7 @@ def bert_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefi
         else:
             da, db = layer_backward(cfg, prep["layers"][l], saved_layers[l], da, db, g, need_dx)
         if not fused:
-            for i, n in enumerate(("query", "key", "value")):
-                grads[L + f"attention.self.{n}.weight"] = dqkv[i * H:(i + 1) * H]
-                grads[L + f"attention.self.{n}.bias"] = dbqkv[i * H:(i + 1) * H]
+            hand_out_qkv(grads, L + "attention.self.", dqkv, dbqkv, H, BERT_QKV)
         if on_ready is not None:
             on_ready(("layer", l))
     if grad_from >= 0:        # frozen embeddings: no embedding-LayerNorm backward, no word / position / type scatter
@@ -713,6 +824,26 @@ def bert_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefi
     ops.bert_embed_bwd_(ids32, dz_e, grads[bm + "embeddings.word_embeddings.weight"],
                         grads[bm + "embeddings.position_embeddings.weight"],
                         grads[bm + "embeddings.token_type_embeddings.weight"][0], pad_id, T, order)
+
+
+def _bert_tower_forward(p, prep, text, c: TowerCall, need_grad, **plan):
+    k = c.kw
+    return bert_forward(p, prep, text, k["heads"], c.dtype, need_grad, k["eps"], k["mask_value"], c.prefix, c.drop, res32=k["res32"],
+                        features_only=c.features_only, **k["position"], **plan)
+
+
+def _bert_no_buffer(names, needs, c: TowerCall, plan):
+    skip = {n for l in range(c.kw["n_layers"]) for n in qkv_names(c.prefix + f"bert_model.encoder.layer.{l}.attention.self.", BERT_QKV)}
+    return skip | {n for n in names if not bert_needs_grad_buffer(n, plan["grad_from"], c.prefix)}      # never reached by the backward
+
+
+TOWER = Tower(
+    prepare=lambda p, c, need_grad: bert_prepare(p, c.kw["n_layers"], c.dtype, c.prefix),
+    # the backward stops at the lowest trainable point of the tower (T/run.py:73-75 freezes a prefix by parameter index)
+    plan=lambda trainable, c: dict(grad_from=bert_grad_from(trainable, c.kw["n_layers"], c.prefix)),
+    forward=_bert_tower_forward,
+    backward=lambda p, prep, saved, d, grads, c: bert_backward(p, prep, saved, d, grads, c.prefix),
+    no_buffer=_bert_no_buffer)
 
 
 # ---------------------------------------------------------------------------------------------------------

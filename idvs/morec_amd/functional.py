@@ -8,7 +8,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from . import beit_engine, deberta_engine, engine, mae_engine, ops, opt_engine, resnet_engine, swin_engine
+from . import engine, ops
 
 
 def _zeros_like_params(names, params, skip=()):
@@ -16,268 +16,72 @@ def _zeros_like_params(names, params, skip=()):
 
 
 class SasrecFn(torch.autograd.Function):
-    """``User_Encoder.forward`` (``T/model/encoders.py:23-28``)."""
+    """``User_Encoder.forward`` (``T/model/encoders.py:23-28``).  ``call``: an ``engine.TowerCall`` with ``kw`` = heads, n_layers, res32
+    (the autocast data flow: fp32 residual stream, ``engine.LayerCfg.res32``)."""
 
     @staticmethod
-    def forward(ctx, x_in, log_mask, cfg, *params):
-        names, heads, n_layers, dtype, prefix, drop = cfg[:6]
-        res32 = bool(cfg[6]) if len(cfg) > 6 else False      # the autocast data flow: fp32 residual stream (engine.LayerCfg.res32)
-        p = dict(zip(names, params))
+    def forward(ctx, x_in, log_mask, call, *params):
+        kw = call.kw
+        p = dict(zip(call.names, params))
         need = any(ctx.needs_input_grad)
         x = x_in.contiguous()
-        if x.dtype != dtype:
-            x = ops.cast(x, dtype)
-        prep = engine.sasrec_prepare(p, n_layers, dtype, prefix)
-        out, saved = engine.sasrec_forward(p, prep, x, log_mask, heads, need, prefix, drop, res32=res32)
-        ctx.stuff = (p, prep, saved, names, prefix, x_in.dtype, tuple(x_in.shape))
+        if x.dtype != call.dtype:
+            x = ops.cast(x, call.dtype)
+        prep = engine.sasrec_prepare(p, kw["n_layers"], call.dtype, call.prefix)
+        out, saved = engine.sasrec_forward(p, prep, x, log_mask, kw["heads"], need, call.prefix, call.drop, res32=kw["res32"])
+        ctx.stuff = (p, prep, saved, call, x_in.dtype, tuple(x_in.shape))
         ctx.fp32_gemm = ops.FP32_GEMM
         return out.view(x_in.shape)
 
     @staticmethod
     def backward(ctx, dout):
-        p, prep, saved, names, prefix, in_dtype, in_shape = ctx.stuff
+        p, prep, saved, call, in_dtype, in_shape = ctx.stuff
         ctx.stuff = None
-        qkv = {prefix + f"transformer_blocks.{l}.multi_head_attention.{w}.weight" for l in range(len(prep))
-               for w in ("w_Q", "w_K", "w_V")}
-        grads = _zeros_like_params(names, [p[n] for n in names], skip=qkv)
+        names = call.names
+        grads = _zeros_like_params(names, [p[n] for n in names], skip=engine.sasrec_no_buffer(len(prep), call.prefix))
         d = dout.contiguous().view(-1, in_shape[-1])
         with ops.fp32_gemm_mode(ctx.fp32_gemm):
-            dx = engine.sasrec_backward(p, prep, saved, d, grads, prefix)
+            dx = engine.sasrec_backward(p, prep, saved, d, grads, call.prefix)
             engine.WgradStream.join(d.device)      # autograd consumers (DDP hooks, the optimizer) read the gradients on this stream
         if dx.dtype != in_dtype:
             dx = ops.cast(dx, in_dtype)
         return (dx.view(in_shape), None, None) + tuple(grads[n] for n in names)
 
 
-class BertEncoderFn(torch.autograd.Function):
-    """``Text_Encoder.forward`` (``T/model/encoders.py:63-70``) over HF ``BertModel`` arithmetic."""
+class TowerFn(torch.autograd.Function):
+    """An item tower as one autograd node: ``TowerFn.apply(x, tower, call, *params)`` with ``tower`` the engine module's ``engine.Tower``
+    (``engine.TOWER``: BERT / RoBERTa, ``swin_engine.TOWER``, ...), ``call`` an ``engine.TowerCall`` and ``params`` in the order of
+    ``call.names``.  The backward ends where ``tower.plan`` says, given what trains; a parameter without ``requires_grad`` gets None, and
+    a trainable one the backward left no gradient for is an error.  ``call.features_only``: the rows in front of the projection head,
+    non-differentiable."""
 
     @staticmethod
-    def forward(ctx, text, cfg, *params):
-        names, heads, n_layers, dtype, prefix, eps, mask_value, drop = cfg[:8]
-        res32 = bool(cfg[8]) if len(cfg) > 8 else False
-        pos_kw = dict(cfg[9]) if len(cfg) > 9 else {}      # position_rule / pad_id (``engine.bert_position_rule``); BERT's when absent
-        p = dict(zip(names, params))
-        need = any(ctx.needs_input_grad)
-        prep = engine.bert_prepare(p, n_layers, dtype, prefix)
-        # the backward stops at the lowest trainable point of the tower (T/run.py:73-75 freezes a prefix by parameter index)
-        grad_from = engine.bert_grad_from([n for n, nd in zip(names, ctx.needs_input_grad[2:]) if nd], n_layers, prefix)
-        item, saved = engine.bert_forward(p, prep, text, heads, dtype, need, eps, mask_value, prefix, drop, grad_from=grad_from, res32=res32,
-                                          **pos_kw)
-        ctx.stuff = (p, prep, saved, names, prefix, grad_from)
-        ctx.needs = ctx.needs_input_grad
+    def forward(ctx, x, tower, call, *params):
+        p = dict(zip(call.names, params))
+        needs = ctx.needs_input_grad[3:]
+        need = any(ctx.needs_input_grad) and not call.features_only
+        prep = tower.prepare(p, call, need)
+        plan = tower.plan([n for n, nd in zip(call.names, needs) if nd], call)
+        out, saved = tower.forward(p, prep, x, call, need, **plan)
+        ctx.stuff = (tower, call, p, prep, saved, plan, needs)
         ctx.fp32_gemm = ops.FP32_GEMM
-        return item
-
-    @staticmethod
-    def backward(ctx, d_item):
-        p, prep, saved, names, prefix, grad_from = ctx.stuff
-        ctx.stuff = None
-        bm = prefix + "bert_model."
-        skip = {bm + f"encoder.layer.{l}.attention.self.{n}.{k}" for l in range(len(prep["layers"]))
-                for n in ("query", "key", "value") for k in ("weight", "bias")}
-        skip |= {n for n in names if not engine.bert_needs_grad_buffer(n, grad_from, prefix)}    # never reached by the backward
-        grads = _zeros_like_params(names, [p[n] for n in names], skip=skip)
-        with ops.fp32_gemm_mode(ctx.fp32_gemm):
-            engine.bert_backward(p, prep, saved, d_item.contiguous(), grads, prefix)
-            engine.WgradStream.join(d_item.device)
-        needs = ctx.needs[2:]
-        return (None, None) + tuple(grads.get(n) if nd else None for n, nd in zip(names, needs))
-
-
-class SwinEncoderFn(torch.autograd.Function):
-    """``Vit_Encoder.forward`` (``V/model/encoders.py:30-31``) over HF ``SwinForImageClassification`` arithmetic."""
-
-    @staticmethod
-    def forward(ctx, pixels, cfg, *params):
-        names, shape, dtype, prefix, drop, training = cfg
-        p = dict(zip(names, params))
-        need = any(ctx.needs_input_grad)
-        prep = swin_engine.swin_prepare(p, shape, dtype, prefix)
-        item, saved = swin_engine.swin_forward(p, prep, shape, pixels, dtype, need, prefix, drop, training)
-        ctx.stuff = (p, prep, saved, names, prefix, shape)
-        ctx.needs = ctx.needs_input_grad
-        ctx.fp32_gemm = ops.FP32_GEMM
-        return item
-
-    @staticmethod
-    def backward(ctx, d_item):
-        p, prep, saved, names, prefix, shape = ctx.stuff
-        ctx.stuff = None
-        qkv = {swin_engine.swin_layer_names(prefix, s, b) + f"attention.{n}.{k}" for s, depth in enumerate(shape.depths)
-               for b in range(depth) for n in ("q_proj", "k_proj", "v_proj") for k in ("weight", "bias")}
-        grads = _zeros_like_params(names, [p[n] for n in names], skip=qkv)
-        with ops.fp32_gemm_mode(ctx.fp32_gemm):
-            swin_engine.swin_backward(p, prep, saved, d_item.contiguous(), grads, prefix)
-            engine.WgradStream.join(d_item.device)
-        needs = ctx.needs[2:]
-        return (None, None) + tuple(grads[n] if nd else None for n, nd in zip(names, needs))
-
-
-class MaeEncoderFn(torch.autograd.Function):
-    """``MAE_Encoder.forward`` (``V/model/encoders.py:20-21``) over HF ``ViTMAEModel`` arithmetic.  ``cfg = (names, shape, dtype, prefix,
-    noise, seed, mask_ratio)``: ``noise`` fp32 [n_img, N] or None (the kept patches are then drawn from ``seed``)."""
-
-    @staticmethod
-    def forward(ctx, pixels, cfg, *params):
-        names, shape, dtype, prefix, noise, seed, mask_ratio = cfg
-        p = dict(zip(names, params))
-        need = any(ctx.needs_input_grad)
-        prep = mae_engine.mae_prepare(p, shape, dtype, prefix)
-        item, saved = mae_engine.mae_forward(p, prep, shape, pixels, dtype, need, prefix, noise=noise, seed=seed, mask_ratio=mask_ratio)
-        ctx.stuff = (p, prep, saved, names, prefix, shape)
-        ctx.needs = ctx.needs_input_grad
-        ctx.fp32_gemm = ops.FP32_GEMM
-        return item
-
-    @staticmethod
-    def backward(ctx, d_item):
-        p, prep, saved, names, prefix, shape = ctx.stuff
-        ctx.stuff = None
-        skip = {mae_engine.mae_layer_names(prefix, l) + f"attention.{n}.{k}" for l in range(shape.num_hidden_layers)
-                for n in ("q_proj", "k_proj", "v_proj") for k in ("weight", "bias")}
-        skip.add(prefix + "image_net.embeddings.position_embeddings")      # frozen in HF: no gradient
-        grads = _zeros_like_params(names, [p[n] for n in names], skip=skip)
-        with ops.fp32_gemm_mode(ctx.fp32_gemm):
-            mae_engine.mae_backward(p, prep, saved, d_item.contiguous(), grads, prefix)
-            engine.WgradStream.join(d_item.device)
-        needs = ctx.needs[2:]
-        return (None, None) + tuple(grads.get(n) if nd else None for n, nd in zip(names, needs))
-
-
-class OptEncoderFn(torch.autograd.Function):
-    """``Text_Encoder_mean.forward`` (``T/model/encoders.py:41-50``) over HF ``OPTModel`` arithmetic.  ``cfg = (names, shape, dtype,
-    prefix, drop, unpad, features_only)``.  The backward ends at the lowest trainable layer (``opt_engine.opt_grad_from``); above it every
-    gradient is computed and a frozen parameter's is not handed out."""
-
-    @staticmethod
-    def forward(ctx, text, cfg, *params):
-        names, shape, dtype, prefix, drop, unpad, features_only = cfg
-        p = dict(zip(names, params))
-        need = any(ctx.needs_input_grad) and not features_only
-        prep = opt_engine.opt_prepare(p, shape, dtype, prefix, features_only=features_only)
-        # the backward stops at the lowest trainable point of the tower (T/run.py:73-75 freezes a prefix by parameter index)
-        grad_from = opt_engine.opt_grad_from([n for n, nd in zip(names, ctx.needs_input_grad[2:]) if nd], shape.num_hidden_layers, prefix)
-        out, saved = opt_engine.opt_forward(p, prep, shape, text, dtype, need, prefix, drop, unpad=unpad, features_only=features_only,
-                                            grad_from=grad_from)
-        ctx.stuff = (p, prep, saved, names, prefix, shape)
-        ctx.needs = ctx.needs_input_grad
-        ctx.fp32_gemm = ops.FP32_GEMM
-        if features_only:
+        if call.features_only:
             ctx.mark_non_differentiable(out)
         return out
 
     @staticmethod
-    def backward(ctx, d_item):
-        p, prep, saved, names, prefix, shape = ctx.stuff
+    def backward(ctx, d_out):
+        tower, call, p, prep, saved, plan, needs = ctx.stuff
         ctx.stuff = None
-        skip = {opt_engine.opt_layer_names(prefix, l) + f"self_attn.{n}.{k}" for l in range(shape.num_hidden_layers)
-                for n in ("q_proj", "k_proj", "v_proj") for k in ("weight", "bias")}
-        grads = _zeros_like_params(names, [p[n] for n in names], skip=skip)
+        names = call.names
+        grads = _zeros_like_params(names, [p[n] for n in names], skip=tower.no_buffer(names, needs, call, plan))
         with ops.fp32_gemm_mode(ctx.fp32_gemm):
-            opt_engine.opt_backward(p, prep, saved, d_item.contiguous(), grads, prefix)
-            engine.WgradStream.join(d_item.device)
-        needs = ctx.needs[2:]
-        return (None, None) + tuple(grads.get(n) if nd else None for n, nd in zip(names, needs))
-
-
-class DebertaEncoderFn(torch.autograd.Function):
-    """``Text_Encoder.forward`` (``GELU(fc(hidden[:, 0]))``) over HF ``DebertaModel`` arithmetic (``deberta_engine``).  ``cfg = (names,
-    shape, dtype, prefix, drop, features_only)``.  The backward ends at the lowest trainable layer (``deberta_grad_from``) and forms
-    dPK / dPQ only in the layers ``deberta_pos_layers`` names; a frozen parameter's gradient is not handed out."""
-
-    @staticmethod
-    def forward(ctx, text, cfg, *params):
-        names, shape, dtype, prefix, drop, features_only = cfg
-        p = dict(zip(names, params))
-        need = any(ctx.needs_input_grad) and not features_only
-        prep = deberta_engine.deberta_prepare(p, shape, dtype, prefix, features_only=features_only)
-        trainable = [n for n, nd in zip(names, ctx.needs_input_grad[2:]) if nd]
-        grad_from = deberta_engine.deberta_grad_from(trainable, shape.num_hidden_layers, prefix)
-        pos_layers = deberta_engine.deberta_pos_layers(trainable, shape.num_hidden_layers, prefix)
-        out, saved = deberta_engine.deberta_forward(p, prep, shape, text, dtype, need, prefix, drop, features_only=features_only,
-                                                    grad_from=grad_from, pos_layers=pos_layers)
-        ctx.stuff = (p, prep, saved, names, prefix, shape)
-        ctx.needs = ctx.needs_input_grad
-        ctx.fp32_gemm = ops.FP32_GEMM
-        if features_only:
-            ctx.mark_non_differentiable(out)
-        return out
-
-    @staticmethod
-    def backward(ctx, d_item):
-        p, prep, saved, names, prefix, shape = ctx.stuff
-        ctx.stuff = None
-        skip = {deberta_engine.deberta_layer_names(prefix, l) + "attention.self." + k for l in range(shape.num_hidden_layers)
-                for k in ("in_proj.weight", "q_bias", "v_bias")}
-        grads = _zeros_like_params(names, [p[n] for n in names], skip=skip)
-        with ops.fp32_gemm_mode(ctx.fp32_gemm):
-            deberta_engine.deberta_backward(p, prep, saved, d_item.contiguous(), grads, prefix)
-            engine.WgradStream.join(d_item.device)
-        needs = ctx.needs[2:]
-        return (None, None) + tuple(grads.get(n) if nd else None for n, nd in zip(names, needs))
-
-
-class BeitEncoderFn(torch.autograd.Function):
-    """``Vit_Encoder.forward`` (``V/model/encoders.py:30-31``) over HF ``BeitForImageClassification`` arithmetic.  ``cfg = (names, shape,
-    dtype, prefix, drop, training)`` as ``SwinEncoderFn``'s.  A frozen bias table or layer scale gets no buffer: its gradient work is
-    skipped (``beit_engine.beit_backward``)."""
-
-    @staticmethod
-    def forward(ctx, pixels, cfg, *params):
-        names, shape, dtype, prefix, drop, training = cfg
-        p = dict(zip(names, params))
-        need = any(ctx.needs_input_grad)
-        prep = beit_engine.beit_prepare(p, shape, dtype, prefix)
-        item, saved = beit_engine.beit_forward(p, prep, shape, pixels, dtype, need, prefix, drop, training)
-        ctx.stuff = (p, prep, saved, names, prefix, shape)
-        ctx.needs = ctx.needs_input_grad
-        ctx.fp32_gemm = ops.FP32_GEMM
-        return item
-
-    @staticmethod
-    def backward(ctx, d_item):
-        p, prep, saved, names, prefix, shape = ctx.stuff
-        ctx.stuff = None
-        needs = ctx.needs[2:]
-        skip = {beit_engine.beit_layer_names(prefix, l) + f"attention.{n}" for l in range(shape.num_hidden_layers)
-                for n in ("q_proj.weight", "q_proj.bias", "k_proj.weight", "v_proj.weight", "v_proj.bias")}
-        skip |= {n for n, nd in zip(names, needs) if not nd and n.endswith((beit_engine.TABLE, ".lambda_1", ".lambda_2"))}
-        grads = _zeros_like_params(names, [p[n] for n in names], skip=skip)
-        with ops.fp32_gemm_mode(ctx.fp32_gemm):
-            beit_engine.beit_backward(p, prep, saved, d_item.contiguous(), grads, prefix)
-            engine.WgradStream.join(d_item.device)
-        return (None, None) + tuple(grads.get(n) if nd else None for n, nd in zip(names, needs))
-
-
-class ResNetEncoderFn(torch.autograd.Function):
-    """``Resnet_Encoder.forward`` (``V/model/encoders.py:40-41``) over torchvision ``ResNet`` arithmetic.  ``cfg = (names, shape, dtype,
-    prefix, bufs, training, sync)``: ``bufs`` are the BatchNorm buffers by name (training mode updates the running statistics in place);
-    ``sync`` is a ``resnet_engine.BnSync`` (training mode takes the statistics over every rank's rows) or None.  A frozen
-    parameter gets no buffer: a frozen convolution skips its weight gradient, a frozen BatchNorm still normalises with batch statistics."""
-
-    @staticmethod
-    def forward(ctx, pixels, cfg, *params):
-        names, shape, dtype, prefix, bufs, training, sync = cfg
-        p = dict(zip(names, params))
-        need = any(ctx.needs_input_grad)
-        prep = resnet_engine.resnet_prepare(p, shape, dtype, prefix, need_grad=need)
-        item, saved = resnet_engine.resnet_forward(p, bufs, prep, shape, pixels, dtype, need, prefix, training, sync=sync)
-        ctx.stuff = (p, prep, saved, names, prefix)
-        ctx.needs = ctx.needs_input_grad
-        ctx.fp32_gemm = ops.FP32_GEMM
-        return item
-
-    @staticmethod
-    def backward(ctx, d_item):
-        p, prep, saved, names, prefix = ctx.stuff
-        ctx.stuff = None
-        needs = ctx.needs[2:]
-        grads = _zeros_like_params(names, [p[n] for n in names], skip={n for n, nd in zip(names, needs) if not nd})
-        with ops.fp32_gemm_mode(ctx.fp32_gemm):
-            resnet_engine.resnet_backward(p, prep, saved, d_item.contiguous(), grads, prefix)
-            engine.WgradStream.join(d_item.device)
-        return (None, None) + tuple(grads.get(n) if nd else None for n, nd in zip(names, needs))
+            tower.backward(p, prep, saved, d_out.contiguous(), grads, call)
+            engine.WgradStream.join(d_out.device)      # autograd consumers (DDP hooks, the optimizer) read the gradients on this stream
+        missing = [n for n, nd in zip(names, needs) if nd and n not in grads]
+        if missing:
+            raise RuntimeError(f"the tower's backward left no gradient for the trainable parameter {missing[0]!r}")
+        return (None, None, None) + tuple(grads[n] if nd else None for n, nd in zip(names, needs))
 
 
 class IdEmbeddingFn(torch.autograd.Function):

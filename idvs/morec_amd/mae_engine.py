@@ -17,8 +17,8 @@ from dataclasses import dataclass
 
 import torch
 
-from . import ops
-from ._lib import ACT_GELU, DACT_MUL
+from . import engine, ops
+from ._lib import ACT_GELU
 from .engine import linear_wgrad_, prepare_linear
 
 ENC = "cv_encoder."
@@ -96,11 +96,8 @@ def mae_prepare(p: dict, shape: MaeShape, dtype, prefix: str = ENC, features_onl
     prep = dict(patch=prepare_linear(pw.reshape(pw.shape[0], -1), dtype), layers=[])
     for l in range(shape.num_hidden_layers):
         L = mae_layer_names(prefix, l)
-        A = L + "attention."
-        wqkv = torch.cat([p[A + f"{n}.weight"] for n in ("q_proj", "k_proj", "v_proj")], 0)
-        bqkv = torch.cat([p[A + f"{n}.bias"] for n in ("q_proj", "k_proj", "v_proj")], 0)
-        prep["layers"].append(dict(qkv=prepare_linear(wqkv, dtype), bqkv=bqkv, o=prepare_linear(p[A + "o_proj.weight"], dtype),
-                                   f1=prepare_linear(p[L + "mlp.fc1.weight"], dtype), f2=prepare_linear(p[L + "mlp.fc2.weight"], dtype)))
+        prep["layers"].append(engine.prepare_block(p, L + "attention.", L + "attention.o_proj.weight", L + "mlp.fc1.weight",
+                                                   L + "mlp.fc2.weight", dtype))
     if not features_only:
         prep["cls"] = prepare_linear(p[prefix + "cv_proj.weight"], dtype)
     return prep
@@ -121,9 +118,7 @@ def mae_forward(p: dict, prep, shape: MaeShape, pixels: torch.Tensor, dtype, nee
     n_img = pixels.shape[0]
     eps = shape.layer_norm_eps
     C, heads = shape.hidden_size, shape.num_attention_heads
-    R = pixels.shape[1] if pixels.dtype == torch.uint8 else pixels.shape[2]
-    if R != shape.image_size:
-        raise ValueError(f"input image size {R} does not match the model's {shape.image_size} (interpolate_pos_encoding is not implemented)")
+    engine.check_image_size(pixels, shape.image_size)
     keep = mae_keep(shape, n_img, pixels.device, noise, seed, mask_ratio)
     Lk = keep.shape[1]
     T = Lk + 1
@@ -161,9 +156,7 @@ def mae_forward(p: dict, prep, shape: MaeShape, pixels: torch.Tensor, dtype, nee
                                                       z_inplace=True)
     if features_only:
         return cls_n, None
-    D = prep["cls"].w.shape[0]
-    pre_c = torch.empty((n_img, D), device=x.device, dtype=dtype) if need_grad else None
-    item = ops.gemm_nt(cls_n, prep["cls"].w, bias=p[prefix + "cv_proj.bias"], act=ACT_GELU, aux_out=pre_c)
+    item, pre_c = engine.head_forward(cls_n, prep["cls"], p[prefix + "cv_proj.bias"], need_grad)
     saved = (shape, n_img, T, desc, key_keep, keep, patches, saved_layers, z_last, mean_f, rstd_f, cls_n, pre_c) if need_grad else None
     return item, saved
 
@@ -175,10 +168,7 @@ def mae_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefix
     shape, n_img, T, desc, key_keep, keep, patches, saved_layers, z_last, mean_f, rstd_f, cls_n, pre_c = saved
     C = shape.hidden_size
     n_layers = shape.num_hidden_layers
-    dv = ops.act_bwd(d_item.contiguous(), pre_c, ACT_GELU)
-    ops.colsum_(dv, grads[prefix + "cv_proj.bias"])
-    linear_wgrad_(dv, cls_n, grads[prefix + "cv_proj.weight"])
-    dcls_n = ops.gemm_nt(dv, prep["cls"].wt, K=dv.shape[1], N=C)
+    dcls_n = engine.head_backward(d_item, pre_c, cls_n, prep["cls"], grads[prefix + "cv_proj.weight"], grads[prefix + "cv_proj.bias"], C)
     # gradient at the last block's output sum, [CLS] rows (every other row: zero); its column sums are that block's fc2.bias gradient
     dz0, _ = ops.layernorm_bwd(dcls_n, None, z_last, mean_f, rstd_f, p[net + "layernorm.weight"], grads[net + "layernorm.weight"],
                                grads[net + "layernorm.bias"], dbias=grads[mae_layer_names(prefix, n_layers - 1) + "mlp.fc2.bias"])
@@ -190,31 +180,33 @@ def mae_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefix
         w = prep["layers"][l]
         x, xn, mean1, rstd1, qkv, ctx, h, hn, mean2, rstd2, pre, g = saved_layers[l]
         # MLP branch: out = h + fc2(gelu(fc1(LN2(h)))) + b2
-        linear_wgrad_(dout, g, grads[L + "mlp.fc2.weight"])
-        du = ops.gemm_nt(dout, w["f2"].wt, dact=DACT_MUL, dact_in=pre, K=dout.shape[1], N=pre.shape[1], colsum_out=grads[L + "mlp.fc1.bias"])
-        linear_wgrad_(du, hn, grads[L + "mlp.fc1.weight"])
-        dhn = ops.gemm_nt(du, w["f1"].wt, K=du.shape[1], N=C)
+        dhn = engine.mlp_backward(dout, w, g, pre, hn, grads[L + "mlp.fc2.weight"], grads[L + "mlp.fc1.bias"], grads[L + "mlp.fc1.weight"], C)
         # h = x + o_proj(ctx) + bo: dh = LN2'(dhn) + dout
         dh, da = ops.layernorm_bwd(dhn, None, h, mean2, rstd2, p[L + "layernorm_after.weight"], grads[L + "layernorm_after.weight"],
                                    grads[L + "layernorm_after.bias"], dbias=grads[A + "o_proj.bias"], dres=dout)
         linear_wgrad_(da, ctx, grads[A + "o_proj.weight"])
         dctx = ops.gemm_nt(da, w["o"].wt, K=da.shape[1], N=C)
-        gw = torch.zeros((3 * C, C), device=dctx.device, dtype=torch.float32)
-        gb = torch.zeros(3 * C, device=dctx.device, dtype=torch.float32)
+        gw, gb = engine.fused_qkv_grads(C, dctx.device)
         dqkv = ops.attn_bwd(desc, qkv, key_keep, dctx, dbias=gb)      # + d(q|k|v bias) = column sums of dqkv
         linear_wgrad_(dqkv, xn, gw)
-        for i, n in enumerate(("q_proj", "k_proj", "v_proj")):
-            grads[A + f"{n}.weight"], grads[A + f"{n}.bias"] = gw[i * C:(i + 1) * C], gb[i * C:(i + 1) * C]
-        # The key bias adds q_i . b to every score of row i: a per-row constant that the softmax removes, so its gradient is exactly
-        # zero (BEiT drops the parameter for this reason).  The column sums of dK only hold the rounding noise of the attention
-        # backward (16-bit: ~1e-3 in norm, which Adam would normalise into steps of the learning rate); the exact value is written.
-        gb[C:2 * C].zero_()
+        engine.hand_out_qkv(grads, A, gw, gb, C, key_bias="zero")
         dxn = ops.gemm_nt(dqkv, w["qkv"].wt, K=dqkv.shape[1], N=C)
         # x is the previous block's output sum (or the assembled embeddings): its bias gradient is the previous block's fc2.bias
         prev_b2 = grads[mae_layer_names(prefix, l - 1) + "mlp.fc2.bias"] if l > 0 else None
         dout, _ = ops.layernorm_bwd(dxn, None, x, mean1, rstd1, p[L + "layernorm_before.weight"], grads[L + "layernorm_before.weight"],
                                     grads[L + "layernorm_before.bias"], dbias=prev_b2, dres=dh)
-    de, _ = ops.mae_assemble_bwd(dout, n_img, T - 1, d_cls=grads[net + "embeddings.cls_token"].view(-1))
-    ops.colsum_(de, grads[net + "embeddings.patch_embeddings.projection.bias"])
-    gpw = grads[net + "embeddings.patch_embeddings.projection.weight"]
-    linear_wgrad_(de, patches, gpw.view(gpw.shape[0], -1))
+    engine.patch_embed_backward(dout, n_img, T - 1, patches, grads, net + "embeddings.")
+
+
+def _no_buffer(names, needs, c, plan):
+    skip = {n for l in range(c.shape.num_hidden_layers) for n in engine.qkv_names(mae_layer_names(c.prefix, l) + "attention.")}
+    return skip | {c.prefix + "image_net.embeddings.position_embeddings"}      # frozen in HF: no gradient
+
+
+TOWER = engine.Tower(
+    prepare=lambda p, c, need_grad: mae_prepare(p, c.shape, c.dtype, c.prefix, features_only=c.features_only),
+    plan=engine.no_plan,
+    forward=lambda p, prep, x, c, need_grad: mae_forward(p, prep, c.shape, x, c.dtype, need_grad, c.prefix, features_only=c.features_only,
+                                                         **c.kw),
+    backward=lambda p, prep, saved, d, grads, c: mae_backward(p, prep, saved, d, grads, c.prefix),
+    no_buffer=_no_buffer)

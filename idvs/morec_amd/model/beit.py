@@ -1,7 +1,7 @@
 """``HipBeitForImageClassification``: parameter container with HuggingFace ``BeitForImageClassification``'s module tree, ``state_dict``
 keys and parameter order (the reference loads it as the image network of ``Vit_Encoder``, ``V/model/encoders.py:24-31``, for
 ``CV_model_load`` names containing 'beit', ``V/model/model.py:26-27``, and replaces ``.classifier`` by ``Linear(hidden, embedding_dim)``,
-``V/run.py:47-54``).  Forward arithmetic is in ``libmorec_hip.so`` (``functional.BeitEncoderFn``); this class only owns the weights so
+``V/run.py:47-54``).  Forward arithmetic is in ``libmorec_hip.so`` (``functional.TowerFn`` over ``beit_engine.TOWER``); this class only owns the weights so
 that a HF checkpoint loads key for key (``from_hf``), including the reference's pinned ``transformers==4.20.1`` key names
 (``remap_legacy_beit_keys``).
 

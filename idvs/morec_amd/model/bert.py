@@ -1,7 +1,7 @@
 """``HipBertModel``: parameter container with HuggingFace ``BertModel``'s module tree and ``state_dict`` keys
 (the reference builds ``BertModel.from_pretrained(...)`` at ``T/run.py:51-53`` and reaches it as
 ``model.module.bert_encoder.text_encoders.title.bert_model``, ``T/run.py:165``).  Forward arithmetic is in
-``libmorec_hip.so`` (``functional.BertEncoderFn``); this class only owns the weights, so a HF checkpoint's
+``libmorec_hip.so`` (``functional.TowerFn`` over ``engine.TOWER``); this class only owns the weights, so a HF checkpoint's
 ``state_dict`` loads key for key (``from_hf``)."""
 import types
 

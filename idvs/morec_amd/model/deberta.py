@@ -1,6 +1,6 @@
 """``HipDebertaModel``: parameter container with HuggingFace ``DebertaModel``'s module tree, ``state_dict`` keys and parameter order (the
 reference builds ``DebertaModel.from_pretrained(...)`` in its DSSM package, ``bce_text/main-end2end(DSSM)/run.py:26-31``, and wraps it in
-``Text_Encoder``).  Forward arithmetic is in ``libmorec_hip.so`` (``functional.DebertaEncoderFn``); this class only owns the weights, so
+``Text_Encoder``).  Forward arithmetic is in ``libmorec_hip.so`` (``functional.TowerFn`` over ``deberta_engine.TOWER``); this class only owns the weights, so
 a HF checkpoint's ``state_dict`` loads key for key (``from_hf``; keys of a ``DebertaFor...`` checkpoint lose their leading ``deberta.``).
 The registration order is the installed transformers': per layer ``q_bias``, ``v_bias``, ``in_proj.weight``, ``pos_proj.weight``,
 ``pos_q_proj.weight``, ``pos_q_proj.bias``, then the output and FFN parameters; ``encoder.rel_embeddings.weight`` LAST

@@ -7,8 +7,9 @@ import torch
 import torch.nn as nn
 from torch.nn.init import constant_, xavier_normal_
 
+from .. import beit_engine, deberta_engine, engine, mae_engine, opt_engine, resnet_engine, swin_engine
 from .. import functional as F_
-from ..engine import NO_DROP, DropCfg, bert_position_rule
+from ..engine import NO_DROP, DropCfg, TowerCall, bert_position_rule
 from ..ops import FLT_MIN_MASK
 from .bert import HipBertModel
 from .swin import HipSwinForImageClassification
@@ -151,8 +152,9 @@ class User_Encoder(nn.Module):
         """[B, S, D] -> [B, S, D] in the compute dtype (internal path of ``Model.forward``)."""
         names, params = zip(*self.named_parameters())
         te = self.transformer_encoder
-        cfg = (names, te.n_heads, te.n_layers, self.compute_dtype, "transformer_encoder.", drop, self.res32)
-        return F_.SasrecFn.apply(input_embs, log_mask, cfg, *params)
+        call = TowerCall(names, None, self.compute_dtype, "transformer_encoder.", drop,
+                         kw=dict(heads=te.n_heads, n_layers=te.n_layers, res32=self.res32))
+        return F_.SasrecFn.apply(input_embs, log_mask, call, *params)
 
     def forward(self, input_embs, log_mask, local_rank=None):
         out = self.encode(input_embs, log_mask)
@@ -175,20 +177,24 @@ class Text_Encoder(nn.Module):
         self.res32 = resolve_res32() if res32 is None else bool(res32)
         self.mask_value = FLT_MIN_MASK   # transformers >= 4.3x eager; set to -10000.0 for 4.20.1 behaviour
 
-    def encode(self, text, drop: DropCfg = NO_DROP, features_only: bool = False):
+    def tower_call(self, drop: DropCfg = NO_DROP, features_only: bool = False, T=None):
+        """(the tower's ``engine.Tower``, the ``TowerCall`` of one pass, its parameters in the call's order); ``T``: the title length."""
         c = self.bert_model.config
         if self.is_deberta:
-            check_deberta_config(c, text.shape[1] // 2)
+            check_deberta_config(c, T)
             names, params = zip(*self.named_parameters())
-            cfg = (names, self.bert_model.shape, self.compute_dtype, "", drop, features_only)
-            return F_.DebertaEncoderFn.apply(text, cfg, *params)
-        if features_only:
+            return deberta_engine.TOWER, TowerCall(names, self.bert_model.shape, self.compute_dtype, "", drop,
+                                                   features_only=features_only), params
+        names, params = zip(*[(n, p) for n, p in self.named_parameters() if ".pooler." not in n])
+        kw = dict(heads=c.num_attention_heads, n_layers=c.num_hidden_layers, eps=c.layer_norm_eps, mask_value=self.mask_value,
+                  res32=self.res32, position=bert_position_rule(c))
+        return engine.TOWER, TowerCall(names, None, self.compute_dtype, "", drop, features_only=features_only, kw=kw), params
+
+    def encode(self, text, drop: DropCfg = NO_DROP, features_only: bool = False):
+        if features_only and not self.is_deberta:
             raise NotImplementedError("Text_Encoder.encode(features_only=True) is the DeBERTa tower's; BERT / RoBERTa: engine.bert_forward")
-        named = [(n, p) for n, p in self.named_parameters() if ".pooler." not in n]
-        names, params = zip(*named)
-        cfg = (names, c.num_attention_heads, c.num_hidden_layers, self.compute_dtype, "", c.layer_norm_eps, self.mask_value,
-               drop, self.res32, tuple(bert_position_rule(c).items()))
-        return F_.BertEncoderFn.apply(text, cfg, *params)
+        tower, call, params = self.tower_call(drop, features_only, text.shape[1] // 2)
+        return F_.TowerFn.apply(text, tower, call, *params)
 
     def forward(self, text):
         return self.encode(text).float()
@@ -210,11 +216,15 @@ class Text_Encoder_mean(nn.Module):
         self.compute_dtype = compute_dtype or resolve_dtype()
         self.unpad = None      # None: MOREC_UNPAD decides; False keeps the padded layout
 
-    def encode(self, text, drop: DropCfg = NO_DROP, features_only: bool = False):
+    def tower_call(self, drop: DropCfg = NO_DROP, features_only: bool = False):
         check_opt_config(self.bert_model.config)
         names, params = zip(*self.named_parameters())
-        cfg = (names, self.bert_model.shape, self.compute_dtype, "", drop, self.unpad, features_only)
-        return F_.OptEncoderFn.apply(text, cfg, *params)
+        return opt_engine.TOWER, TowerCall(names, self.bert_model.shape, self.compute_dtype, "", drop, features_only=features_only,
+                                           kw=dict(unpad=self.unpad)), params
+
+    def encode(self, text, drop: DropCfg = NO_DROP, features_only: bool = False):
+        tower, call, params = self.tower_call(drop, features_only)
+        return F_.TowerFn.apply(text, tower, call, *params)
 
     def forward(self, text):
         return self.encode(text).float()
@@ -270,16 +280,18 @@ class Vit_Encoder(nn.Module):
         self.is_beit = isinstance(self.image_net, HipBeitForImageClassification)
         self.compute_dtype = compute_dtype or resolve_dtype()
 
-    def encode(self, item_content, drop: DropCfg = NO_DROP, interpolate_pos_encoding: bool = False):
-        named = [(n, p) for n, p in self.named_parameters()]
-        names, params = zip(*named)
-        cfg = (names, self.image_net.shape, self.compute_dtype, "image_net.", drop, self.training)
+    def tower_call(self, drop: DropCfg = NO_DROP, features_only: bool = False):
         if self.is_beit:
-            if interpolate_pos_encoding:
-                raise NotImplementedError("BEiT tower: interpolate_pos_encoding (a bias table resampled to another grid) is not built")
             check_beit_config(self.image_net.config)
-            return F_.BeitEncoderFn.apply(item_content, cfg, *params)
-        return F_.SwinEncoderFn.apply(item_content, cfg, *params)
+        names, params = zip(*self.named_parameters())
+        return (beit_engine.TOWER if self.is_beit else swin_engine.TOWER,
+                TowerCall(names, self.image_net.shape, self.compute_dtype, "image_net.", drop, self.training, features_only), params)
+
+    def encode(self, item_content, drop: DropCfg = NO_DROP, interpolate_pos_encoding: bool = False):
+        if self.is_beit and interpolate_pos_encoding:
+            raise NotImplementedError("BEiT tower: interpolate_pos_encoding (a bias table resampled to another grid) is not built")
+        tower, call, params = self.tower_call(drop)
+        return F_.TowerFn.apply(item_content, tower, call, *params)
 
     def forward(self, item_content, interpolate_pos_encoding: bool = False):
         return self.encode(item_content, interpolate_pos_encoding=interpolate_pos_encoding).float()
@@ -323,11 +335,16 @@ class Resnet_Encoder(nn.Module):
         world = dist.get_world_size(group)
         return BnSync(group, world) if world > 1 else None
 
-    def encode(self, item_content, drop: DropCfg = NO_DROP):
+    def tower_call(self, drop: DropCfg = NO_DROP, features_only: bool = False):
+        """``kw``: ``bufs``, the BatchNorm buffers by name (training mode updates the running statistics in place), and ``sync``, a
+        ``resnet_engine.BnSync`` (training mode takes the statistics over every rank's rows) or None."""
         names, params = zip(*self.named_parameters())
-        cfg = (names, self.image_net.shape, self.compute_dtype, "image_net.", dict(self.named_buffers()), self.training,
-               self.sync_context())
-        return F_.ResNetEncoderFn.apply(item_content, cfg, *params)
+        return resnet_engine.TOWER, TowerCall(names, self.image_net.shape, self.compute_dtype, "image_net.", drop, self.training, features_only,
+                                              kw=dict(bufs=dict(self.named_buffers()), sync=self.sync_context())), params
+
+    def encode(self, item_content, drop: DropCfg = NO_DROP):
+        tower, call, params = self.tower_call(drop)
+        return F_.TowerFn.apply(item_content, tower, call, *params)
 
     def forward(self, item_content):
         return self.encode(item_content).float()
@@ -375,11 +392,17 @@ class MAE_Encoder(nn.Module):
         seed, ratio = self.masking(drop)
         return mae_keep(self.image_net.shape, n_img, device, self.noise if noise is None else noise, seed, ratio)
 
-    def encode(self, item_content, drop: DropCfg = NO_DROP, noise=None):
+    def tower_call(self, drop: DropCfg = NO_DROP, features_only: bool = False, noise=None):
+        """``kw``: ``noise`` fp32 [n_img, N] or None (the kept patches are then drawn from ``seed``), ``seed`` and ``mask_ratio`` of the
+        current mode (``masking``)."""
         names, params = zip(*self.named_parameters())
         seed, ratio = self.masking(drop)
-        cfg = (names, self.image_net.shape, self.compute_dtype, "", self.noise if noise is None else noise, seed, ratio)
-        return F_.MaeEncoderFn.apply(item_content, cfg, *params)
+        return mae_engine.TOWER, TowerCall(names, self.image_net.shape, self.compute_dtype, "", drop, self.training, features_only,
+                                           kw=dict(noise=noise, seed=seed, mask_ratio=ratio)), params
+
+    def encode(self, item_content, drop: DropCfg = NO_DROP, noise=None):
+        tower, call, params = self.tower_call(drop, noise=self.noise if noise is None else noise)
+        return F_.TowerFn.apply(item_content, tower, call, *params)
 
     def forward(self, item_content, noise=None):
         return self.encode(item_content, noise=noise).float()

@@ -1,6 +1,6 @@
 """``HipViTMAEModel``: parameter container with HuggingFace ``ViTMAEModel``'s module tree, ``state_dict`` keys and parameter order
 (the reference loads it as the image network of ``MAE_Encoder``, ``V/model/encoders.py:7-21``, for ``CV_model_load`` names containing
-'mae' or 'checkpoint', ``V/model/model.py:28-29``).  Forward arithmetic is in ``libmorec_hip.so`` (``functional.MaeEncoderFn``); this
+'mae' or 'checkpoint', ``V/model/model.py:28-29``).  Forward arithmetic is in ``libmorec_hip.so`` (``functional.TowerFn`` over ``mae_engine.TOWER``); this
 class only owns the weights so that a HF checkpoint loads key for key (``from_hf``), including the reference's pinned
 ``transformers==4.20.1`` key names (``remap_legacy_mae_keys``).  The MAE decoder is not part of ``ViTMAEModel`` and is not built."""
 import math

@@ -1,6 +1,6 @@
 """``HipOPTModel``: parameter container with HuggingFace ``OPTModel``'s module tree, ``state_dict`` keys and parameter order (the
 reference builds ``OPTModel.from_pretrained(...)`` at ``T/run.py:41-47`` and wraps it in ``Text_Encoder_mean``, ``T/model/encoders.py:
-31-50``).  Forward arithmetic is in ``libmorec_hip.so`` (``functional.OptEncoderFn``); this class only owns the weights, so a HF
+31-50``).  Forward arithmetic is in ``libmorec_hip.so`` (``functional.TowerFn`` over ``opt_engine.TOWER``); this class only owns the weights, so a HF
 checkpoint's ``state_dict`` loads key for key (``from_hf``; keys of an ``OPTForCausalLM`` checkpoint lose their leading ``model.``).
 The registration order is the installed transformers': the decoder-level ``final_layer_norm`` before the layers, and k, v, q, out inside
 ``self_attn`` (``tests/golden/g30_opt_keys.json``) -- ``--freeze_paras_before`` counts by it."""

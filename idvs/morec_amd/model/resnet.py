@@ -2,7 +2,7 @@
 default vision encoder: ``--CV_model_load resnet-50``, ``Resnet_Encoder`` in ``V/model/encoders.py:34-41``, selected by ``'resnet' in
 CV_model_load``, ``V/model/model.py:24-25``; ``V/run.py:38-46`` builds ``torchvision.models.resnet*``, loads ``<pretrained>/<name>`` with
 ``load_state_dict`` and replaces ``.fc`` by a Xavier-initialised ``Linear(num_fc_ftr, embedding_dim)``).  Forward arithmetic is in
-``libmorec_hip.so`` (``functional.ResNetEncoderFn`` over ``resnet_engine``); this class only owns the weights and the BatchNorm buffers,
+``libmorec_hip.so`` (``functional.TowerFn`` over ``resnet_engine.TOWER``); this class only owns the weights and the BatchNorm buffers,
 so that a torchvision checkpoint loads key for key and ``--freeze_paras_before`` counts parameters as it does in the reference.
 
 torchvision's v1.5 layout: the stride of a Bottleneck sits on ``conv2``; ``zero_init_residual`` is off."""

@@ -1,7 +1,7 @@
 """``HipSwinForImageClassification``: parameter container with HuggingFace ``SwinForImageClassification``'s module tree
 and ``state_dict`` keys (the reference builds it at ``V/run.py:47-54`` -- ``from_pretrained`` then a fresh
 ``classifier = Linear(num_features, embedding_dim)`` -- and reaches it as ``model.module.cv_encoder.image_net``,
-``V/run.py:138``).  Forward arithmetic is in ``libmorec_hip.so`` (``functional.SwinEncoderFn``); this class only owns
+``V/run.py:138``).  Forward arithmetic is in ``libmorec_hip.so`` (``functional.TowerFn`` over ``swin_engine.TOWER``); this class only owns
 the weights so that a HF checkpoint loads key for key (``from_hf``), including the reference's pinned
 ``transformers==4.20.1`` key names (``remap_legacy_swin_keys``)."""
 import re

@@ -25,7 +25,7 @@ from dataclasses import dataclass
 import torch
 
 from . import engine, ops
-from ._lib import ACT_GELU, ACT_RELU, DACT_MUL
+from ._lib import ACT_RELU
 from .engine import NO_DROP, DropCfg, linear_wgrad_, prepare_linear
 
 TE = engine.TE
@@ -130,12 +130,8 @@ def opt_grad_from(trainable_names, n_layers: int, prefix: str = TE) -> int:
 def opt_prepare(p: dict, shape: OptShape, dtype, prefix: str = TE, features_only: bool = False):
     prep = dict(layers=[])
     for l in range(shape.num_hidden_layers):
-        A = opt_layer_names(prefix, l) + "self_attn."
         L = opt_layer_names(prefix, l)
-        wqkv = torch.cat([p[A + f"{n}.weight"] for n in ("q_proj", "k_proj", "v_proj")], 0)
-        bqkv = torch.cat([p[A + f"{n}.bias"] for n in ("q_proj", "k_proj", "v_proj")], 0)
-        prep["layers"].append(dict(qkv=prepare_linear(wqkv, dtype), bqkv=bqkv, o=prepare_linear(p[A + "out_proj.weight"], dtype),
-                                   f1=prepare_linear(p[L + "fc1.weight"], dtype), f2=prepare_linear(p[L + "fc2.weight"], dtype)))
+        prep["layers"].append(engine.prepare_block(p, L + "self_attn.", L + "self_attn.out_proj.weight", L + "fc1.weight", L + "fc2.weight", dtype))
     if not features_only:
         prep["fc"] = prepare_linear(p[prefix + "fc.weight"], dtype)
     return prep
@@ -211,9 +207,7 @@ def opt_forward(p: dict, prep, shape: OptShape, text: torch.Tensor, dtype, need_
     mean = ops.masked_mean_fwd(y, keep, Nc, T, cu)
     if features_only:
         return mean, None
-    D = prep["fc"].w.shape[0]
-    pre_c = torch.empty((Nc, D), device=x.device, dtype=dtype) if need_grad else None
-    item = ops.gemm_nt(mean, prep["fc"].w, bias=p[prefix + "fc.bias"], act=ACT_GELU, aux_out=pre_c)
+    item, pre_c = engine.head_forward(mean, prep["fc"], p[prefix + "fc.bias"], need_grad)
     saved = ((shape, Nc, T, rows, ids32, perm, cnt, keep, cu, tok_idx, ph, saved_layers, z_last, mean_f, rstd_f, mean, pre_c, grad_from)
              if need_grad else None)
     return item, saved
@@ -226,10 +220,7 @@ def opt_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefix
     shape, Nc, T, rows, ids32, perm, cnt, keep, cu, tok_idx, ph, saved_layers, z_last, mean_f, rstd_f, mean, pre_c, grad_from = saved
     H = shape.hidden_size
     n_layers = shape.num_hidden_layers
-    dv = ops.act_bwd(d_item.contiguous(), pre_c, ACT_GELU)
-    ops.colsum_(dv, grads[prefix + "fc.bias"])
-    linear_wgrad_(dv, mean, grads[prefix + "fc.weight"])
-    dmean = ops.gemm_nt(dv, prep["fc"].wt, K=dv.shape[1], N=H)
+    dmean = engine.head_backward(d_item, pre_c, mean, prep["fc"], grads[prefix + "fc.weight"], grads[prefix + "fc.bias"], H)
     dy = ops.masked_mean_bwd(dmean, keep, Nc, T, rows, cu)      # zeros on the masked rows
     # gradient at the last block's output sum (dres) and behind that block's FFN dropout (dsub); its column sums are that block's fc2.bias
     if n_layers == 0 or grad_from >= n_layers:      # no block below, or none that trains: no FFN dropout / fc2.bias to go through
@@ -248,24 +239,16 @@ def opt_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefix
         w = prep["layers"][l]
         desc, x, xn, mean1, rstd1, qkv, ctx, h, hn, mean2, rstd2, pre, g, s1, s2 = saved_layers[l]
         # FFN branch: out = h + drop(fc2(relu(fc1(LN2(h)))) + b2)
-        linear_wgrad_(dsub, g, grads[L + "fc2.weight"])
-        du = ops.gemm_nt(dsub, w["f2"].wt, dact=DACT_MUL, dact_in=pre, K=dsub.shape[1], N=pre.shape[1], colsum_out=grads[L + "fc1.bias"])
-        linear_wgrad_(du, hn, grads[L + "fc1.weight"])
-        dhn = ops.gemm_nt(du, w["f1"].wt, K=du.shape[1], N=H)
+        dhn = engine.mlp_backward(dsub, w, g, pre, hn, grads[L + "fc2.weight"], grads[L + "fc1.bias"], grads[L + "fc1.weight"], H)
         # h = x + drop(out_proj(ctx) + bo): dh = LN2'(dhn) + dres, da = drop'(dh)
         dh, da = ops.layernorm_bwd(dhn, None, h, mean2, rstd2, p[L + "final_layer_norm.weight"], grads[L + "final_layer_norm.weight"],
                                    grads[L + "final_layer_norm.bias"], p_in=ph, seed_in=s1, dbias=grads[A + "out_proj.bias"], dres=dres)
         linear_wgrad_(da, ctx, grads[A + "out_proj.weight"])
         dctx = ops.gemm_nt(da, w["o"].wt, K=da.shape[1], N=H)
-        gw = torch.zeros((3 * H, H), device=dctx.device, dtype=torch.float32)
-        gb = torch.zeros(3 * H, device=dctx.device, dtype=torch.float32)
+        gw, gb = engine.fused_qkv_grads(H, dctx.device)
         dqkv = ops.attn_bwd(desc, qkv, keep, dctx, dbias=gb)      # + d(q|k|v bias) = column sums of dqkv
         linear_wgrad_(dqkv, xn, gw)
-        for i, n in enumerate(("q_proj", "k_proj", "v_proj")):
-            grads[A + f"{n}.weight"], grads[A + f"{n}.bias"] = gw[i * H:(i + 1) * H], gb[i * H:(i + 1) * H]
-        # The key bias adds q_i . b to every score of row i: a per-row constant that the softmax removes, under the causal and the key
-        # mask as without them, so its gradient is exactly zero; the column sums of dK only hold rounding noise.  The exact value is written.
-        gb[H:2 * H].zero_()
+        engine.hand_out_qkv(grads, A, gw, gb, H, key_bias="zero")
         dxn = ops.gemm_nt(dqkv, w["qkv"].wt, K=dqkv.shape[1], N=H)
         if 0 < l == grad_from:      # nothing trainable below: only this LayerNorm's own gradients are wanted
             ops.layernorm_bwd(dxn, None, x, mean1, rstd1, p[L + "self_attn_layer_norm.weight"], grads[L + "self_attn_layer_norm.weight"],
@@ -288,3 +271,17 @@ def opt_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefix
     # word rows (id 1 = padding_idx skipped whatever the mask says) and position rows 2 + k; no token-type table
     ops.roberta_embed_bwd_(ids32, dres, grads[dec + "embed_tokens.weight"], grads[dec + "embed_positions.weight"], None, PAD_ID, T, perm, cnt,
                            POS_OFFSET - 1, order)
+
+
+def _no_buffer(names, needs, c, plan):
+    return {n for l in range(c.shape.num_hidden_layers) for n in engine.qkv_names(opt_layer_names(c.prefix, l) + "self_attn.")}
+
+
+TOWER = engine.Tower(
+    prepare=lambda p, c, need_grad: opt_prepare(p, c.shape, c.dtype, c.prefix, features_only=c.features_only),
+    # the backward stops at the lowest trainable point of the tower (T/run.py:73-75 freezes a prefix by parameter index)
+    plan=lambda trainable, c: dict(grad_from=opt_grad_from(trainable, c.shape.num_hidden_layers, c.prefix)),
+    forward=lambda p, prep, x, c, need_grad, **plan: opt_forward(p, prep, c.shape, x, c.dtype, need_grad, c.prefix, c.drop,
+                                                                 features_only=c.features_only, **c.kw, **plan),
+    backward=lambda p, prep, saved, d, grads, c: opt_backward(p, prep, saved, d, grads, c.prefix),
+    no_buffer=_no_buffer)

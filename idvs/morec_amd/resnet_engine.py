@@ -32,8 +32,7 @@ from typing import Any, NamedTuple
 
 import torch
 
-from . import ops
-from ._lib import ACT_GELU
+from . import engine, ops
 from .engine import _splitk, linear_wgrad_, prepare_linear
 
 IN = "image_net."
@@ -244,9 +243,7 @@ def resnet_forward(p: dict, bufs: dict, prep, shape, pixels: torch.Tensor, dtype
     pooled = ops.swin_pool_fwd(x, N, geom[1] * geom[2])
     if features_only:
         return pooled, None
-    D = prep["fc"].w.shape[0]
-    pre = torch.empty((N, D), device=x.device, dtype=dtype) if need_grad else None
-    item = ops.gemm_nt(pooled, prep["fc"].w, bias=p[prefix + "fc.bias"], act=ACT_GELU, aux_out=pre)
+    item, pre = engine.head_forward(pooled, prep["fc"], p[prefix + "fc.bias"], need_grad)
     saved = (shape, stem, tape, geom, pooled, pre, training, sync) if need_grad else None
     return item, saved
 
@@ -258,12 +255,7 @@ def resnet_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, pre
     rank)."""
     shape, stem, tape, geom, pooled, pre, training, sync = saved
     n_conv = 2 if shape.block == "basic" else 3
-    dv = ops.act_bwd(d_item.contiguous(), pre, ACT_GELU)
-    if prefix + "fc.bias" in grads:
-        ops.colsum_(dv, grads[prefix + "fc.bias"])
-    if prefix + "fc.weight" in grads:
-        linear_wgrad_(dv, pooled, grads[prefix + "fc.weight"])
-    dpooled = ops.gemm_nt(dv, prep["fc"].wt, K=dv.shape[1], N=pooled.shape[1])
+    dpooled = engine.head_backward(d_item, pre, pooled, prep["fc"], grads.get(prefix + "fc.weight"), grads.get(prefix + "fc.bias"), pooled.shape[1])
     dout = ops.swin_pool_bwd(dpooled, geom[0], geom[1] * geom[2])
     # the backward ends at the lowest block that holds a trainable parameter (``--freeze_paras_before``: the frozen prefix is not walked)
     lowest = min((i for i, rec in enumerate(tape) if any(n.startswith(rec["name"]) for n in grads)), default=len(tape))
@@ -293,3 +285,13 @@ def resnet_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, pre
     dy0 = ops.maxpool3x3s2_bwd(dout, idx, *g1)
     dc0, _ = _bn_bwd(p, grads, prefix + "bn1", dy0, y0, c0, s0, training, sync=sync)
     _conv_bwd(dc0, x0, None, g0, prep[prefix + "conv1.weight"], grads.get(prefix + "conv1.weight"), False, chunk_images)      # pixels take no gradient
+
+
+TOWER = engine.Tower(
+    prepare=lambda p, c, need_grad: resnet_prepare(p, c.shape, c.dtype, c.prefix, need_grad=need_grad, features_only=c.features_only),
+    plan=engine.no_plan,
+    forward=lambda p, prep, x, c, need_grad: resnet_forward(p, c.kw["bufs"], prep, c.shape, x, c.dtype, need_grad, c.prefix, c.training,
+                                                            features_only=c.features_only, sync=c.kw["sync"]),
+    backward=lambda p, prep, saved, d, grads, c: resnet_backward(p, prep, saved, d, grads, c.prefix),
+    # a frozen parameter gets no buffer: a frozen convolution skips its weight gradient (``resnet_backward``)
+    no_buffer=lambda names, needs, c, plan: {n for n, nd in zip(names, needs) if not nd})

@@ -15,8 +15,8 @@ from dataclasses import dataclass
 
 import torch
 
-from . import ops
-from ._lib import ACT_GELU, DACT_MUL
+from . import engine, ops
+from ._lib import ACT_GELU
 from .engine import NO_DROP, DropCfg, linear_wgrad_, prepare_linear
 
 IN = "cv_encoder.image_net."
@@ -107,15 +107,8 @@ def swin_prepare(p: dict, shape: SwinShape, dtype, prefix: str = IN, shadow: dic
         blocks = []
         for b in range(depth):
             L = swin_layer_names(prefix, s, b)
-            A = L + "attention."
-            wqkv, bqkv = p.get(A + "qkv_fused.weight"), p.get(A + "qkv_fused.bias")
-            if wqkv is None:
-                wqkv = torch.cat([p[A + f"{n}.weight"] for n in ("q_proj", "k_proj", "v_proj")], 0)
-                bqkv = torch.cat([p[A + f"{n}.bias"] for n in ("q_proj", "k_proj", "v_proj")], 0)
-            blocks.append(dict(qkv=prepare_linear(wqkv, dtype, sh.get(A + "qkv_fused.weight"), sh.get(A + "qkv_fused.weight" + "^T")), bqkv=bqkv,
-                               o=prepare_linear(p[A + "o_proj.weight"], dtype, sh.get(A + "o_proj.weight"), sh.get(A + "o_proj.weight" + "^T")),
-                               f1=prepare_linear(p[L + "mlp.fc1.weight"], dtype, sh.get(L + "mlp.fc1.weight"), sh.get(L + "mlp.fc1.weight" + "^T")),
-                               f2=prepare_linear(p[L + "mlp.fc2.weight"], dtype, sh.get(L + "mlp.fc2.weight"), sh.get(L + "mlp.fc2.weight" + "^T"))))
+            blocks.append(engine.prepare_block(p, L + "attention.", L + "attention.o_proj.weight", L + "mlp.fc1.weight", L + "mlp.fc2.weight",
+                                               dtype, sh))
         prep["stages"].append(blocks)
         if s < len(shape.depths) - 1:
             k = sw + f"encoder.layers.{s}.downsample.reduction.weight"
@@ -205,9 +198,7 @@ def swin_forward(p: dict, prep, shape: SwinShape, pixels: torch.Tensor, dtype, n
     pooled = ops.swin_pool_fwd(xf, n_img, H * W)
     if features_only:
         return pooled, None
-    D = prep["cls"].w.shape[0]
-    pre_c = torch.empty((n_img, D), device=x.device, dtype=dtype) if need_grad else None
-    item = ops.gemm_nt(pooled, prep["cls"].w, bias=p[prefix + "classifier.bias"], act=ACT_GELU, aux_out=pre_c)
+    item, pre_c = engine.head_forward(pooled, prep["cls"], p[prefix + "classifier.bias"], need_grad)
     saved = (shape, n_img, saved_embed, saved_stages, saved_merges, z_last, mean_f, rstd_f, pooled, pre_c) if need_grad else None
     return item, saved
 
@@ -220,11 +211,8 @@ def swin_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefi
     sw = prefix + "swin."
     shape, n_img, saved_embed, saved_stages, saved_merges, z_last, mean_f, rstd_f, pooled, pre_c = saved
     geom = shape.stage_geometry()
-    dv = ops.act_bwd(d_item.contiguous(), pre_c, ACT_GELU)
-    ops.colsum_(dv, grads[prefix + "classifier.bias"])
-    linear_wgrad_(dv, pooled, grads[prefix + "classifier.weight"])
     C, H, W, _, _ = geom[-1]
-    dpooled = ops.gemm_nt(dv, prep["cls"].wt, K=dv.shape[1], N=C)
+    dpooled = engine.head_backward(d_item, pre_c, pooled, prep["cls"], grads[prefix + "classifier.weight"], grads[prefix + "classifier.bias"], C)
     dxf = ops.swin_pool_bwd(dpooled, n_img, H * W)
     last_s, last_b = len(shape.depths) - 1, shape.depths[-1] - 1
     b2_name = swin_layer_names(prefix, last_s, last_b) + "mlp.fc2.bias"
@@ -248,14 +236,13 @@ def swin_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefi
             w = prep["stages"][s][b]
             desc, bias_t, x, xn, mean1, rstd1, qkv, ctx, h, hn, mean2, rstd2, pre, g, scale, tokens = saved_stages[s][b]
             # MLP branch: out = h + fc2(gelu(fc1(LN2(h)))) + b2
-            linear_wgrad_(dout, g, grads[L + "mlp.fc2.weight"])
             if pre is None:
+                linear_wgrad_(dout, g, grads[L + "mlp.fc2.weight"])
                 du = ops.mlp_dact_recompute(dout, w["f2"].wt, hn, w["f1"].w, p[L + "mlp.fc1.bias"], colsum_out=grads[L + "mlp.fc1.bias"])
+                linear_wgrad_(du, hn, grads[L + "mlp.fc1.weight"])
+                dhn = ops.gemm_nt(du, w["f1"].wt, K=du.shape[1], N=C)
             else:
-                du = ops.gemm_nt(dout, w["f2"].wt, dact=DACT_MUL, dact_in=pre, K=dout.shape[1], N=pre.shape[1],
-                                 colsum_out=grads[L + "mlp.fc1.bias"])
-            linear_wgrad_(du, hn, grads[L + "mlp.fc1.weight"])
-            dhn = ops.gemm_nt(du, w["f1"].wt, K=du.shape[1], N=C)
+                dhn = engine.mlp_backward(dout, w, g, pre, hn, grads[L + "mlp.fc2.weight"], grads[L + "mlp.fc1.bias"], grads[L + "mlp.fc1.weight"], C)
             # h = x + droppath * (o_proj(ctx) + bo): dh = LN2'(dhn) + dout; da = droppath * dh
             dh, da = ops.layernorm_bwd(dhn, None, h, mean2, rstd2, p[L + "layernorm_after.weight"], grads[L + "layernorm_after.weight"],
                                        grads[L + "layernorm_after.bias"], dbias=grads[A + "o_proj.bias"], dres=dout,
@@ -266,14 +253,12 @@ def swin_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefi
             gw, gb = grads.get(A + "qkv_fused.weight"), grads.get(A + "qkv_fused.bias")
             fused = gw is not None
             if not fused:
-                gw = torch.zeros((3 * C, C), device=dctx.device, dtype=torch.float32)
-                gb = torch.zeros(3 * C, device=dctx.device, dtype=torch.float32)
+                gw, gb = engine.fused_qkv_grads(C, dctx.device)
             dqkv = ops.swin_attn_bwd(desc, qkv, bias_t, ctx, dctx, dbias_t, dbqkv=gb)      # + d(q|k|v bias) = column sums of dqkv
             ops.swin_bias_reduce_(dbias_t, grads[A + "relative_position_bias.relative_position_bias_table"], desc.window)
             linear_wgrad_(dqkv, xn, gw)
             if not fused:
-                for i, n in enumerate(("q_proj", "k_proj", "v_proj")):
-                    grads[A + f"{n}.weight"], grads[A + f"{n}.bias"] = gw[i * C:(i + 1) * C], gb[i * C:(i + 1) * C]
+                engine.hand_out_qkv(grads, A, gw, gb, C)
             dxn = ops.gemm_nt(dqkv, w["qkv"].wt, K=dqkv.shape[1], N=C)
             # x is the previous block's output sum (or the stage input): its bias gradient is the previous block's fc2.bias
             prev_b2 = grads[swin_layer_names(prefix, s, b - 1) + "mlp.fc2.bias"] if b > 0 else None
@@ -287,3 +272,17 @@ def swin_backward(p: dict, prep, saved, d_item: torch.Tensor, grads: dict, prefi
                               grads[sw + "embeddings.norm.bias"], dbias=grads[sw + "embeddings.patch_embeddings.projection.bias"])
     gpw = grads[sw + "embeddings.patch_embeddings.projection.weight"]
     linear_wgrad_(de, patches, gpw.view(gpw.shape[0], -1))
+
+
+def _no_buffer(names, needs, c, plan):
+    return {n for s, depth in enumerate(c.shape.depths) for b in range(depth)
+            for n in engine.qkv_names(swin_layer_names(c.prefix, s, b) + "attention.")}
+
+
+TOWER = engine.Tower(
+    prepare=lambda p, c, need_grad: swin_prepare(p, c.shape, c.dtype, c.prefix),
+    plan=engine.no_plan,
+    forward=lambda p, prep, x, c, need_grad: swin_forward(p, prep, c.shape, x, c.dtype, need_grad, c.prefix, c.drop, c.training,
+                                                          features_only=c.features_only),
+    backward=lambda p, prep, saved, d, grads, c: swin_backward(p, prep, saved, d, grads, c.prefix),
+    no_buffer=_no_buffer)
