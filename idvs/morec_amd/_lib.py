@@ -222,6 +222,11 @@ _SIGS = {
     "morec_maxpool3x3s2_bwd": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "morec_pixels_to_nhwc": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P]),
     "morec_image_resize_u8": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    "morec_swin_patchify_u8_idx": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
+                                             _P]),
+    "morec_mae_patchify_keep_u8_idx": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                                 C.c_float, C.c_int, _P]),
+    "morec_pixels_to_nhwc_idx": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P]),
     "morec_comm_available": (C.c_int, []),
     "morec_comm_unique_id": (C.c_int, [_P]),
     "morec_comm_create": (C.c_int, [C.POINTER(_P), _P, C.c_int, C.c_int]),

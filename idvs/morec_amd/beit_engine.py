@@ -140,7 +140,9 @@ def beit_forward(p: dict, prep, shape: BeitShape, pixels: torch.Tensor, dtype, n
     C, heads, g = shape.hidden_size, shape.num_attention_heads, shape.grid
     engine.check_image_size(pixels, shape.image_size)
     T = shape.num_patches + 1
-    if pixels.dtype == torch.uint8:
+    if hasattr(pixels, "catalogue"):    # data_utils.images.ImageIds: the im2col reads the device catalogue's rows through the ids
+        patches = ops.swin_patchify_u8_idx(*engine.catalogue_and_ids(pixels), shape.patch_size, dtype)
+    elif pixels.dtype == torch.uint8:
         patches = ops.swin_patchify_u8(pixels.contiguous(), shape.patch_size, dtype)
     else:
         patches = ops.swin_patchify(pixels.contiguous(), shape.patch_size, dtype)

@@ -41,6 +41,8 @@ def collate_train_batch(u2seq, users, item_content, max_seq_len, use_modal):
         log_mask[r, L - len(seq):] = 1.0
     if use_modal and hasattr(item_content, "device_batch"):      # vision catalogue in the reference's LMDB (data_utils/images.py)
         return torch.from_numpy(ids), item_content.device_batch(ids, "cuda"), torch.from_numpy(log_mask)
+    if use_modal and hasattr(item_content, "batch"):             # images.DeviceImageCatalogue: the batch is its ids (an ImageIds)
+        return torch.from_numpy(ids), item_content.batch(ids), torch.from_numpy(log_mask)
     items = np.asarray(item_content)[ids] if use_modal else ids
     items = torch.from_numpy(np.ascontiguousarray(items))
     if items.dtype != torch.uint8:          # uint8 = decoded images of the vision variant (normalised on the device)
@@ -67,9 +69,12 @@ def collate_bce_batch(u2seq, users, item_content, max_seq_len, item_num, use_mod
             while neg in seen:
                 neg = int(rng.integers(1, item_num + 1))
             items[r, L - n + j, 1] = neg
-    out = torch.from_numpy(np.ascontiguousarray(np.asarray(item_content)[items] if use_modal else items))
-    if out.dtype != torch.uint8:          # uint8 = decoded images of the vision variant (normalised on the device)
-        out = out.long()
+    if use_modal and hasattr(item_content, "batch"):             # images.DeviceImageCatalogue: the batch is its ids (an ImageIds)
+        out = item_content.batch(items)
+    else:
+        out = torch.from_numpy(np.ascontiguousarray(np.asarray(item_content)[items] if use_modal else items))
+        if out.dtype != torch.uint8:          # uint8 = decoded images of the vision variant (normalised on the device)
+            out = out.long()
     if with_ids:
         return torch.from_numpy(items), out, torch.from_numpy(log_mask)
     return out, torch.from_numpy(log_mask)

@@ -187,6 +187,131 @@ class PatchRows:
         self.device, self.shape = patches.device, (int(n_img),)
 
 
+IMAGES_ON_DEVICE = "--images_on_device"
+UPLOAD_CHUNK_BYTES = 256 << 20      # the page-locked staging buffer of DeviceImageCatalogue (tests lower it)
+HEADROOM_BYTES = 1 << 30            # what has to stay free next to the catalogue
+
+
+class ImageIds:
+    """A batch of images as item ids into a uint8 catalogue on the device: what the towers accept wherever they accept a uint8 pixel
+    tensor.  Their first kernel reads image k's pixels from ``catalogue[ids[k]]`` (``ops.*_idx``), so the batch that crosses PCIe is the
+    ids.  ``shape`` / ``dtype`` / ``device`` / ``reshape`` / ``view`` behave like those of the uint8 ``[*ids.shape, R, R, 3]`` tensor that
+    ``catalogue[ids]`` would be: ``reshape`` takes that tensor's new shape and keeps the ids' leading dimensions."""
+
+    def __init__(self, catalogue, ids):
+        import torch
+        assert catalogue.dtype == torch.uint8 and catalogue.dim() == 4 and ids.dtype == torch.int32 and ids.device == catalogue.device
+        self.catalogue, self.ids = catalogue, ids.contiguous()
+        self.device, self.dtype, self.is_cuda = catalogue.device, torch.uint8, catalogue.is_cuda
+
+    @property
+    def shape(self):
+        import torch
+        return torch.Size((*self.ids.shape, *self.catalogue.shape[1:]))
+
+    def dim(self):
+        return self.ids.dim() + 3
+
+    def reshape(self, *shape):
+        if len(shape) == 1 and not isinstance(shape[0], int):
+            shape = tuple(shape[0])
+        if len(shape) < 3 or tuple(int(v) for v in shape[-3:]) != tuple(self.catalogue.shape[1:]):
+            raise ValueError(f"an ImageIds batch keeps its image dimensions {tuple(self.catalogue.shape[1:])}: reshape{tuple(shape)}")
+        return ImageIds(self.catalogue, self.ids.reshape(*shape[:-3]))
+
+    view = reshape
+
+    def contiguous(self):
+        return self
+
+    def to(self, device=None, *args, **kw):
+        import torch
+        if device is not None and not isinstance(device, torch.dtype):
+            d = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+            if d.type != self.device.type or (d.index is not None and d.index != self.device.index):
+                raise ValueError(f"an ImageIds batch lives with its catalogue on {self.device}; it does not move to {d}")
+        return self
+
+    def pixels(self):
+        """The uint8 tensor this batch stands for (a gather; tests and the paths that are not built for ids)."""
+        return self.catalogue.index_select(0, self.ids.reshape(-1).long()).view(*self.shape)
+
+
+class DeviceImageCatalogue:
+    """The item images of a vision run on ONE device: uint8 ``[n + 1, R, R, 3]`` (row 0 = the padding item), uploaded once; indexable by
+    item id like the other catalogues.  ``batch(ids)`` is a training batch (``ImageIds``), ``pixels(a, b)`` the device view of rows
+    ``[a, b)`` that the catalogue pass at evaluation encodes.
+
+    ``source``: a host array (``--images_npy`` memory map, the synthetic array), copied in chunks of at most ``UPLOAD_CHUNK_BYTES`` through
+    one page-locked staging buffer and never materialised as a whole; or an ``LmdbItemImages``, whose ``device_batch`` runs once over id
+    chunks.  A catalogue that does not fit next to ``HEADROOM_BYTES`` of free memory exits before anything is allocated."""
+
+    def __init__(self, source, device, chunk_ids: int = 512):
+        import torch
+        self.dev = torch.device(device)
+        lazy = hasattr(source, "device_batch")
+        n_rows = len(source)
+        img_shape = (source.R, source.R, 3) if lazy else tuple(source.shape[1:])
+        if len(img_shape) != 3 or (not lazy and source.dtype != np.uint8):
+            raise ValueError(f"{IMAGES_ON_DEVICE}: the catalogue must be uint8 [n, H, W, C] images")
+        self.nbytes = self.check_fits(n_rows, img_shape, self.dev)
+        self.data = torch.empty((n_rows, *img_shape), device=self.dev, dtype=torch.uint8)
+        self.n_chunks = 0                  # uploads it took
+        if lazy:
+            for s in range(0, n_rows, chunk_ids):
+                e = min(n_rows, s + chunk_ids)
+                self.n_chunks += 1
+                self.data[s:e].copy_(source.device_batch(np.arange(s, e), self.dev))
+        else:
+            self._upload(source)
+
+    @staticmethod
+    def check_fits(n_rows, img_shape, device, mem_get_info=None):
+        """-> the catalogue's bytes; exits when they do not fit next to the headroom.  Nothing is allocated here."""
+        import torch
+        need = int(n_rows)
+        for v in img_shape:
+            need *= int(v)
+        free, _ = (mem_get_info or torch.cuda.mem_get_info)(device)
+        if need + HEADROOM_BYTES > free:
+            raise SystemExit(f"{IMAGES_ON_DEVICE}: the image catalogue needs {need} bytes (+ {HEADROOM_BYTES} of headroom) and the device "
+                             f"has {free} bytes free; run without the flag to keep the catalogue on the host")
+        return need
+
+    def _upload(self, arr):
+        import torch
+        per = int(np.prod(arr.shape[1:]))
+        rows = max(1, min(len(arr), UPLOAD_CHUNK_BYTES // per))
+        stage = torch.empty((rows, *arr.shape[1:]), dtype=torch.uint8).pin_memory()
+        host = stage.numpy()
+        for s in range(0, len(arr), rows):
+            e = min(len(arr), s + rows)
+            host[:e - s] = arr[s:e]            # memory map -> page-locked rows; the one host copy
+            self.data[s:e].copy_(stage[:e - s], non_blocking=True)
+            self.n_chunks += 1
+            torch.cuda.current_stream(self.dev).synchronize()      # the staging buffer is rewritten by the next chunk
+
+    def __len__(self):
+        return self.data.shape[0]
+
+    @property
+    def shape(self):
+        return tuple(self.data.shape)
+
+    @property
+    def dtype(self):
+        return np.dtype(np.uint8)
+
+    def batch(self, ids) -> ImageIds:
+        """ids of any shape (numpy, CPU or device tensor) -> ``ImageIds``; ids from the host outside the catalogue raise here."""
+        from .. import ops
+        shape = tuple(ids.shape) if hasattr(ids, "shape") else (len(ids),)
+        return ImageIds(self.data, ops.catalogue_ids(self.data, ids).view(*shape))
+
+    def pixels(self, a: int, b: int):
+        return self.data[a:b]
+
+
 class DeviceImageFeed:
     """Device half of the vision input pipeline, off the training step's stream.  The reference's DataLoader workers decode + resize
     the NEXT batch's images while the GPU trains on the current one, and the main loop only uploads tensors (``V/run.py:93-94,201-204``,

@@ -51,7 +51,8 @@ def _get_item_embeddings(model, item_content, test_batch_size, args, use_modal, 
                 else:
                     outs.append(m.cv_encoder(px))
         return torch.cat(outs, 0).float().detach()
-    content = torch.as_tensor(np.asarray(item_content))
+    on_device = vision and hasattr(item_content, "pixels")      # images.DeviceImageCatalogue: the chunks are views of the device copy
+    content = item_content.pixels(0, len(item_content)) if on_device else torch.as_tensor(np.asarray(item_content))
     if not vision:
         content = content.long()
     elif content.dtype != torch.uint8:      # uint8 HWC images are normalised on the device (morec_swin_patchify_u8)

@@ -281,6 +281,13 @@ def mlp_backward(d, w: dict, g, pre, hn, g_fc2_w, g_fc1_b, g_fc1_w, C: int):
     return ops.gemm_nt(du, w["f1"].wt, K=du.shape[1], N=C)
 
 
+def catalogue_and_ids(pixels):
+    """``data_utils.images.ImageIds`` in a tower's forward -> (uint8 catalogue [n_rows, H, W, 3], int32 ids [n_img]): one id per image."""
+    if pixels.ids.dim() != 1:
+        raise ValueError(f"an ImageIds batch enters a tower flat ([n_img] ids), got ids of shape {tuple(pixels.ids.shape)}")
+    return pixels.catalogue, pixels.ids
+
+
 def check_image_size(pixels: torch.Tensor, image_size: int):
     R = pixels.shape[1] if pixels.dtype == torch.uint8 else pixels.shape[2]
     if R != image_size:

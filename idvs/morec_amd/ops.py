@@ -1096,6 +1096,74 @@ def swin_patchify_u8(pixels_hwc, patch, dtype, mean=0.5, std=0.5, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------
+# Image catalogue on the device, a batch as its item ids (csrc/image_ids.hip)
+# ---------------------------------------------------------------------------------------------------------
+def check_catalogue_ids(ids, n_rows):
+    """Host-side ids (numpy array or CPU tensor) outside ``[0, n_rows)`` raise here, before anything is uploaded: the kernels only clamp."""
+    if isinstance(ids, torch.Tensor):
+        if ids.is_cuda or ids.numel() == 0:
+            return
+        lo, hi = int(ids.min()), int(ids.max())
+    else:
+        import numpy as np
+        a = np.asarray(ids)
+        if a.size == 0:
+            return
+        lo, hi = int(a.min()), int(a.max())
+    if lo < 0 or hi >= n_rows:
+        raise _lib.MorecError(f"image ids outside the catalogue: [{lo}, {hi}] against {n_rows} rows")
+
+
+def catalogue_ids(catalogue, ids):
+    """(uint8 catalogue [n_rows, ...] on the device, ids of any shape: numpy, CPU or device tensor) -> contiguous int32 ids on the
+    catalogue's device, flat.  Ids that come from the host are range-checked there."""
+    _dev(catalogue)
+    if catalogue.dtype != torch.uint8 or catalogue.dim() != 4 or not catalogue.is_contiguous():
+        raise _lib.MorecError("expected a contiguous uint8 [n_rows, H, W, C] catalogue")
+    if not isinstance(ids, torch.Tensor):
+        import numpy as np
+        ids = torch.from_numpy(np.ascontiguousarray(ids))
+    check_catalogue_ids(ids, catalogue.shape[0])
+    return ids.to(device=catalogue.device, dtype=torch.int32).reshape(-1).contiguous()
+
+
+def swin_patchify_u8_idx(catalogue, ids, patch, dtype, mean=0.5, std=0.5):
+    """``swin_patchify_u8(catalogue[ids], ...)`` without the gather: the kernel reads image k's pixels from catalogue row ``ids[k]``."""
+    ids = catalogue_ids(catalogue, ids)
+    n_rows, R, _, c = catalogue.shape
+    n, G = ids.numel(), R // patch
+    out = torch.empty((n * G * G, c * patch * patch), device=catalogue.device, dtype=dtype)
+    check(_lib.lib().morec_swin_patchify_u8_idx(_p(catalogue), _p(ids), n_rows, _p(out), n, c, R, patch, out.stride(0), mean, std, code(dtype),
+                                                _stream()), "morec_swin_patchify_u8_idx")
+    return out
+
+
+def mae_patchify_keep_u8_idx(catalogue, ids, keep, patch, dtype, mean=0.5, std=0.5):
+    """``mae_patchify_keep(catalogue[ids], keep, ...)`` without the gather: patches from ``keep[k]``, pixels from row ``ids[k]``."""
+    ids = catalogue_ids(catalogue, ids)
+    _dev(keep)
+    n_img, len_keep = keep.shape
+    if keep.dtype != torch.int32 or ids.numel() != n_img:
+        raise _lib.MorecError("mae keep must be int32 [n_img, len_keep]")
+    n_rows, R, _, c = catalogue.shape
+    out = torch.empty((n_img * len_keep, c * patch * patch), device=catalogue.device, dtype=dtype)
+    check(_lib.lib().morec_mae_patchify_keep_u8_idx(_p(catalogue), _p(ids), n_rows, _p(keep), _p(out), n_img, c, R, patch, len_keep,
+                                                    out.stride(0), mean, std, code(dtype), _stream()), "morec_mae_patchify_keep_u8_idx")
+    return out
+
+
+def pixels_to_nhwc_idx(catalogue, ids, dtype, mean=0.5, std=0.5):
+    """``pixels_to_nhwc(catalogue[ids], ...)`` without the gather -> [n H W, C] rows."""
+    ids = catalogue_ids(catalogue, ids)
+    n_rows, H, W, Cc = catalogue.shape
+    n = ids.numel()
+    out = torch.empty((n * H * W, Cc), device=catalogue.device, dtype=dtype)
+    check(_lib.lib().morec_pixels_to_nhwc_idx(_p(catalogue), _p(ids), n_rows, _p(out), n, Cc, H, W, float(mean), float(std), code(dtype),
+                                              _stream()), "morec_pixels_to_nhwc_idx")
+    return out
+
+
 def swin_merge(x, n_img, H, W, Cc, reverse=False):
     _dev(x)
     out = torch.empty((n_img * H * W, Cc) if reverse else (n_img * (H // 2) * (W // 2), 4 * Cc), device=x.device, dtype=x.dtype)

@@ -81,6 +81,10 @@ def build_parser():
     p.add_argument("--images_npy", type=str, default="None",
                    help="uint8 array [item_num + 1, R, R, 3] of decoded, resized item images (row 0 = padding item); stands in for the "
                         "LMDB reader of V/data_utils/dataset.py, whose lmdb / torchvision dependencies are not part of this package")
+    p.add_argument("--images_on_device", action="store_true",
+                   help="vision towers: upload the image catalogue (--images_npy, the synthetic array or --image_lmdb) to the device once "
+                        "(every rank its own copy); a training batch is then its item ids and the towers' first kernels read the pixels "
+                        "through them (data_utils.images.DeviceImageCatalogue); the catalogue pass at evaluation reads device views")
     # ============== cold-start / new-item evaluation (V/parameters.py:16-19; data_utils/special.py) ==============
     p.add_argument("--cold_seqs", type=str, default="None", help="--mode test: user lines whose target is a cold item (evaluated after "
                    "the test split); with --synthetic N, a path that does not exist yet is written with synthetic lines")
@@ -354,6 +358,24 @@ def check_id_two_stage_args(args):
         why = "--mo_dnn_layers and --dnn_layers must be >= 0"
     if why:
         raise SystemExit("--arch id_two_stage (id-two-stage: frozen item features fused with a trained id table): " + why)
+    return True
+
+
+def check_images_on_device_args(args):
+    """What ``--images_on_device`` does not run with: exits naming the flag (before anything touches a device).  True when it is on."""
+    if not getattr(args, "images_on_device", False):
+        return False
+    why = None
+    if "modal" not in args.item_tower:
+        why = f"--item_tower {args.item_tower}: the ID tower has no images"
+    elif getattr(args, "CV_model_load", "None") == "None":
+        why = "a text tower has no images (vision towers: --CV_model_load)"
+    elif getattr(args, "graph", False):
+        why = "--graph: graph capture of an ids-only vision step is not built"
+    elif getattr(args, "arch", "sasrec") != "sasrec":
+        why = f"--arch {args.arch}: the device catalogue is built for the end-to-end SASRec models (--loss inbatch | bce)"
+    if why:
+        raise SystemExit("--images_on_device (image catalogue on the device, batches as item ids): " + why)
     return True
 
 

@@ -49,7 +49,7 @@ from .model.opt import HipOPTModel, strip_model_prefix
 from .opt_engine import OptShape
 from .model.deberta import HipDebertaModel, strip_deberta_prefix
 from .deberta_engine import DebertaShape
-from .parameters import (check_beit_args, check_deberta_args, check_dssm_args, check_fusion_args, check_id_two_stage_args, check_mae_args, check_opt_args, check_resnet_args, is_resnet_run,
+from .parameters import (check_beit_args, check_deberta_args, check_dssm_args, check_fusion_args, check_id_two_stage_args, check_images_on_device_args, check_mae_args, check_opt_args, check_resnet_args, is_resnet_run,
                          check_two_stage_args, is_beit_run, is_deberta_run, is_mae_run, is_opt_run, parse_args)
 from . import engine
 from .train_step import TrainStep
@@ -622,6 +622,17 @@ def build_vision_tower(args):
     return HipSwinForImageClassification(SwinShape.named(args.CV_model_load), args.embedding_dim)   # V/run.py:47-54
 
 
+def device_image_catalogue(item_content, local_rank):
+    """``--images_on_device``: the vision catalogue of ``load_dataset`` (host array, memory map or ``LmdbItemImages``) uploaded once to this
+    rank's device (``data_utils.images.DeviceImageCatalogue``); every rank holds its own copy."""
+    from .data_utils.images import DeviceImageCatalogue
+    t0 = time.time()
+    cat = DeviceImageCatalogue(item_content, local_rank)
+    torch.cuda.synchronize(local_rank)
+    Log.info("--images_on_device: %d images, %.1f MB on the device, uploaded in %.2f s" % (len(cat), cat.nbytes / 1e6, time.time() - t0))
+    return cat
+
+
 def load_dataset(args, use_modal, vision):
     """The data of a SASRec-family run -- ``--synthetic N``, the text tables (tokenizer), the vision catalogue (LMDB) or the bare ids -- as
     ``(item_num, item_content, users_train, users_valid, users_test, hist_valid, hist_test, pop, catalogue)``."""
@@ -820,6 +831,8 @@ def train(args, use_modal, local_rank):
     if not vision and hasattr(args, "CV_model_load"):
         del args.CV_model_load                # `Model` picks the vision tower by the presence of this attribute (V/model/model.py:24-29)
     item_num, item_content, users_train, users_valid, users_test, hist_valid, hist_test, pop, catalogue = load_dataset(args, use_modal, vision)
+    if vision and getattr(args, "images_on_device", False):
+        item_content = device_image_catalogue(item_content, local_rank)
     bert = None
     if vision:
         bert = build_vision_tower(args)
@@ -872,7 +885,8 @@ def train(args, use_modal, local_rank):
         scaler = restore_optimizer_and_scaler(optimizer, args, ckpt)      # (the fused step keeps the GradScaler protocol in its device block: TrainStep.sp)
     ctl = autograd_step_control(args, optimizer, scaler, total_steps) if optimizer is not None else None
     stop, step = EarlyStop(6 if vision else 10, ckpt is None, args.epoch), 0
-    on_device = hasattr(item_content, "device_batch")       # LMDB catalogue: the collate itself issues device work (decode -> H2D -> resize)
+    # LMDB catalogue: the collate itself issues device work (decode -> H2D -> resize); --images_on_device: it hands out device objects (ImageIds)
+    on_device = hasattr(item_content, "device_batch") or hasattr(item_content, "batch")
     n_workers = 0 if (bce or on_device) else max(0, int(getattr(args, "collate_workers", 0)))
     depth = 0 if on_device else int(getattr(args, "prefetch", 2))
     # host side of a batch: a picklable object over numpy tables and flags (no closure over the model / stepper)
@@ -1267,6 +1281,7 @@ def train_two_stage(args, use_modal, local_rank, id_fusion=False):
 
 def main(argv=None):
     args = parse_args(argv)
+    check_images_on_device_args(args)
     check_mae_args(args)
     check_beit_args(args)
     check_resnet_args(args)

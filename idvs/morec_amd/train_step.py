@@ -414,6 +414,9 @@ class TrainStep:
         ``reduce_gradients`` must follow to reduce the rest and join them before the arenas are read."""
         m, p, g = self.model, self.p, self.g
         D, S = m.args.embedding_dim, m.max_seq_len
+        if self.dedup_items and hasattr(sample_items, "catalogue"):      # data_utils.images.ImageIds; refused before the step begins
+            raise SystemExit("--images_on_device: stepper.dedup_items gathers the batch's pixel rows, and an ids batch has none "
+                             "(deduplicating the ids of a batch is not built)")
         self._begin_step()
         # Nothing in the FORWARD pass reads the gradient arenas or the W^T copies (dX = dY W): zero / refresh them on the side stream,
         # under the forward GEMMs (HBM-bound fills next to MFMA-bound kernels), and let the main stream wait for them right before
@@ -953,6 +956,9 @@ class TrainStep:
         read from the device block, so nothing of it is frozen into the graph.  Text tower: pass ``token_packing`` (host-prepared index
         vectors) or run the padded layout -- the device-side packing synchronises with the host and cannot be captured."""
         tp = token_packing
+        if self.graph and hasattr(sample_items, "catalogue"):      # data_utils.images.ImageIds
+            raise SystemExit("--images_on_device: --graph copies a batch into static pixel buffers; graph capture of an ids-only vision "
+                             "step is not built")
         if (not self.graph or self.dedup_items or len(self.text_attrs) > 1
                 or (self.model.use_modal and not self.vision and tp is None and engine.UNPAD_DEFAULT)):
             return self.step(sample_items_id, sample_items, log_mask, token_packing)

@@ -994,6 +994,24 @@ int morec_probe(int32_t* out, void* stream);
 int morec_image_resize_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, uint8_t* out, int n, int R, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The image catalogue on the device, a batch as its item ids (csrc/image_ids.hip): the indexed forms of the three kernels through
+ * which decoded uint8 images enter a vision tower.  catalogue: uint8 [n_rows, R, R, channels] ([n_rows, H, W, C] for the NHWC form);
+ * ids: int32 [n_img] on the device; the remaining arguments are the parent's.  Image k of the output is computed from catalogue
+ * row ids[k], clamped into [0, n_rows - 1] (a bad id never reads outside the catalogue; hosts reject it before it gets here).
+ * The arithmetic is the parent's, so the output is bit-equal to a row gather of the catalogue followed by the parent.  The MAE form
+ * takes its kept patches from keep[k] and its pixels from row ids[k].  RGB catalogues with patch % 4 == 0 (H W C % 4 == 0) move 4
+ * pixels (4 bytes) per thread; other shapes move single elements.  No atomics, one writer per output element.
+ * Errors as the parents', judged before any launch; n_rows <= 0 or n_img <= 0: MOREC_E_ARG.
+ * ------------------------------------------------------------------------------------------ */
+int morec_swin_patchify_u8_idx(const uint8_t* catalogue, const int32_t* ids, int n_rows, void* out, int n_img, int channels, int R,
+                               int patch, int ld_out, float mean, float std, int dtype, void* stream);
+int morec_mae_patchify_keep_u8_idx(const uint8_t* catalogue, const int32_t* ids, int n_rows, const int32_t* keep, void* out, int n_img,
+                                   int channels, int R, int patch, int len_keep, int ld_out, float mean, float std, int dtype,
+                                   void* stream);
+int morec_pixels_to_nhwc_idx(const uint8_t* catalogue, const int32_t* ids, int n_rows, void* out, int n_img, int C, int H, int W,
+                             float mean, float std, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Collectives of the data-parallel step on the CALLER's stream (RCCL over xGMI, resolved with dlopen from the
  * librccl.so.1 already mapped in the process -- PyTorch's -- and never linked).  They replace, stream-ordered with the kernels
  * around them, what the reference gets from DistributedDataParallel's NCCL hooks (T/run.py:148,321) plus the exchange the
