@@ -140,12 +140,7 @@ def beit_forward(p: dict, prep, shape: BeitShape, pixels: torch.Tensor, dtype, n
     C, heads, g = shape.hidden_size, shape.num_attention_heads, shape.grid
     engine.check_image_size(pixels, shape.image_size)
     T = shape.num_patches + 1
-    if hasattr(pixels, "catalogue"):    # data_utils.images.ImageIds: the im2col reads the device catalogue's rows through the ids
-        patches = ops.swin_patchify_u8_idx(*engine.catalogue_and_ids(pixels), shape.patch_size, dtype)
-    elif pixels.dtype == torch.uint8:
-        patches = ops.swin_patchify_u8(pixels.contiguous(), shape.patch_size, dtype)
-    else:
-        patches = ops.swin_patchify(pixels.contiguous(), shape.patch_size, dtype)
+    patches = engine.patch_rows(pixels, shape.patch_size, dtype)
     e = ops.gemm_nt(patches, prep["patch"].w, bias=p[net + "embeddings.patch_embeddings.projection.bias"])
     x = ops.beit_assemble_fwd(e, p[net + "embeddings.cls_token"].reshape(-1), n_img)
     key_keep = torch.ones((n_img, T), device=x.device, dtype=torch.float32)

@@ -228,7 +228,6 @@ __global__ __launch_bounds__(256) void beit_assemble_fwd_kernel(const T* __restr
     }
 }
 
-int beit_grid(size_t total) { return (int)std::min<size_t>((total + 255) / 256, 256 * 32); }
 int check_rows(size_t M, int N, int dtype) {
     if (M == 0 || N <= 0) return MOREC_E_ARG;
     if (dtype != MOREC_F32 && !is_h16(dtype)) return MOREC_E_DTYPE;
@@ -268,7 +267,7 @@ extern "C" int morec_layerscale_res_fwd(const void* a, const float* bias, const 
     const size_t total = (size_t)M * (N / (16 / elt_size(dtype)));
     by_dtype(dtype, [&](auto tag) {
         using T = MOREC_TAG_T(tag);
-        hipLaunchKernelGGL((layerscale_res_fwd_kernel<T>), dim3(beit_grid(total)), dim3(256), 0, s, (const T*)a, bias, lam, (const T*)res,
+        hipLaunchKernelGGL((layerscale_res_fwd_kernel<T>), dim3(grid_for(total)), dim3(256), 0, s, (const T*)a, bias, lam, (const T*)res,
                            rowscale, rowscale ? rows_per_scale : 1, (T*)h, (size_t)M, N);
     });
     MOREC_CHECK_LAUNCH();
@@ -328,7 +327,7 @@ extern "C" int morec_beit_pool_bwd(const void* dpool, void* dx, int n_img, int T
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     by_dtype(dtype, [&](auto tag) {
         using Ty = MOREC_TAG_T(tag);
-        hipLaunchKernelGGL((beit_pool_bwd_kernel<Ty>), dim3(beit_grid(total)), dim3(256), 0, s, (const Ty*)dpool, (Ty*)dx, n_img, T, C);
+        hipLaunchKernelGGL((beit_pool_bwd_kernel<Ty>), dim3(grid_for(total)), dim3(256), 0, s, (const Ty*)dpool, (Ty*)dx, n_img, T, C);
     });
     MOREC_CHECK_LAUNCH();
     return MOREC_OK;
@@ -343,7 +342,7 @@ extern "C" int morec_beit_assemble_fwd(const void* e, const float* cls_token, vo
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     by_dtype(dtype, [&](auto tag) {
         using Ty = MOREC_TAG_T(tag);
-        hipLaunchKernelGGL((beit_assemble_fwd_kernel<Ty>), dim3(beit_grid(total)), dim3(256), 0, s, (const Ty*)e, cls_token, (Ty*)x, n_img, N, C);
+        hipLaunchKernelGGL((beit_assemble_fwd_kernel<Ty>), dim3(grid_for(total)), dim3(256), 0, s, (const Ty*)e, cls_token, (Ty*)x, n_img, N, C);
     });
     MOREC_CHECK_LAUNCH();
     return MOREC_OK;

@@ -427,6 +427,23 @@ static inline bool by_h16(int dtype, F&& f) {
     }
 }
 #define MOREC_TAG_T(tag) typename std::remove_pointer<decltype(tag)>::type
+// blocks of 256 threads for a grid-stride loop over `total` work items
+static inline int grid_for(size_t total) {
+    const size_t blocks = (total + 255) / 256;
+    return blocks < 256 * 32 ? (int)blocks : 256 * 32;
+}
+// the rules of the kept-patch im2col (morec_mae_patchify_keep, morec_mae_patchify_keep_u8[_idx]), in the order they are judged
+static inline int check_patchify(const void* pixels, const int32_t* keep, const void* out, int n_img, int channels, int R, int patch,
+                                 int len_keep, int ld_out, int dtype) {
+    if (!pixels || !keep || !out || n_img <= 0 || channels <= 0 || R <= 0 || patch <= 0 || len_keep <= 0) return MOREC_E_ARG;
+    if (dtype != MOREC_F32 && !is_h16(dtype)) return MOREC_E_DTYPE;
+    if (R % patch) return MOREC_E_UNSUPPORTED;
+    if (len_keep > (R / patch) * (R / patch)) return MOREC_E_ARG;
+    const int ev = 16 / elt_size(dtype);
+    // whole 16-byte lanes: runs of 4 pixels on the input side, EV elements on the output side
+    if (patch % 4 || (channels * patch * patch) % ev || ld_out < channels * patch * patch || ld_out % ev || !aligned16(out)) return MOREC_E_ALIGN;
+    return MOREC_OK;
+}
 #define MOREC_CHECK_LAUNCH()                        \
     do {                                            \
         hipError_t e__ = hipGetLastError();         \

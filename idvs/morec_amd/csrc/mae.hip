@@ -1,6 +1,6 @@
 // mae.hip -- the front of the MAE (ViT) item tower: HF ViTMAEEmbeddings (modeling_vit_mae.py:182-327) for the KEPT patches only.
 //   * keep_ids        random_masking's argsort(noise)[:, :len_keep] (:297-327), one workgroup per image           (ranking in LDS)
-//   * patchify_keep   the normalising im2col of swin.hip's patchify / patchify_u8, rows of the kept patches only
+//   * patchify_keep   the im2col of swin.hip's patchify, rows of the kept patches only (from uint8 images: image_front.hip)
 //   * assemble        [CLS] + position row 0, kept patch embeddings + their position rows (:259-267); backward
 // HF projects every patch and gathers len_keep of them afterwards; here only the kept patches get an im2col row and a row of the
 // patch GEMM.  No atomics, every output element is written exactly once, the same bits on every run.
@@ -71,41 +71,6 @@ __global__ __launch_bounds__(256) void mae_patchify_keep_kernel(const float* __r
                 io<float>::load4(px + (((size_t)n * Cin + c) * R + (py * ps + i)) * R + pxx * ps + jj, t);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) v[4 * q + u] = t[u];
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < EV; ++u) v[u] = 0.f;
-        }
-        vio<T>::store(out + row * ld_out + k0, v);
-    }
-}
-
-// The same rows from decoded uint8 HWC images, ToTensor + Normalize applied in flight in swin_patchify_u8_kernel's operation order.
-template <typename T>
-__global__ __launch_bounds__(256) void mae_patchify_keep_u8_kernel(const uint8_t* __restrict__ px, const int32_t* __restrict__ keep,
-                                                                   T* __restrict__ out, int n_img, int Cin, int R, int ps, int len_keep,
-                                                                   int ld_out, float mean, float std) {
-    constexpr int EV = vio<T>::EV;
-    const int G = R / ps;
-    const int K = Cin * ps * ps;
-    const int chunks = K / EV;
-    const size_t total = (size_t)n_img * len_keep * chunks;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const size_t row = e / chunks;
-        const int k0 = (int)(e - row * chunks) * EV;
-        const int n = (int)(row / len_keep);
-        const int patch = keep[row];
-        float v[EV];
-        if ((unsigned)patch < (unsigned)(G * G)) {
-            const int py = patch / G, pxx = patch - py * G;
-#pragma unroll
-            for (int q = 0; q < EV / 4; ++q) {
-                const int k = k0 + 4 * q;
-                const int ci = k / ps, jj = k - ci * ps;
-                const int c = ci / ps, i = ci - c * ps;
-                const uint8_t* src = px + (((size_t)n * R + (py * ps + i)) * R + pxx * ps + jj) * Cin + c;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) v[4 * q + u] = ((float)src[u * Cin] / 255.0f - mean) / std;
             }
         } else {
 #pragma unroll
@@ -195,20 +160,6 @@ __global__ __launch_bounds__(CLS_NT) void mae_assemble_bwd_kernel(const T* __res
     if (threadIdx.x < EV) d_cls[c0 + threadIdx.x] = part[0][threadIdx.x];
 }
 
-int mae_grid(size_t total) { return (int)std::min<size_t>((total + 255) / 256, 256 * 32); }
-
-int check_patchify(const void* pixels, const int32_t* keep, const void* out, int n_img, int channels, int R, int patch, int len_keep,
-                   int ld_out, int dtype) {
-    if (!pixels || !keep || !out || n_img <= 0 || channels <= 0 || R <= 0 || patch <= 0 || len_keep <= 0) return MOREC_E_ARG;
-    if (dtype != MOREC_F32 && !is_h16(dtype)) return MOREC_E_DTYPE;
-    if (R % patch) return MOREC_E_UNSUPPORTED;
-    if (len_keep > (R / patch) * (R / patch)) return MOREC_E_ARG;
-    const int ev = 16 / elt_size(dtype);
-    // whole 16-byte lanes: runs of 4 pixels on the input side, EV elements on the output side
-    if (patch % 4 || (channels * patch * patch) % ev || ld_out < channels * patch * patch || ld_out % ev || !aligned16(out)) return MOREC_E_ALIGN;
-    return MOREC_OK;
-}
-
 }  // namespace
 
 extern "C" int morec_mae_keep_ids(const float* noise, uint64_t seed, int32_t* keep, int n_img, int N, int len_keep, void* stream) {
@@ -232,24 +183,8 @@ extern "C" int morec_mae_patchify_keep(const float* pixels, const int32_t* keep,
     const size_t total = (size_t)n_img * len_keep * (channels * patch * patch / (16 / elt_size(dtype)));
     by_dtype(dtype, [&](auto tag) {
         using T = MOREC_TAG_T(tag);
-        hipLaunchKernelGGL((mae_patchify_keep_kernel<T>), dim3(mae_grid(total)), dim3(256), 0, s, pixels, keep, (T*)out, n_img, channels, R,
+        hipLaunchKernelGGL((mae_patchify_keep_kernel<T>), dim3(grid_for(total)), dim3(256), 0, s, pixels, keep, (T*)out, n_img, channels, R,
                            patch, len_keep, ld_out);
-    });
-    MOREC_CHECK_LAUNCH();
-    return MOREC_OK;
-}
-
-extern "C" int morec_mae_patchify_keep_u8(const uint8_t* pixels_hwc, const int32_t* keep, void* out, int n_img, int channels, int R,
-                                          int patch, int len_keep, int ld_out, float mean, float std, int dtype, void* stream) {
-    const int rc = check_patchify(pixels_hwc, keep, out, n_img, channels, R, patch, len_keep, ld_out, dtype);
-    if (rc != MOREC_OK) return rc;
-    if (std == 0.f) return MOREC_E_ARG;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const size_t total = (size_t)n_img * len_keep * (channels * patch * patch / (16 / elt_size(dtype)));
-    by_dtype(dtype, [&](auto tag) {
-        using T = MOREC_TAG_T(tag);
-        hipLaunchKernelGGL((mae_patchify_keep_u8_kernel<T>), dim3(mae_grid(total)), dim3(256), 0, s, pixels_hwc, keep, (T*)out, n_img,
-                           channels, R, patch, len_keep, ld_out, mean, std);
     });
     MOREC_CHECK_LAUNCH();
     return MOREC_OK;
@@ -265,7 +200,7 @@ extern "C" int morec_mae_assemble_fwd(const void* e, const float* cls_token, con
     const size_t total = (size_t)n_img * (len_keep + 1) * (C / (16 / elt_size(dtype)));
     by_dtype(dtype, [&](auto tag) {
         using T = MOREC_TAG_T(tag);
-        hipLaunchKernelGGL((mae_assemble_fwd_kernel<T>), dim3(mae_grid(total)), dim3(256), 0, s, (const T*)e, cls_token, pos, keep, (T*)x,
+        hipLaunchKernelGGL((mae_assemble_fwd_kernel<T>), dim3(grid_for(total)), dim3(256), 0, s, (const T*)e, cls_token, pos, keep, (T*)x,
                            n_img, len_keep, N, C);
     });
     MOREC_CHECK_LAUNCH();
@@ -278,7 +213,7 @@ extern "C" int morec_mae_assemble_bwd(const void* dx, void* de, float* d_cls, in
     if (C % 8 || !aligned16(dx) || !aligned16(de)) return MOREC_E_ALIGN;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int ev = 16 / elt_size(dtype);
-    const int copy_blocks = mae_grid((size_t)n_img * len_keep * (C / ev));
+    const int copy_blocks = grid_for((size_t)n_img * len_keep * (C / ev));
     by_dtype(dtype, [&](auto tag) {
         using T = MOREC_TAG_T(tag);
         hipLaunchKernelGGL((mae_assemble_bwd_kernel<T>), dim3(copy_blocks + C / ev), dim3(CLS_NT), 0, s, (const T*)dx, (T*)de, d_cls, n_img,

@@ -1,5 +1,5 @@
 // resnet.hip -- the kernels of the ResNet item tower that are not convolutions (resnet_engine.py), over NHWC activations viewed as
-// [rows, C] with rows = N H W: BatchNorm2d, the 3 x 3 stride-2 max pool and the pixel layout change in front of the stem.
+// [rows, C] with rows = N H W: BatchNorm2d and the 3 x 3 stride-2 max pool (the pixel layout change in front of the stem: image_front.hip).
 //
 // BatchNorm statistics are (count, mean, M2) partials per slab of BN_SLAB rows and per channel: the slab mean first, then the squares of the
 // deviations from THAT mean -- never E[x^2] - mean^2, which loses the digits of a post-ReLU activation (mean ~ std) in the fp32 parity
@@ -19,8 +19,6 @@
 namespace {
 constexpr int BN_SLAB = 1024;      // rows per statistics partial
 constexpr int BN_RL = 16;          // row lanes of a block: thread = (row lane, channel vector)
-
-int grid_for(size_t total) { return (int)std::min<size_t>((total + 255) / 256, 256 * 32); }
 
 // fixed-order sum over the BN_RL row lanes of a block: v[EV] of thread (ry, cx) -> the totals, in every thread of the column
 template <int EV>
@@ -351,25 +349,6 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
     }
 }
 
-// ---- pixels -> NHWC rows [n H W, C] in the compute type: fp32 NCHW as it is, or uint8 NHWC under ToTensor + Normalize
-template <typename T>
-__global__ __launch_bounds__(256) void pixels_to_nhwc_kernel(const void* __restrict__ src, T* __restrict__ out, int n, int C, int H, int W,
-                                                             int src_u8, float mean, float std) {
-    const size_t hw = (size_t)H * W, total = (size_t)n * hw * C;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        float v;
-        if (src_u8) {
-            v = ((float)reinterpret_cast<const uint8_t*>(src)[e] / 255.0f - mean) / std;
-        } else {
-            const size_t pix = e / C;
-            const int c = (int)(e - pix * C);
-            const size_t img = pix / hw;
-            v = reinterpret_cast<const float*>(src)[(img * C + c) * hw + (pix - img * hw)];
-        }
-        io<T>::store1(out + e, v);
-    }
-}
-
 int vec_check(const void* a, const void* b, long long rows, int C) {
     if (!a || !b || rows <= 0 || C <= 0) return MOREC_E_ARG;
     if (C % 8 || !aligned16(a) || !aligned16(b)) return MOREC_E_ALIGN;
@@ -544,16 +523,3 @@ extern "C" int morec_maxpool3x3s2_bwd(const void* dy, const uint8_t* idx, void* 
     return MOREC_OK;
 }
 
-extern "C" int morec_pixels_to_nhwc(const void* src, void* out, int n, int C, int H, int W, int src_u8, float mean, float std, int dtype,
-                                    void* stream) {
-    if (!src || !out || n <= 0 || C <= 0 || H <= 0 || W <= 0 || (src_u8 && !(std > 0.f))) return MOREC_E_ARG;
-    const size_t total = (size_t)n * H * W * C;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (!by_dtype(dtype, [&](auto* t) {
-            using T = MOREC_TAG_T(t);
-            hipLaunchKernelGGL((pixels_to_nhwc_kernel<T>), dim3(grid_for(total)), dim3(256), 0, s, src, (T*)out, n, C, H, W, src_u8, mean, std);
-        }))
-        return MOREC_E_DTYPE;
-    MOREC_CHECK_LAUNCH();
-    return MOREC_OK;
-}

@@ -194,8 +194,8 @@ HEADROOM_BYTES = 1 << 30            # what has to stay free next to the catalogu
 
 class ImageIds:
     """A batch of images as item ids into a uint8 catalogue on the device: what the towers accept wherever they accept a uint8 pixel
-    tensor.  Their first kernel reads image k's pixels from ``catalogue[ids[k]]`` (``ops.*_idx``), so the batch that crosses PCIe is the
-    ids.  ``shape`` / ``dtype`` / ``device`` / ``reshape`` / ``view`` behave like those of the uint8 ``[*ids.shape, R, R, 3]`` tensor that
+    tensor.  Their first kernel reads image k's pixels from ``catalogue[ids[k]]`` (the ``ids=`` argument of ``ops.swin_patchify_u8`` /
+    ``mae_patchify_keep`` / ``pixels_to_nhwc``), so the batch that crosses PCIe is the ids.  ``shape`` / ``dtype`` / ``device`` / ``reshape`` / ``view`` behave like those of the uint8 ``[*ids.shape, R, R, 3]`` tensor that
     ``catalogue[ids]`` would be: ``reshape`` takes that tensor's new shape and keeps the ids' leading dimensions."""
 
     def __init__(self, catalogue, ids):

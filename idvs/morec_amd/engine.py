@@ -281,11 +281,28 @@ def mlp_backward(d, w: dict, g, pre, hn, g_fc2_w, g_fc1_b, g_fc1_w, C: int):
     return ops.gemm_nt(du, w["f1"].wt, K=du.shape[1], N=C)
 
 
-def catalogue_and_ids(pixels):
-    """``data_utils.images.ImageIds`` in a tower's forward -> (uint8 catalogue [n_rows, H, W, 3], int32 ids [n_img]): one id per image."""
+def image_source(pixels):
+    """A tower's pixel batch -> ``(tensor, ids)`` for the front kernels: a pixel tensor made contiguous and None, or -- for a
+    ``data_utils.images.ImageIds`` -- the uint8 catalogue [n_rows, H, W, 3] on the device and its int32 ids [n_img], one per image."""
+    if not hasattr(pixels, "catalogue"):
+        return pixels.contiguous(), None
     if pixels.ids.dim() != 1:
         raise ValueError(f"an ImageIds batch enters a tower flat ([n_img] ids), got ids of shape {tuple(pixels.ids.shape)}")
     return pixels.catalogue, pixels.ids
+
+
+def patch_rows(pixels, patch: int, dtype, rows_image_size: int | None = None):
+    """The im2col rows [n_img (R / patch)^2, 3 patch^2] of the Swin / BEiT patch embedding: decoded uint8 HWC images or an ``ImageIds`` batch
+    (ToTensor + Normalize(0.5, 0.5) fused into the im2col, §8(f)-3) or fp32 NCHW pixels.  ``rows_image_size`` (the Swin tower passes its
+    image size): a ``data_utils.images.PatchRows``, whose im2col already ran (on the input feed's stream, under the previous step), is
+    accepted too."""
+    if rows_image_size is not None and hasattr(pixels, "patches"):
+        assert pixels.patches.dtype == dtype and pixels.patches.shape[0] == pixels.shape[0] * (rows_image_size // patch) ** 2
+        return pixels.patches
+    src, ids = image_source(pixels)
+    if src.dtype == torch.uint8:
+        return ops.swin_patchify_u8(src, patch, dtype, ids=ids)
+    return ops.swin_patchify(src, patch, dtype)
 
 
 def check_image_size(pixels: torch.Tensor, image_size: int):

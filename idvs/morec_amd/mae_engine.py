@@ -122,10 +122,8 @@ def mae_forward(p: dict, prep, shape: MaeShape, pixels: torch.Tensor, dtype, nee
     keep = mae_keep(shape, n_img, pixels.device, noise, seed, mask_ratio)
     Lk = keep.shape[1]
     T = Lk + 1
-    if hasattr(pixels, "catalogue"):    # data_utils.images.ImageIds: kept patches from keep[k], pixels from catalogue row ids[k]
-        patches = ops.mae_patchify_keep_u8_idx(*engine.catalogue_and_ids(pixels), keep, shape.patch_size, dtype)
-    else:
-        patches = ops.mae_patchify_keep(pixels.contiguous(), keep, shape.patch_size, dtype)
+    src, ids = engine.image_source(pixels)      # ImageIds: kept patches from keep[k], pixels from catalogue row ids[k]
+    patches = ops.mae_patchify_keep(src, keep, shape.patch_size, dtype, ids=ids)
     e = ops.gemm_nt(patches, prep["patch"].w, bias=p[net + "embeddings.patch_embeddings.projection.bias"])
     x = ops.mae_assemble_fwd(e, p[net + "embeddings.cls_token"].reshape(-1), p[net + "embeddings.position_embeddings"].reshape(-1, C), keep)
     key_keep = torch.ones((n_img, T), device=x.device, dtype=torch.float32)

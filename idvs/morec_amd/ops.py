@@ -1079,25 +1079,9 @@ def swin_patchify(pixels, patch, dtype):
     return out
 
 
-def swin_patchify_u8(pixels_hwc, patch, dtype, mean=0.5, std=0.5, out=None):
-    """uint8 [n, R, R, 3] decoded images -> normalised patch rows (ToTensor + Normalize(0.5, 0.5), V/data_utils/dataset.py:69-73).
-    ``out``: a caller-owned [n G G, 3 patch^2] buffer of ``dtype`` (the double-buffered input feed, ``data_utils.images.DeviceImageFeed``)."""
-    _dev(pixels_hwc)
-    if pixels_hwc.dtype != torch.uint8:
-        raise _lib.MorecError("expected uint8 HWC images")
-    n, R, _, c = pixels_hwc.shape
-    G = R // patch
-    if out is None:
-        out = torch.empty((n * G * G, c * patch * patch), device=pixels_hwc.device, dtype=dtype)
-    else:
-        assert out.shape == (n * G * G, c * patch * patch) and out.dtype == dtype and out.is_contiguous()
-    check(_lib.lib().morec_swin_patchify_u8(_p(pixels_hwc), _p(out), n, c, R, patch, out.stride(0), mean, std, code(dtype), _stream()),
-          "morec_swin_patchify_u8")
-    return out
-
-
 # ---------------------------------------------------------------------------------------------------------
-# Image catalogue on the device, a batch as its item ids (csrc/image_ids.hip)
+# uint8 image fronts (csrc/image_front.hip): decoded images in batch order, or -- with ``ids`` -- the rows ``ids[k]`` of an image
+# catalogue that stays on the device
 # ---------------------------------------------------------------------------------------------------------
 def check_catalogue_ids(ids, n_rows):
     """Host-side ids (numpy array or CPU tensor) outside ``[0, n_rows)`` raise here, before anything is uploaded: the kernels only clamp."""
@@ -1128,39 +1112,28 @@ def catalogue_ids(catalogue, ids):
     return ids.to(device=catalogue.device, dtype=torch.int32).reshape(-1).contiguous()
 
 
-def swin_patchify_u8_idx(catalogue, ids, patch, dtype, mean=0.5, std=0.5):
-    """``swin_patchify_u8(catalogue[ids], ...)`` without the gather: the kernel reads image k's pixels from catalogue row ``ids[k]``."""
-    ids = catalogue_ids(catalogue, ids)
-    n_rows, R, _, c = catalogue.shape
-    n, G = ids.numel(), R // patch
-    out = torch.empty((n * G * G, c * patch * patch), device=catalogue.device, dtype=dtype)
-    check(_lib.lib().morec_swin_patchify_u8_idx(_p(catalogue), _p(ids), n_rows, _p(out), n, c, R, patch, out.stride(0), mean, std, code(dtype),
-                                                _stream()), "morec_swin_patchify_u8_idx")
-    return out
-
-
-def mae_patchify_keep_u8_idx(catalogue, ids, keep, patch, dtype, mean=0.5, std=0.5):
-    """``mae_patchify_keep(catalogue[ids], keep, ...)`` without the gather: patches from ``keep[k]``, pixels from row ``ids[k]``."""
-    ids = catalogue_ids(catalogue, ids)
-    _dev(keep)
-    n_img, len_keep = keep.shape
-    if keep.dtype != torch.int32 or ids.numel() != n_img:
-        raise _lib.MorecError("mae keep must be int32 [n_img, len_keep]")
-    n_rows, R, _, c = catalogue.shape
-    out = torch.empty((n_img * len_keep, c * patch * patch), device=catalogue.device, dtype=dtype)
-    check(_lib.lib().morec_mae_patchify_keep_u8_idx(_p(catalogue), _p(ids), n_rows, _p(keep), _p(out), n_img, c, R, patch, len_keep,
-                                                    out.stride(0), mean, std, code(dtype), _stream()), "morec_mae_patchify_keep_u8_idx")
-    return out
-
-
-def pixels_to_nhwc_idx(catalogue, ids, dtype, mean=0.5, std=0.5):
-    """``pixels_to_nhwc(catalogue[ids], ...)`` without the gather -> [n H W, C] rows."""
-    ids = catalogue_ids(catalogue, ids)
-    n_rows, H, W, Cc = catalogue.shape
-    n = ids.numel()
-    out = torch.empty((n * H * W, Cc), device=catalogue.device, dtype=dtype)
-    check(_lib.lib().morec_pixels_to_nhwc_idx(_p(catalogue), _p(ids), n_rows, _p(out), n, Cc, H, W, float(mean), float(std), code(dtype),
-                                              _stream()), "morec_pixels_to_nhwc_idx")
+def swin_patchify_u8(pixels, patch, dtype, mean=0.5, std=0.5, out=None, ids=None):
+    """uint8 [n, R, R, 3] decoded images -> normalised patch rows (ToTensor + Normalize(0.5, 0.5), V/data_utils/dataset.py:69-73).
+    ``ids``: ``pixels`` is the image catalogue, image k of the batch its row ``ids[k]`` (``swin_patchify_u8(pixels[ids], ...)`` without the gather).
+    ``out``: a caller-owned [n G G, 3 patch^2] buffer of ``dtype`` (the double-buffered input feed, ``data_utils.images.DeviceImageFeed``)."""
+    _dev(pixels)
+    if pixels.dtype != torch.uint8:
+        raise _lib.MorecError("expected uint8 HWC images")
+    if ids is not None:
+        ids = catalogue_ids(pixels, ids)
+    n_rows, R, _, c = pixels.shape
+    n = n_rows if ids is None else ids.numel()
+    G = R // patch
+    if out is None:
+        out = torch.empty((n * G * G, c * patch * patch), device=pixels.device, dtype=dtype)
+    else:
+        assert out.shape == (n * G * G, c * patch * patch) and out.dtype == dtype and out.is_contiguous()
+    if ids is None:
+        check(_lib.lib().morec_swin_patchify_u8(_p(pixels), _p(out), n, c, R, patch, out.stride(0), mean, std, code(dtype), _stream()),
+              "morec_swin_patchify_u8")
+    else:
+        check(_lib.lib().morec_swin_patchify_u8_idx(_p(pixels), _p(ids), n_rows, _p(out), n, c, R, patch, out.stride(0), mean, std, code(dtype),
+                                                    _stream()), "morec_swin_patchify_u8_idx")
     return out
 
 
@@ -1219,18 +1192,25 @@ def mae_keep_ids(n_img, N, len_keep, *, noise=None, seed=0, device="cuda"):
     return keep
 
 
-def mae_patchify_keep(pixels, keep, patch, dtype, mean=0.5, std=0.5):
+def mae_patchify_keep(pixels, keep, patch, dtype, mean=0.5, std=0.5, ids=None):
     """The im2col rows of the kept patches only: fp32 NCHW pixels, or uint8 [n, R, R, 3] decoded images (normalised in flight) ->
-    [n * len_keep, 3 patch^2] of ``dtype``; bit-equal to ``swin_patchify[_u8]`` followed by a row gather."""
+    [n * len_keep, 3 patch^2] of ``dtype``; bit-equal to ``swin_patchify[_u8]`` followed by a row gather.  ``ids``: ``pixels`` is the uint8
+    image catalogue -- patches from ``keep[k]``, pixels from its row ``ids[k]``."""
     _dev(pixels), _dev(keep)
+    if ids is not None:
+        ids = catalogue_ids(pixels, ids)
     n_img, len_keep = keep.shape
-    if keep.dtype != torch.int32 or pixels.shape[0] != n_img:
+    if keep.dtype != torch.int32 or (pixels.shape[0] if ids is None else ids.numel()) != n_img:
         raise _lib.MorecError("mae keep must be int32 [n_img, len_keep]")
     if pixels.dtype == torch.uint8:
-        _, R, _, c = pixels.shape
+        n_rows, R, _, c = pixels.shape
         out = torch.empty((n_img * len_keep, c * patch * patch), device=pixels.device, dtype=dtype)
-        check(_lib.lib().morec_mae_patchify_keep_u8(_p(pixels), _p(keep), _p(out), n_img, c, R, patch, len_keep, out.stride(0), mean, std,
-                                                    code(dtype), _stream()), "morec_mae_patchify_keep_u8")
+        if ids is None:
+            check(_lib.lib().morec_mae_patchify_keep_u8(_p(pixels), _p(keep), _p(out), n_img, c, R, patch, len_keep, out.stride(0), mean, std,
+                                                        code(dtype), _stream()), "morec_mae_patchify_keep_u8")
+        else:
+            check(_lib.lib().morec_mae_patchify_keep_u8_idx(_p(pixels), _p(ids), n_rows, _p(keep), _p(out), n_img, c, R, patch, len_keep,
+                                                            out.stride(0), mean, std, code(dtype), _stream()), "morec_mae_patchify_keep_u8_idx")
         return out
     if pixels.dtype != torch.float32:
         raise _lib.MorecError("pixels must be fp32 NCHW or uint8 NHWC")
@@ -1629,9 +1609,17 @@ def maxpool3x3s2_bwd(dy, idx, N, H, W):
     return dx
 
 
-def pixels_to_nhwc(pixels, dtype, mean=0.5, std=0.5):
-    """fp32 [n, C, H, W] (normalised already) or uint8 [n, H, W, C] (decoded: ``(x / 255 - mean) / std`` is applied) -> [n H W, C] rows."""
+def pixels_to_nhwc(pixels, dtype, mean=0.5, std=0.5, ids=None):
+    """fp32 [n, C, H, W] (normalised already) or uint8 [n, H, W, C] (decoded: ``(x / 255 - mean) / std`` is applied) -> [n H W, C] rows.
+    ``ids``: ``pixels`` is the uint8 image catalogue, image k of the batch its row ``ids[k]``."""
     _dev(pixels)
+    if ids is not None:
+        ids = catalogue_ids(pixels, ids)
+        n_rows, H, W, Cc = pixels.shape
+        out = torch.empty((ids.numel() * H * W, Cc), device=pixels.device, dtype=dtype)
+        check(_lib.lib().morec_pixels_to_nhwc_idx(_p(pixels), _p(ids), n_rows, _p(out), ids.numel(), Cc, H, W, float(mean), float(std),
+                                                  code(dtype), _stream()), "morec_pixels_to_nhwc_idx")
+        return out
     u8 = pixels.dtype == torch.uint8
     if not u8 and pixels.dtype != torch.float32:
         raise _lib.MorecError("pixels must be fp32 NCHW or uint8 NHWC")

@@ -211,10 +211,8 @@ def resnet_forward(p: dict, bufs: dict, prep, shape, pixels: torch.Tensor, dtype
     q["eps"], q["momentum"] = shape.eps, shape.momentum
     u8 = pixels.dtype == torch.uint8
     N, H, W = (pixels.shape[0], pixels.shape[1], pixels.shape[2]) if u8 else (pixels.shape[0], pixels.shape[2], pixels.shape[3])
-    if hasattr(pixels, "catalogue"):    # data_utils.images.ImageIds: the conversion reads the device catalogue's rows through the ids
-        x0 = ops.pixels_to_nhwc_idx(*engine.catalogue_and_ids(pixels), dtype)
-    else:
-        x0 = ops.pixels_to_nhwc(pixels.contiguous(), dtype)
+    src, ids = engine.image_source(pixels)      # ImageIds: the conversion reads the device catalogue's rows through the ids
+    x0 = ops.pixels_to_nhwc(src, dtype, ids=ids)
     tape = []
     c0, g1, _ = _conv_fwd(x0, (N, H, W), prep[prefix + "conv1.weight"])
     y0, s0 = _bn_fwd(q, bufs, prefix + "bn1", c0, training, True, sync=sync)

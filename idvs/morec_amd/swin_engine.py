@@ -132,15 +132,7 @@ def swin_forward(p: dict, prep, shape: SwinShape, pixels: torch.Tensor, dtype, n
     sw = prefix + "swin."
     n_img = pixels.shape[0]
     eps = shape.layer_norm_eps
-    if hasattr(pixels, "patches"):    # data_utils.images.PatchRows: the normalising im2col already ran (on the input feed's stream, under the previous step)
-        patches = pixels.patches
-        assert patches.dtype == dtype and patches.shape[0] == n_img * (shape.image_size // shape.patch_size) ** 2
-    elif hasattr(pixels, "catalogue"):  # data_utils.images.ImageIds: the catalogue is on the device, the im2col reads its rows through the ids
-        patches = ops.swin_patchify_u8_idx(*engine.catalogue_and_ids(pixels), shape.patch_size, dtype)
-    elif pixels.dtype == torch.uint8:   # decoded HWC images: ToTensor + Normalize(0.5, 0.5) fused into the im2col (§8(f)-3)
-        patches = ops.swin_patchify_u8(pixels.contiguous(), shape.patch_size, dtype)
-    else:
-        patches = ops.swin_patchify(pixels.contiguous(), shape.patch_size, dtype)
+    patches = engine.patch_rows(pixels, shape.patch_size, dtype, rows_image_size=shape.image_size)
     e = ops.gemm_nt(patches, prep["patch"].w, bias=p[sw + "embeddings.patch_embeddings.projection.bias"])
     x, _, mean_e, rstd_e = ops.layernorm_fwd(e, p[sw + "embeddings.norm.weight"], p[sw + "embeddings.norm.bias"], 1e-5,
                                              save_z=False)

@@ -440,7 +440,9 @@ int morec_swin_bias_reduce(const float* dbias_t, float* dtable, int window, int 
 int morec_swin_patchify(const float* pixels, void* out, int n_img, int channels, int R, int patch, int ld_out, int dtype,
                         void* stream);
 /* the same rows from decoded uint8 HWC images [n, R, R, channels]: ToTensor + Normalize(mean, std) of
- * V/data_utils/dataset.py:69-73 applied in flight (fp32, reference operation order: (x / 255 - mean) / std). */
+ * V/data_utils/dataset.py:69-73 applied in flight (fp32, reference operation order: (x / 255 - mean) / std).  The uint8 fronts --
+ * this one, morec_mae_patchify_keep_u8 and the uint8 case of morec_pixels_to_nhwc -- live in csrc/image_front.hip, one kernel per
+ * layout shared with their _idx forms (below: "The image catalogue on the device"). */
 int morec_swin_patchify_u8(const uint8_t* pixels_hwc, void* out, int n_img, int channels, int R, int patch, int ld_out,
                            float mean, float std, int dtype, void* stream);
 /* SwinPatchMerging gather (:309-320): [n,H,W,C] -> [n,H/2,W/2,4C]; reverse != 0 is the inverse copy (backward). */
@@ -583,7 +585,7 @@ int morec_bn_bwd_apply_n(const void* dy, const void* y, const void* x, const flo
 int morec_maxpool3x3s2_fwd(const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, int dtype, void* stream);
 int morec_maxpool3x3s2_bwd(const void* dy, const uint8_t* idx, void* dx, int N, int H, int W, int C, int dtype, void* stream);
 /* src fp32 [n, C, H, W] (src_u8 == 0; copied), or uint8 [n, H, W, C] (src_u8 != 0; (x / 255 - mean) / std as morec_swin_patchify_u8)
- * -> out [n H W, C] of the storage type. */
+ * -> out [n H W, C] of the storage type (csrc/image_front.hip). */
 int morec_pixels_to_nhwc(const void* src, void* out, int n, int C, int H, int W, int src_u8, float mean, float std, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -994,14 +996,16 @@ int morec_probe(int32_t* out, void* stream);
 int morec_image_resize_u8(const uint8_t* src, const int64_t* meta, const int32_t* tables, uint8_t* out, int n, int R, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * The image catalogue on the device, a batch as its item ids (csrc/image_ids.hip): the indexed forms of the three kernels through
- * which decoded uint8 images enter a vision tower.  catalogue: uint8 [n_rows, R, R, channels] ([n_rows, H, W, C] for the NHWC form);
- * ids: int32 [n_img] on the device; the remaining arguments are the parent's.  Image k of the output is computed from catalogue
- * row ids[k], clamped into [0, n_rows - 1] (a bad id never reads outside the catalogue; hosts reject it before it gets here).
- * The arithmetic is the parent's, so the output is bit-equal to a row gather of the catalogue followed by the parent.  The MAE form
- * takes its kept patches from keep[k] and its pixels from row ids[k].  RGB catalogues with patch % 4 == 0 (H W C % 4 == 0) move 4
- * pixels (4 bytes) per thread; other shapes move single elements.  No atomics, one writer per output element.
- * Errors as the parents', judged before any launch; n_rows <= 0 or n_img <= 0: MOREC_E_ARG.
+ * The image catalogue on the device, a batch as its item ids (csrc/image_front.hip): the indexed forms of the three entry points
+ * through which decoded uint8 images enter a vision tower -- morec_swin_patchify_u8, morec_mae_patchify_keep_u8 and the uint8 case
+ * of morec_pixels_to_nhwc, the direct forms.  One kernel per layout serves both: the direct form reads image k of the pixel batch,
+ * the indexed form catalogue row ids[k].  catalogue: uint8 [n_rows, R, R, channels] ([n_rows, H, W, C] for the NHWC form); ids:
+ * int32 [n_img] on the device; the remaining arguments are the direct form's.  ids[k] is clamped into [0, n_rows - 1] (a bad id
+ * never reads outside the catalogue; hosts reject it before it gets here).  The output is bit-equal to a row gather of the catalogue
+ * followed by the direct form.  The MAE form takes its kept patches from keep[k] and its pixels from row ids[k].  In both forms RGB
+ * images with patch % 4 == 0 and ld_out % 4 == 0 (NHWC: H W C % 4 == 0), a source on 4 bytes and an output on 16 move 4 pixels
+ * (4 bytes) per thread; anything else moves single elements.  No atomics, one writer per output element.
+ * Errors as the direct forms', judged before any launch; ids == NULL, n_rows <= 0 or n_img <= 0: MOREC_E_ARG.
  * ------------------------------------------------------------------------------------------ */
 int morec_swin_patchify_u8_idx(const uint8_t* catalogue, const int32_t* ids, int n_rows, void* out, int n_img, int channels, int R,
                                int patch, int ld_out, float mean, float std, int dtype, void* stream);

@@ -3,8 +3,8 @@
 
     python scripts/image_ids_bench.py [--out profiles/image_ids.txt] [--rounds 5] [--skip swin,mae,resnet]
 
-(a) the input side alone, per front kernel: host gather of the batch's images into a page-locked buffer + H2D + the parent kernel, against
-    H2D of the int32 ids + the indexed kernel;
+(a) the input side alone, per front kernel: host gather of the batch's images into a page-locked buffer + H2D + the front kernel's direct form, against
+    H2D of the int32 ids + its indexed form (the same kernel reading the catalogue through the ids);
 (b) a whole autograd step (forward + backward of the tower, AdamW left out) of the MAE-base and ResNet-50 towers, and the fused Swin-T
     step (``TrainStep``; the host side goes through ``DeviceImageFeed`` one batch ahead, as the driver does), with the batch as gathered
     pixels and as ids.  The "pixels" side is the baseline: it runs only kernels and Python paths that the flag leaves as they were;
@@ -109,25 +109,25 @@ def main():
 
     # (a)
     keep = ops.mae_keep_ids(N_IMG, 196, 49, seed=7, device=DEV)
-    report(lines, "(a) input side, Swin / BEiT front (patch 4): gather + H2D + swin_patchify_u8  |  ids H2D + swin_patchify_u8_idx",
-           ab(sides(lambda k: ops.swin_patchify_u8(gathered(k), 4, DT), lambda k: ops.swin_patchify_u8_idx(cat.data, as_ids(k).ids, 4, DT)),
+    report(lines, "(a) input side, Swin / BEiT front (patch 4): gather + H2D + swin_patchify_u8  |  ids H2D + swin_patchify_u8(ids=)",
+           ab(sides(lambda k: ops.swin_patchify_u8(gathered(k), 4, DT), lambda k: ops.swin_patchify_u8(cat.data, 4, DT, ids=as_ids(k).ids)),
               a.rounds, a.steps))
-    report(lines, "(a) input side, MAE front (patch 16, 49 of 196 kept): gather + H2D + mae_patchify_keep_u8  |  ids H2D + ..._idx",
+    report(lines, "(a) input side, MAE front (patch 16, 49 of 196 kept): gather + H2D + mae_patchify_keep  |  ids H2D + mae_patchify_keep(ids=)",
            ab(sides(lambda k: ops.mae_patchify_keep(gathered(k), keep, 16, DT),
-                    lambda k: ops.mae_patchify_keep_u8_idx(cat.data, as_ids(k).ids, keep, 16, DT)), a.rounds, a.steps))
-    report(lines, "(a) input side, ResNet front: gather + H2D + pixels_to_nhwc  |  ids H2D + pixels_to_nhwc_idx",
-           ab(sides(lambda k: ops.pixels_to_nhwc(gathered(k), DT), lambda k: ops.pixels_to_nhwc_idx(cat.data, as_ids(k).ids, DT)),
+                    lambda k: ops.mae_patchify_keep(cat.data, keep, 16, DT, ids=as_ids(k).ids)), a.rounds, a.steps))
+    report(lines, "(a) input side, ResNet front: gather + H2D + pixels_to_nhwc  |  ids H2D + pixels_to_nhwc(ids=)",
+           ab(sides(lambda k: ops.pixels_to_nhwc(gathered(k), DT), lambda k: ops.pixels_to_nhwc(cat.data, DT, ids=as_ids(k).ids)),
               a.rounds, a.steps))
-    # the kernels alone, inputs resident: the indexed forms against gather-free parents
+    # the kernels alone, inputs resident: direct | indexed form of one kernel
     px0 = gathered(0)
     i0 = as_ids(0).ids
-    report(lines, "    kernel alone, Swin front: swin_patchify_u8 (pixels resident)  |  swin_patchify_u8_idx",
-           ab({"parent": lambda k: ops.swin_patchify_u8(px0, 4, DT), "indexed": lambda k: ops.swin_patchify_u8_idx(cat.data, i0, 4, DT)},
+    report(lines, "    kernel alone, Swin front (pixels resident): direct | indexed",
+           ab({"direct": lambda k: ops.swin_patchify_u8(px0, 4, DT), "indexed": lambda k: ops.swin_patchify_u8(cat.data, 4, DT, ids=i0)},
               a.rounds, 50))
-    report(lines, "    kernel alone, MAE front", ab({"parent": lambda k: ops.mae_patchify_keep(px0, keep, 16, DT),
-                                                     "indexed": lambda k: ops.mae_patchify_keep_u8_idx(cat.data, i0, keep, 16, DT)}, a.rounds, 50))
-    report(lines, "    kernel alone, ResNet front", ab({"parent": lambda k: ops.pixels_to_nhwc(px0, DT),
-                                                        "indexed": lambda k: ops.pixels_to_nhwc_idx(cat.data, i0, DT)}, a.rounds, 50))
+    report(lines, "    kernel alone, MAE front: direct | indexed", ab({"direct": lambda k: ops.mae_patchify_keep(px0, keep, 16, DT),
+                                                     "indexed": lambda k: ops.mae_patchify_keep(cat.data, keep, 16, DT, ids=i0)}, a.rounds, 50))
+    report(lines, "    kernel alone, ResNet front: direct | indexed", ab({"direct": lambda k: ops.pixels_to_nhwc(px0, DT),
+                                                        "indexed": lambda k: ops.pixels_to_nhwc(cat.data, DT, ids=i0)}, a.rounds, 50))
     del px0
     lines.append("")
 

@@ -11,7 +11,7 @@ from idvs.morec_amd import _lib, ops
 from idvs.morec_amd.data_utils import collate_bce_batch, collate_train_batch
 from idvs.morec_amd.parameters import check_images_on_device_args, parse_args
 
-E_ARG, E_UNSUPPORTED, E_DTYPE = -1, -3, -4      # include/morec_hip.h
+E_ARG, E_ALIGN, E_UNSUPPORTED, E_DTYPE = -1, -2, -3, -4      # include/morec_hip.h
 NAMES = ("morec_swin_patchify_u8_idx", "morec_mae_patchify_keep_u8_idx", "morec_pixels_to_nhwc_idx")
 
 
@@ -82,6 +82,65 @@ def test_nhwc_form_judges_arguments_before_any_launch():
     assert call(cat=None) == E_ARG and call(ids=None) == E_ARG and call(out=None) == E_ARG
     assert call(n_rows=0) == E_ARG and call(n_img=0) == E_ARG and call(H=0) == E_ARG
     assert call(dtype=7) == E_DTYPE
+
+
+# The direct entry points (pixels in batch order) share their kernels and launchers with the indexed ones; each keeps the outcomes of
+# its own argument ladder, as they were when each had a kernel of its own.
+def test_direct_swin_entry_judges_arguments_before_any_launch():
+    f = _lib.lib().morec_swin_patchify_u8
+    px, _, _, out = _bufs()
+    ok = dict(px=px, out=out, n_img=2, ch=3, R=8, patch=4, ld=48, std=0.5, dtype=_lib.F32)
+
+    def call(**kw):
+        a = dict(ok, **kw)
+        return f(a["px"], a["out"], a["n_img"], a["ch"], a["R"], a["patch"], a["ld"], 0.5, a["std"], a["dtype"], None)
+
+    assert call(px=None) == E_ARG and call(out=None) == E_ARG
+    assert call(n_img=0) == E_ARG and call(n_img=-2) == E_ARG and call(ch=0) == E_ARG and call(patch=0) == E_ARG
+    assert call(std=0.0) == E_ARG
+    assert call(R=10) == E_UNSUPPORTED          # R % patch
+    assert call(ld=47) == E_ALIGN               # rows shorter than channels * patch^2: the entry's only rule about the output
+    assert call(dtype=7) == E_DTYPE
+    assert call(R=10, dtype=7) == E_UNSUPPORTED and call(ld=47, dtype=7) == E_ALIGN and call(px=None, R=10) == E_ARG      # the ladder's order
+
+
+def test_direct_mae_entry_judges_arguments_before_any_launch():
+    f = _lib.lib().morec_mae_patchify_keep_u8
+    px, _, keep, out = _bufs()
+    ok = dict(px=px, keep=keep, out=out, n_img=2, ch=3, R=8, patch=4, len_keep=1, ld=48, std=0.5, dtype=_lib.F16)
+
+    def call(**kw):
+        a = dict(ok, **kw)
+        return f(a["px"], a["keep"], a["out"], a["n_img"], a["ch"], a["R"], a["patch"], a["len_keep"], a["ld"], 0.5, a["std"], a["dtype"], None)
+
+    assert call(px=None) == E_ARG and call(keep=None) == E_ARG and call(out=None) == E_ARG
+    assert call(n_img=0) == E_ARG and call(len_keep=0) == E_ARG
+    assert call(len_keep=5) == E_ARG            # more kept patches than the 2 x 2 grid has
+    assert call(R=10) == E_UNSUPPORTED
+    assert call(dtype=7) == E_DTYPE
+    assert call(R=12, patch=6, ld=108) == E_ALIGN      # patch % 4
+    assert call(out=out + 2) == E_ALIGN and call(out=out + 8) == E_ALIGN      # the output off 16 bytes
+    assert call(ld=47) == E_ALIGN and call(ld=52) == E_ALIGN      # short rows; rows that are not whole 16-byte lanes of fp16
+    assert call(std=0.0) == E_ARG
+    assert call(dtype=7, R=10) == E_DTYPE and call(std=0.0, out=out + 2) == E_ALIGN      # the ladder's order: dtype, shape, alignment, std
+
+
+def test_direct_nhwc_entry_judges_arguments_before_any_launch():
+    f = _lib.lib().morec_pixels_to_nhwc
+    px, _, _, out = _bufs()
+    ok = dict(px=px, out=out, n=2, ch=3, H=8, W=8, u8=1, std=0.5, dtype=_lib.BF16)
+
+    def call(**kw):
+        a = dict(ok, **kw)
+        return f(a["px"], a["out"], a["n"], a["ch"], a["H"], a["W"], a["u8"], 0.5, a["std"], a["dtype"], None)
+
+    assert call(px=None) == E_ARG and call(out=None) == E_ARG
+    assert call(n=0) == E_ARG and call(ch=0) == E_ARG and call(H=0) == E_ARG and call(W=-1) == E_ARG
+    assert call(std=0.0) == E_ARG and call(std=-1.0) == E_ARG and call(std=float("nan")) == E_ARG
+    assert call(dtype=7) == E_DTYPE
+    assert call(px=None, dtype=7) == E_ARG
+    # fp32 pixels take no normalisation: std is not judged
+    assert call(u8=0, px=None) == E_ARG and call(u8=0, n=0) == E_ARG and call(u8=0, dtype=7) == E_DTYPE and call(u8=0, std=0.0, dtype=7) == E_DTYPE
 
 
 # ------------------------------------------------------------------------------------------------ flag

@@ -1,7 +1,9 @@
 """-m gpu: ``--images_on_device`` on a real MI355X -- the image catalogue on the device, a batch as its item ids.
 
-* kernel parity: each indexed front kernel is bit-equal to ``catalogue.index_select(0, ids)`` + its parent, fp32 / bf16 / fp16, at image
-  counts on both sides of one grid pass, and clamps ids that were written into the device tensor directly;
+* kernel parity: the indexed form of each uint8 front kernel is bit-equal to its direct form over ``catalogue.index_select(0, ids)``, and
+  the direct form to the host reference (``image_front_ref``), fp32 / bf16 / fp16, at image counts on both sides of one grid pass; ids
+  that were written into the device tensor directly are clamped; the direct form's own edges: both paths of each front, a misaligned
+  source, padded output rows, kept-patch entries outside the grid;
 * the four vision towers, ``Model`` and ``BceModel``: an ``ImageIds`` batch gives the item vectors, the loss and every parameter gradient
   of the gathered pixel batch, bit for bit, in deterministic mode;
 * ``DeviceImageCatalogue``: chunked upload from a host array, one pass over an ``LmdbItemImages``, the refusal of a catalogue that does
@@ -21,6 +23,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import image_front_ref as ref  # noqa: E402
 import resnet_ref  # noqa: E402
 from idvs.morec_amd import ops  # noqa: E402
 from idvs.morec_amd.beit_engine import BeitShape  # noqa: E402
@@ -41,6 +44,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DT = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
 N_IMG = (1, 3, 65, 257)
 N_ROWS = (2, 7)
+# ToTensor + Normalize as the drivers use it, and a pair with mean != std: the parent commit's kernels were bit-equal to the host reference
+# under both, so both are held
+NORMS = ((0.5, 0.5), (0.485, 0.229))
 
 
 def _catalogue(n_rows, H, W, seed):
@@ -67,10 +73,13 @@ def _cases():
 @pytest.mark.parametrize("R,patch", [(8, 4), (32, 16), (56, 4), (6, 3)])
 def test_swin_form_equals_gather_plus_parent(R, patch, dt):
     cats = {n: _catalogue(n, R, R, 10 + n) for n in N_ROWS}
-    for n_rows, n_img, name, ids in _cases():
-        want = ops.swin_patchify_u8(cats[n_rows].index_select(0, ids.long()), patch, DT[dt])
-        got = ops.swin_patchify_u8_idx(cats[n_rows], ids, patch, DT[dt])
-        assert got.dtype == DT[dt] and torch.equal(got, want), (n_rows, n_img, name)
+    for norm in NORMS:
+        host = {n: ref.patch_rows(c.cpu(), patch, DT[dt], *norm).view(n, (R // patch) ** 2, -1).to(DEV) for n, c in cats.items()}
+        for n_rows, n_img, name, ids in _cases():
+            want = ops.swin_patchify_u8(cats[n_rows].index_select(0, ids.long()), patch, DT[dt], *norm)
+            got = ops.swin_patchify_u8(cats[n_rows], patch, DT[dt], *norm, ids=ids)
+            assert got.dtype == DT[dt] and torch.equal(got, want), (norm, n_rows, n_img, name)
+            assert want.dtype == DT[dt] and torch.equal(want, host[n_rows][ids.long()].reshape(want.shape)), (norm, n_rows, n_img, name)
 
 
 @pytest.mark.parametrize("dt", list(DT))
@@ -79,15 +88,19 @@ def test_mae_form_equals_gather_plus_parent(R, patch, len_keep, dt):
     N = (R // patch) ** 2
     cats = {n: _catalogue(n, R, R, 20 + n) for n in N_ROWS}
     noise = torch.from_numpy(np.random.default_rng(77).random((max(N_IMG), N), dtype=np.float32)).to(DEV)
-    for n_rows, n_img, name, ids in _cases():
-        keep = ops.mae_keep_ids(n_img, N, len_keep, noise=noise[:n_img].contiguous())
-        want = ops.mae_patchify_keep(cats[n_rows].index_select(0, ids.long()), keep, patch, DT[dt])
-        got = ops.mae_patchify_keep_u8_idx(cats[n_rows], ids, keep, patch, DT[dt])
-        assert torch.equal(got, want), (n_rows, n_img, name)
+    for norm in NORMS:
+        host = {n: ref.patch_rows(c.cpu(), patch, DT[dt], *norm).to(DEV) for n, c in cats.items()}
+        for n_rows, n_img, name, ids in _cases():
+            keep = ops.mae_keep_ids(n_img, N, len_keep, noise=noise[:n_img].contiguous())
+            want = ops.mae_patchify_keep(cats[n_rows].index_select(0, ids.long()), keep, patch, DT[dt], *norm)
+            got = ops.mae_patchify_keep(cats[n_rows], keep, patch, DT[dt], *norm, ids=ids)
+            assert torch.equal(got, want), (norm, n_rows, n_img, name)
+            rows = (ids.long()[:, None] * N + keep.long()).reshape(-1)      # patch keep[k, j] of catalogue row ids[k]
+            assert want.dtype == DT[dt] and torch.equal(want, host[n_rows][rows]), (norm, n_rows, n_img, name)
     # the keep entries decide the patches, the ids the pixels: two images of ONE row with different kept patches differ
     if len_keep < N:
         keep = torch.tensor([[0], [N - 1]], device=DEV, dtype=torch.int32).repeat(1, len_keep)
-        rows = ops.mae_patchify_keep_u8_idx(cats[2], torch.tensor([1, 1], device=DEV, dtype=torch.int32), keep, patch, DT[dt])
+        rows = ops.mae_patchify_keep(cats[2], keep, patch, DT[dt], ids=torch.tensor([1, 1], device=DEV, dtype=torch.int32))
         full = ops.swin_patchify_u8(cats[2][1:2], patch, DT[dt])
         assert torch.equal(rows[0], full[0]) and torch.equal(rows[len_keep], full[N - 1])
 
@@ -97,31 +110,41 @@ def test_mae_form_equals_gather_plus_parent(R, patch, len_keep, dt):
 @pytest.mark.parametrize("H", [8, 64, 5])
 def test_nhwc_form_equals_gather_plus_parent(H, dt):
     cats = {n: _catalogue(n, H, H, 30 + n) for n in N_ROWS}
-    for n_rows, n_img, name, ids in _cases():
-        want = ops.pixels_to_nhwc(cats[n_rows].index_select(0, ids.long()), DT[dt])
-        got = ops.pixels_to_nhwc_idx(cats[n_rows], ids, DT[dt])
-        assert torch.equal(got, want), (n_rows, n_img, name)
+    for norm in NORMS:
+        host = {n: ref.nhwc_rows(c.cpu(), DT[dt], *norm).view(n, H * H, 3).to(DEV) for n, c in cats.items()}
+        for n_rows, n_img, name, ids in _cases():
+            want = ops.pixels_to_nhwc(cats[n_rows].index_select(0, ids.long()), DT[dt], *norm)
+            got = ops.pixels_to_nhwc(cats[n_rows], DT[dt], *norm, ids=ids)
+            assert torch.equal(got, want), (norm, n_rows, n_img, name)
+            assert want.dtype == DT[dt] and torch.equal(want, host[n_rows][ids.long()].reshape(want.shape)), (norm, n_rows, n_img, name)
 
 
 def test_forms_beyond_one_pass_of_the_grid():
     """The launches are capped at 8192 blocks of 256 threads; image counts whose work exceeds 2 097 152 threads take the grid-stride loop
     round a second time: 2688 images x 784 threads (Swin form, 56 / 4), 8320 x 256 (MAE form, 64 / 16 keeping 4), 704 x 3072 (ResNet
-    form, 64 x 64)."""
+    form, 64 x 64).  Both forms: the indexed one equals the direct one over the gathered pixels, the direct one the host reference (the MAE
+    front: a row gather of the Swin rows)."""
     rng = np.random.default_rng(99)
     ids = lambda n: torch.from_numpy(rng.integers(0, 7, n)).to(DEV, torch.int32)
     cat = _catalogue(7, 56, 56, 50)
     i = ids(2688)
     assert 2688 * 14 * 14 * 4 > 8192 * 256
-    assert torch.equal(ops.swin_patchify_u8_idx(cat, i, 4, torch.float16), ops.swin_patchify_u8(cat.index_select(0, i.long()), 4, torch.float16))
+    direct = ops.swin_patchify_u8(cat.index_select(0, i.long()), 4, torch.float16)
+    assert torch.equal(ops.swin_patchify_u8(cat, 4, torch.float16, ids=i), direct)
+    assert torch.equal(direct, ref.patch_rows(cat.cpu(), 4, torch.float16).view(7, 196, 48).to(DEV)[i.long()].reshape(direct.shape))
     cat = _catalogue(7, 64, 64, 51)
     i = ids(8320)
     keep = ops.mae_keep_ids(8320, 16, 4, seed=3, device=DEV)
     assert 8320 * 4 * 16 * 4 > 8192 * 256
-    assert torch.equal(ops.mae_patchify_keep_u8_idx(cat, i, keep, 16, torch.float16),
-                       ops.mae_patchify_keep(cat.index_select(0, i.long()), keep, 16, torch.float16))
+    px = cat.index_select(0, i.long())
+    direct = ops.mae_patchify_keep(px, keep, 16, torch.float16)
+    assert torch.equal(ops.mae_patchify_keep(cat, keep, 16, torch.float16, ids=i), direct)
+    assert torch.equal(direct, ref.keep_rows(ops.swin_patchify_u8(px, 16, torch.float16), keep, 16))
     i = ids(704)
     assert 704 * 64 * 64 * 3 // 4 > 8192 * 256
-    assert torch.equal(ops.pixels_to_nhwc_idx(cat, i, torch.float16), ops.pixels_to_nhwc(cat.index_select(0, i.long()), torch.float16))
+    direct = ops.pixels_to_nhwc(cat.index_select(0, i.long()), torch.float16)
+    assert torch.equal(ops.pixels_to_nhwc(cat, torch.float16, ids=i), direct)
+    assert torch.equal(direct, ref.nhwc_rows(cat.cpu(), torch.float16).view(7, 64 * 64, 3).to(DEV)[i.long()].reshape(direct.shape))
 
 
 @pytest.mark.parametrize("n_rows", N_ROWS)
@@ -132,13 +155,104 @@ def test_ids_written_on_the_device_are_clamped(n_rows):
     good = torch.tensor([0, n_rows - 1, 1], device=DEV, dtype=torch.int32)
     keep = torch.tensor([[1], [2], [3]], device=DEV, dtype=torch.int32)
     for dt in DT.values():
-        assert torch.equal(ops.swin_patchify_u8_idx(cat, bad, 16, dt), ops.swin_patchify_u8_idx(cat, good, 16, dt))
-        assert torch.equal(ops.swin_patchify_u8_idx(cat, bad, 16, dt), ops.swin_patchify_u8(cat[good.long()], 16, dt))
-        assert torch.equal(ops.mae_patchify_keep_u8_idx(cat, bad, keep, 16, dt), ops.mae_patchify_keep(cat[good.long()], keep, 16, dt))
-        assert torch.equal(ops.pixels_to_nhwc_idx(cat, bad, dt), ops.pixels_to_nhwc(cat[good.long()], dt))
+        assert torch.equal(ops.swin_patchify_u8(cat, 16, dt, ids=bad), ops.swin_patchify_u8(cat, 16, dt, ids=good))
+        assert torch.equal(ops.swin_patchify_u8(cat, 16, dt, ids=bad), ops.swin_patchify_u8(cat[good.long()], 16, dt))
+        assert torch.equal(ops.swin_patchify_u8(cat, 16, dt, ids=bad), ref.patch_rows(cat[good.long()].cpu(), 16, dt).to(DEV))
+        assert torch.equal(ops.mae_patchify_keep(cat, keep, 16, dt, ids=bad), ops.mae_patchify_keep(cat[good.long()], keep, 16, dt))
+        assert torch.equal(ops.mae_patchify_keep(cat[good.long()], keep, 16, dt),
+                           ref.keep_rows(ref.patch_rows(cat[good.long()].cpu(), 16, dt), keep.cpu(), 4).to(DEV))
+        assert torch.equal(ops.pixels_to_nhwc(cat, dt, ids=bad), ops.pixels_to_nhwc(cat[good.long()], dt))
+        assert torch.equal(ops.pixels_to_nhwc(cat[good.long()], dt), ref.nhwc_rows(cat[good.long()].cpu(), dt).to(DEV))
     # the same ids from the host raise instead
     with pytest.raises(Exception, match="outside the catalogue"):
-        ops.swin_patchify_u8_idx(cat, np.array([-5, n_rows + 3, 1]), 16, torch.float32)
+        ops.swin_patchify_u8(cat, 16, torch.float32, ids=np.array([-5, n_rows + 3, 1]))
+
+
+# ------------------------------------------------------------------------------------------------ the direct form's own edges
+# The direct form (pixels in batch order, no ids) runs the same kernels, so it has their two paths: 4 pixels per thread (3 channels, patch
+# % 4 == 0, output rows a multiple of 4 elements long, source on 4 bytes, output on 16), single elements otherwise.
+@pytest.mark.parametrize("norm", NORMS)
+@pytest.mark.parametrize("dt", list(DT))
+def test_direct_form_on_both_paths_equals_the_host_reference(dt, norm):
+    d = DT[dt]
+    for n in (1, 3):
+        for R, patch in ((8, 4), (32, 16), (6, 3)):      # wide, wide, single elements (patch % 4)
+            u8 = _catalogue(n, R, R, 60 + R)
+            assert torch.equal(ops.swin_patchify_u8(u8, patch, d, *norm), ref.patch_rows(u8.cpu(), patch, d, *norm).to(DEV)), (n, R, patch)
+        grey = _catalogue(n, 8, 8, 61)[..., :1].contiguous()      # [n, 8, 8, 1]: channels != 3, single elements
+        assert torch.equal(ops.swin_patchify_u8(grey, 4, d, *norm), ref.patch_rows(grey.cpu(), 4, d, *norm).to(DEV)), n
+        for H in (8, 5):      # wide; H W C % 4 != 0, single elements
+            u8 = _catalogue(n, H, H, 62 + H)
+            assert torch.equal(ops.pixels_to_nhwc(u8, d, *norm), ref.nhwc_rows(u8.cpu(), d, *norm).to(DEV)), (n, H)
+        for R, patch, len_keep in ((32, 16, 1), (64, 16, 4)):
+            N = (R // patch) ** 2
+            u8 = _catalogue(n, R, R, 63 + R)
+            keep = ops.mae_keep_ids(n, N, len_keep, seed=n, device=DEV)
+            want = ref.keep_rows(ref.patch_rows(u8.cpu(), patch, d, *norm), keep.cpu(), N).to(DEV)
+            assert torch.equal(ops.mae_patchify_keep(u8, keep, patch, d, *norm), want), (n, R)
+
+
+def _u8_at_offset(n, R, offset, seed):
+    """uint8 [n, R, R, 3] as a view ``offset`` bytes into a larger allocation (torch's allocations start on 512 bytes)"""
+    buf = torch.from_numpy(np.random.default_rng(seed).integers(0, 256, n * R * R * 3 + 16, dtype=np.uint8)).to(DEV)
+    u8 = buf[offset:offset + n * R * R * 3].view(n, R, R, 3)
+    assert buf.data_ptr() % 16 == 0 and u8.data_ptr() == buf.data_ptr() + offset and u8.is_contiguous()
+    return u8
+
+
+@pytest.mark.parametrize("dt", list(DT))
+def test_direct_form_from_a_misaligned_source(dt):
+    """A source one byte into an allocation cannot be read as dwords: the launch takes single elements; at offset 4 it takes the 4-pixel path.
+    The same bytes give the same rows, the host reference's, through all three fronts."""
+    d, n, R, patch = DT[dt], 3, 8, 4
+    keep = torch.tensor([[0, 3], [3, 1], [2, 2]], device=DEV, dtype=torch.int32)
+    outs = []
+    for offset in (1, 4):
+        u8 = _u8_at_offset(n, R, offset, 70)      # one seed: the two views hold different bytes of one buffer
+        host = ref.patch_rows(u8.cpu(), patch, d)
+        assert torch.equal(ops.swin_patchify_u8(u8, patch, d), host.to(DEV)), offset
+        assert torch.equal(ops.mae_patchify_keep(u8, keep, patch, d), ref.keep_rows(host, keep.cpu(), 4).to(DEV)), offset
+        assert torch.equal(ops.pixels_to_nhwc(u8, d), ref.nhwc_rows(u8.cpu(), d).to(DEV)), offset
+        # the same pixels at an aligned address: the path taken does not show in the rows
+        same = u8.clone()
+        assert same.data_ptr() % 16 == 0 and torch.equal(ops.swin_patchify_u8(same, patch, d), ops.swin_patchify_u8(u8, patch, d))
+        assert torch.equal(ops.mae_patchify_keep(same, keep, patch, d), ops.mae_patchify_keep(u8, keep, patch, d))
+        assert torch.equal(ops.pixels_to_nhwc(same, d), ops.pixels_to_nhwc(u8, d))
+
+
+@pytest.mark.parametrize("dt", list(DT))
+@pytest.mark.parametrize("pad", [4, 1])
+def test_swin_entry_leaves_the_padding_of_wider_output_rows(pad, dt):
+    """``morec_swin_patchify_u8`` with ``ld_out = K + 4`` (rows still a multiple of 4 elements: the 4-pixel path) and ``K + 1`` (single
+    elements): the K columns are the host reference's, the columns beyond them keep what they held."""
+    from idvs.morec_amd import _lib
+    d, n, R, patch = DT[dt], 3, 8, 4
+    K, rows = 3 * patch * patch, n * (R // patch) ** 2
+    u8 = _catalogue(n, R, R, 80)
+    out = torch.full((rows, K + pad), -7.0, device=DEV, dtype=d)
+    rc = _lib.lib().morec_swin_patchify_u8(u8.data_ptr(), out.data_ptr(), n, 3, R, patch, K + pad, 0.5, 0.5, ops.code(d),
+                                           torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert rc == 0 and out.data_ptr() % 16 == 0
+    assert torch.equal(out[:, :K], ref.patch_rows(u8.cpu(), patch, d).to(DEV))
+    assert bool((out[:, K:] == -7.0).all())
+
+
+@pytest.mark.parametrize("dt", list(DT))
+def test_mae_keep_entry_outside_the_grid_leaves_a_zero_row(dt):
+    """-1 and G * G in ``keep``: a zero row, on the 4-pixel path and (source one byte off) on the single-element path, direct and indexed."""
+    d, n, R, patch = DT[dt], 3, 8, 4
+    N = (R // patch) ** 2
+    keep = torch.tensor([[-1, 1], [2, N], [0, 3]], device=DEV, dtype=torch.int32)
+    ids = torch.tensor([2, 0, 2], device=DEV, dtype=torch.int32)
+    for offset in (0, 1):
+        cat = _u8_at_offset(n, R, offset, 90)
+        want = ref.keep_rows(ref.patch_rows(cat.cpu(), patch, d), keep.cpu(), N).to(DEV)
+        assert not bool(want[0].any()) and not bool(want[3].any()) and bool(want[1].any())
+        assert torch.equal(ops.mae_patchify_keep(cat, keep, patch, d), want), offset
+        px = cat.index_select(0, ids.long())
+        want = ref.keep_rows(ref.patch_rows(px.cpu(), patch, d), keep.cpu(), N).to(DEV)
+        assert torch.equal(ops.mae_patchify_keep(cat, keep, patch, d, ids=ids), want), offset
 
 
 # ------------------------------------------------------------------------------------------------ towers
